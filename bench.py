@@ -14,7 +14,8 @@ bases of the timed steps / wall time (max over ranks), summed over ranks.  Reads
 index is replicated in every GPU's HBM; there is no collective on the data path, only
 the timing barrier.
 
-One JSON line on stdout (rank 0):
+One JSON line on stdout (rank 0): metric, value, unit, higher_is_better, dtype, ms_per_step (wall time of one timed step) and
+the workload's config.  With --full it also holds:
   roofline      the graded Occ-rank kernel (kmer_grid_kernel) of the same run: algorithmic bytes (rank blocks +
                 k-mer table lines, 64 B each, counted on the device) / its HIP-event time on the ctx stream
   roofline_extra  the same pricing for the FM-extension kernels of the walk-parallel flow (wp_prepare / wp_begin / wp_extend: where
@@ -24,6 +25,8 @@ One JSON line on stdout (rank 0):
   parity_sample the oracle's corrected strings and integer counters for those sampled reads compared with what
                 the GPU produced for the same reads in the timed run; a mismatch makes the process exit 3
 `--stage seeds` times configs[1] (Occ-rank + LongReadProbe kernels only) and says so in `metric`.
+`--dump-outputs DIR` writes what the last timed step returned to its caller as DIR/<name>.npy (see dump_outputs); the inputs
+are seeded, so two builds run with the same arguments can be compared array for array.
 """
 from __future__ import annotations
 
@@ -87,12 +90,19 @@ def main():
     ap.add_argument("--pipeline", action="store_true",
                     help="several concurrent parts: no join per step (see run_steps); measured 65.8 vs 59.9 corrected Mbases/s, with the Occ-rank "
                          "kernel's own time doubled by the contention")
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the cpu_baseline leg (0 disables it and parity_sample)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the cpu_baseline leg of --full (0 disables it and parity_sample)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="oracle threads of the cpu_baseline leg (0 = all host cores of this process)")
     ap.add_argument("--stage", choices=list(STAGE_INFO), default="correct",
                     help="correct (default): BASELINE configs[2], the whole per-read path with the DP fallback; correct-nodp: the "
                          "same with --nodp; seeds: configs[1], Occ-rank + LongReadProbe kernels only")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: roofline / roofline_extra (with a copy-peak "
+                         "measurement of its own), and on one GPU the cpu_baseline leg with its parity_sample")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's outputs of the last timed step as DIR/<name>.npy (float64 / float32)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     sinfo = STAGE_INFO[args.stage]
 
     # The two concurrent parts of a step use ~10 HIP streams between them (main + yield + MSA side streams each); the ROCm runtime
@@ -177,7 +187,8 @@ def main():
         f"{int(off[-1]) / 1e6:.1f} Mbases in all")
 
     totals = {"walks": 0, "fm": 0, "dp": 0, "corrected_reads": 0, "corrected_bases": 0, "not_ok": 0}
-    kept = {}            # results of part 0 of sub-batch 0 from its latest pass (parity_sample compares them with the oracle)
+    kept = {}            # --full: results of part 0 of sub-batch 0 from its latest pass (parity_sample compares them with the oracle)
+    last = {}            # part j -> (res, poff, out) of its latest timed pass: after the timed steps, the last step's (--dump-outputs)
 
     def correct_part(g, j, timed, acc):
         b = groups[g][j]
@@ -185,7 +196,8 @@ def main():
         if timed:
             acc.append((sum(r.total_walk_num for r in res), sum(r.fm_num for r in res), sum(r.dp_num for r in res),
                         sum(1 for r in res if r.merge), int(out.size), sum(1 for r in res if r.status != 0)))
-        if g == 0 and j == 0:
+            last[j] = (res, poff, out)    # views of the batch's own buffers: only this batch's next correct() overwrites them
+        if args.full and g == 0 and j == 0:
             kept["res"], kept["poff"], kept["out"] = res, poff.copy(), out.copy()
 
     def part_work(g, j, timed, acc):
@@ -272,6 +284,16 @@ def main():
 
     # max over ranks of the elapsed time; sum over ranks of the bases processed
     elapsed_max, total_bases = lrdist.combine(elapsed, float(my_bases), device="cpu" if one_device else "cuda")
+    if rank == 0 and args.dump_outputs:
+        g_last = (args.warmup + args.steps - 1) % len(groups)
+        if args.stage == "seeds":
+            parts = [b.seeds(want_attribute=False)[:2] for b in groups[g_last]]
+        else:
+            parts = [last[j] for j in range(n_streams)]
+        t = time.time()
+        written = dump_outputs(Path(args.dump_outputs), args.stage, parts)
+        log(f"--dump-outputs: {len(written)} arrays of step {args.steps}/{args.steps} ({sum(written.values()) / 1e6:.1f} MB) "
+            f"written to {args.dump_outputs} in {time.time() - t:.1f}s")
 
     class Agg:
         def __init__(self, which):
@@ -294,22 +316,6 @@ def main():
     result = None
     rc = 0
     if rank == 0:
-        roof = roofline_of(K_GRID, "kmer_grid_kernel")
-        # HBM-side traffic of the same kernel on the same launch shape comes from the committed rocprofv3 --pmc passes (counters
-        # cannot be sampled from inside the process); null for any other workload
-        pmc = REPO / "profiles" / "r03_pmc" / "traffic.json"
-        roof["peak_measured"] = measured_copy_peak(torch)
-        roof["frac_of_measured"] = roof["achieved"] / roof["peak_measured"] if roof["peak_measured"] else None
-        roof["peak_measured_how"] = "device-to-device copy of 4 GiB inside this run (read + write bytes / HIP-event time, best of 5)"
-        if pmc.exists():
-            pj = json.loads(pmc.read_text())
-            # the counters were collected for one build of the kernel: only quote them for that build
-            same_build = pj.get("kernel_source_sha256") == grid_kernel_source_hash()
-            for shape in pj.get("shapes", [pj]):
-                if same_build and shape.get("reads_per_launch") == batches[0].n_reads and shape.get("index_reads") == n_reads and shape.get("read_len") == args.read_len:
-                    roof["traffic"] = shape["traffic_bytes_per_launch"] / 1e9
-                    roof["traffic_unit"] = "GB per launch (separate rocprofv3 --pmc passes, corrected as MI355X_MICROARCH.md prescribes)"
-                    roof["traffic_source"] = shape["source"]
         value = total_bases / elapsed_max / 1e6
         stage_ms = {"kmer_grid": Agg(K_GRID).total_ms / args.steps, "seed_scan_group": Agg(K_SEEDS).total_ms / args.steps}
         if args.stage != "seeds":
@@ -355,11 +361,28 @@ def main():
                 "reads_per_gpu": n_reads,
                 "parallelism": f"reads sharded x{world}, index replicated, no data-path collective",
             },
-            "roofline": roof,
         }
-        if args.stage != "seeds":
-            result["roofline_extra"] = [roofline_of(K_EXTEND, "wp_prepare + wp_begin + wp_extend kernels (one timed group per round)")]
-        if world == 1 and args.cpu_seconds > 0:
+        if args.full:
+            roof = roofline_of(K_GRID, "kmer_grid_kernel")
+            # HBM-side traffic of the same kernel on the same launch shape comes from the committed rocprofv3 --pmc passes (counters
+            # cannot be sampled from inside the process); null for any other workload
+            pmc = REPO / "profiles" / "r03_pmc" / "traffic.json"
+            roof["peak_measured"] = measured_copy_peak(torch)
+            roof["frac_of_measured"] = roof["achieved"] / roof["peak_measured"] if roof["peak_measured"] else None
+            roof["peak_measured_how"] = "device-to-device copy of 4 GiB inside this run (read + write bytes / HIP-event time, best of 5)"
+            if pmc.exists():
+                pj = json.loads(pmc.read_text())
+                # the counters were collected for one build of the kernel: only quote them for that build
+                same_build = pj.get("kernel_source_sha256") == grid_kernel_source_hash()
+                for shape in pj.get("shapes", [pj]):
+                    if same_build and shape.get("reads_per_launch") == batches[0].n_reads and shape.get("index_reads") == n_reads and shape.get("read_len") == args.read_len:
+                        roof["traffic"] = shape["traffic_bytes_per_launch"] / 1e9
+                        roof["traffic_unit"] = "GB per launch (separate rocprofv3 --pmc passes, corrected as MI355X_MICROARCH.md prescribes)"
+                        roof["traffic_source"] = shape["source"]
+            result["roofline"] = roof
+            if args.stage != "seeds":
+                result["roofline_extra"] = [roofline_of(K_EXTEND, "wp_prepare + wp_begin + wp_extend kernels (one timed group per round)")]
+        if args.full and world == 1 and args.cpu_seconds > 0:
             cb, ps = cpu_baseline(units, n_reads, n_sym, params, bases, off, batches[0].n_reads, args, kept, batches[0])
             result["cpu_baseline"] = cb
             if ps is not None:
@@ -378,6 +401,73 @@ def main():
     if rc:
         log("parity_sample: the GPU results differ from the CPU oracle's for the sampled reads")
         sys.exit(rc)
+
+
+DUMP_SAMPLE_READS = 512          # reads of the step whose corrected bases / seeds are written out in full
+DUMP_SAMPLE_BYTES = 32 << 20     # at most this much of sampled bases (4 B each) or seeds (64 B each), so that a dump stays < 64 MB
+DUMP_SEED = 0x5EED0003
+READ_RESULT_COLUMNS = ("merge", "n_pieces", "total_reads_len", "corrected_len", "total_seed_num", "total_walk_num", "high_error_num",
+                       "exceed_depth_num", "exceed_leave_num", "fm_num", "dp_num", "seed_dis", "status")
+
+
+def dump_sample(n_reads: int, nbytes: np.ndarray) -> np.ndarray:
+    """A fixed, seeded sample of up to DUMP_SAMPLE_READS of the step's reads (sorted), cut to DUMP_SAMPLE_BYTES of output in all."""
+    pick = np.random.default_rng(DUMP_SEED).permutation(n_reads)[:DUMP_SAMPLE_READS]
+    keep = np.cumsum(nbytes[pick]) <= DUMP_SAMPLE_BYTES
+    return np.sort(pick[keep])
+
+
+def dump_outputs(out_dir: Path, stage: str, parts) -> dict:
+    """Writes what the last timed step returned to its caller, its concurrent parts joined in read order, as out_dir/<name>.npy.
+    Every integer is below 2**53 and is written exactly as float64; bases are their ASCII codes as float32.
+      correct stages (parts = [(ReadResult[n], piece offsets, corrected bytes)] per part):
+        read_results   [n_reads, 13]  READ_RESULT_COLUMNS of every read of the step
+        piece_lengths  [n_pieces]     length of every corrected piece
+        piece_crc32    [n_pieces]     zlib.crc32 of every corrected piece
+        sample_reads   [S]            the sampled reads (index within the step)
+        sample_bases   [..]           their pieces' bases, read after read
+      seeds (parts = [(seed count uint32[n], seeds SEED_DTYPE[m])] per part):
+        seed_count     [n_reads]      seeds of every read of the step
+        sample_reads   [S]            the sampled reads
+        sample_seeds   [.., 8]        every field of every seed of the sampled reads, read after read
+    Returns {name: bytes written}."""
+    import zlib
+
+    arrays = {}
+    if stage == "seeds":
+        count = np.concatenate([c for c, _ in parts]).astype(np.int64)
+        seeds = np.concatenate([s for _, s in parts])
+        first = np.concatenate([[0], np.cumsum(count)])
+        sample = dump_sample(count.size, count * 64)
+        rows = np.concatenate([np.arange(first[r], first[r + 1]) for r in sample]) if sample.size else np.zeros(0, dtype=np.int64)
+        arrays["seed_count"] = count.astype(np.float64)
+        arrays["sample_reads"] = sample.astype(np.float64)
+        arrays["sample_seeds"] = np.stack([seeds[f][rows] for f in seeds.dtype.names], axis=1).astype(np.float64)
+    else:
+        reads, lengths, crcs, spans = [], [], [], []     # spans: (part, first byte, end byte) of every read's corrected pieces
+        for j, (res, poff, out) in enumerate(parts):
+            rr = np.ctypeslib.as_array(res)
+            poff = poff.astype(np.int64)
+            reads.append(np.stack([rr[f] for f in READ_RESULT_COLUMNS], axis=1).astype(np.float64))
+            lengths.append(np.diff(poff))
+            buf = memoryview(out)
+            crcs.append(np.array([zlib.crc32(buf[a: b]) for a, b in zip(poff[:-1].tolist(), poff[1:].tolist())], dtype=np.float64))
+            first = rr["piece_first"].astype(np.int64)
+            spans.append(np.stack([np.full(first.size, j), poff[first], poff[first + rr["n_pieces"]]], axis=1))
+        spans = np.concatenate(spans)
+        sample = dump_sample(len(spans), (spans[:, 2] - spans[:, 1]) * 4)
+        arrays["read_results"] = np.concatenate(reads)
+        arrays["piece_lengths"] = np.concatenate(lengths).astype(np.float64)
+        arrays["piece_crc32"] = np.concatenate(crcs)
+        arrays["sample_reads"] = sample.astype(np.float64)
+        arrays["sample_bases"] = np.concatenate([np.zeros(0, dtype=np.uint8)] +
+                                                [parts[j][2][lo: hi] for j, lo, hi in spans[sample]]).astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, f"--dump-outputs would write {total} bytes"
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out_dir / f"{name}.npy", a)
+    return {name: a.nbytes for name, a in arrays.items()}
 
 
 def grid_kernel_source_hash() -> str:

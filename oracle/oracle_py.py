@@ -1,6 +1,6 @@
 """ctypes loaders for the CPU checker libraries -- TEST INFRASTRUCTURE ONLY.
 
-Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module.
+Only tests/, __graft_entry__ (build() and smoke()) and bench.py's cpu_baseline leg may import this module.
 
   Oracle  -> oracle/_build/liblrsc_oracle.so   (our CPU restatement of the reference algorithm)
   Ref     -> oracle/_ref/liblrsc_ref.so        (the reference's own sources, compiled by oracle/Makefile;
@@ -9,6 +9,7 @@ Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import 
 from __future__ import annotations
 
 import ctypes as C
+import os
 import subprocess
 from pathlib import Path
 
@@ -27,9 +28,11 @@ def build_oracle():
 
 
 def build_ref(reference: str = "/root/reference") -> bool:
-    if not Path(reference).is_dir():
+    if not os.access(reference, os.R_OK | os.X_OK) or not os.path.isdir(reference):      # absent, or not this user's to read
         return REF_SO.exists()
-    subprocess.run(["make", "-C", str(HERE), "ref", "-j8", f"REF={reference}"], check=True, capture_output=True)
+    r = subprocess.run(["make", "-C", str(HERE), "ref", "-j8", f"REF={reference}"], capture_output=True, text=True)
+    if r.returncode != 0:
+        raise RuntimeError(f"make ref in {HERE} failed:\n{r.stdout[-4000:]}\n{r.stderr[-4000:]}")
     return REF_SO.exists()
 
 
