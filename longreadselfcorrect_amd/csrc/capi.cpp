@@ -1498,7 +1498,6 @@ struct WpScratch {
     hipStream_t side[2] = {nullptr, nullptr};
     hipEvent_t ev_side[2] = {nullptr, nullptr}, ev_ready = nullptr;
     DevBuf<unsigned long long> d_prof;
-    DevBuf<uint8_t> d_coop, d_coop_side;
     DevBuf<WpSched> d_sched;
     DevBuf<uint32_t> d_sched_lists[2];
     DevArena persist;
@@ -1640,8 +1639,10 @@ static int batch_correct_wp(lrsc_ctx* ctx, lrsc_batch* b, lrsc_read_result* res,
 
     uint32_t mid_stride = 64, long_mode = 0;
     if(const char* ev = std::getenv("LRSC_WP_LONG_MODE")) long_mode = (uint32_t)std::atoi(ev);
-    bool coop_helpers = false;                       // experiment: run-ahead helper lanes in the one-walk-per-wavefront launches
-    if(const char* ev = std::getenv("LRSC_WP_COOP")) coop_helpers = std::atoi(ev) != 0;
+    // one-walk-per-wavefront launches: 1 = the frontier across the wavefront (wp_extend_wave_kernel), 0 = lane 0 walks alone
+    // (wp_extend_kernel); 2 = test hook: every extension launch goes through wp_extend_wave_kernel at stride 64
+    uint32_t wave_mode = 1;
+    if(const char* ev = std::getenv("LRSC_WP_WAVE")) wave_mode = (uint32_t)std::min(2, std::max(0, std::atoi(ev)));
     uint32_t leaves_in_lds = 0;                      // measured: 77.5-77.7 vs 79.1-80.3 corrected Mbases/s with the leaves in LDS (the DP stage beside it wants the LDS)
     if(const char* ev = std::getenv("LRSC_WP_LEAVES_LDS")) leaves_in_lds = std::atoi(ev) != 0;
     uint32_t long_first_div = 8;
@@ -1653,6 +1654,7 @@ static int batch_correct_wp(lrsc_ctx* ctx, lrsc_batch* b, lrsc_read_result* res,
     uint64_t side_div = 2;                                                   // the side launch's share of the wavefront slots: 1 / side_div
     auto extend_range = [&](WpArgs x, const uint32_t* list, const WpRequest* reqs, uint32_t count, uint32_t pathw, hipStream_t st, int which, uint32_t stride) -> hipError_t {
         if(count == 0) return hipSuccess;
+        if(wave_mode == 2) stride = 64;
         const WpLaneLayout LL = wp_lane_layout(lbytes, pathw);
         // wavefront slots: the side launches (which != 0) and the bulk launch are persistent and share the device, so each gets a share
         // of the resident wavefronts -- a launch that fills every slot first would keep the others out until it ends
@@ -1671,13 +1673,7 @@ static int batch_correct_wp(lrsc_ctx* ctx, lrsc_batch* b, lrsc_read_result* res,
         x.queue = ws.d_small.p + 8 + which;
         e2 = hipMemsetAsync(x.queue, 0, sizeof(uint32_t), st);
         if(e2 != hipSuccess) return e2;
-        if(coop_helpers && stride == 64) {
-            // one walk per wavefront with run-ahead helper lanes (wp_extend_coop_kernel): a private leaf buffer per lane
-            DevBuf<uint8_t>& cb = which ? ws.d_coop_side : ws.d_coop;
-            e2 = cb.reserve(lanes * 64 * kWpCoopLeaves * lbytes);
-            if(e2 != hipSuccess) return e2;
-            return launch_wp_extend_coop(ctx->fm, x, cb.p, st);
-        }
+        if(stride == 64 && wave_mode != 0) return launch_wp_extend_wave(ctx->fm, x, st);
         return launch_wp_extend(ctx->fm, x, st);
     };
 

@@ -517,21 +517,28 @@ struct Walk {
             for(uint32_t b = 0; b < 4; ++b) {
                 if(!(mask & (1u << b))) continue;
                 if(n_nxt >= kMaxChildren) { error = LRSC_WALK_ERR_CHILDREN; return; }
-                Leaf<P> ch = par;                                  // createChild copies the node state (SAINode.cpp:166-189)
-                ch.flo = ext[b].f.lo; ch.fhi = ext[b].f.hi; ch.rlo = ext[b].r.lo; ch.rhi = ext[b].r.hi;
-                ch.kmerFrequency = ext[b].freq;
-                ch.currOverlapLen++;
-                ch.queryOverlapLen++;
-                if(par.tailLetter == b) ch.tailLetterCount = par.tailLetterCount + 1;
-                else { ch.tailLetter = b; ch.tailLetterCount = 1; }
-                suf_push(ch, b);
-                ch.parent = (uint16_t)i;
-                ch.ext = (uint8_t)b;
-                ch.alive = 1;
+                const Leaf<P> ch = make_child(par, i, b, ext[b]);
                 if(ch.kmerFrequency > highfreqThreshold) n_highfreq++;      // for isInsufficientFreqs, which looks at exactly these values
                 nxt[n_nxt++] = ch;
             }
         }
+    }
+    // updateLeaves' child of leaf i of cur[] by base b: createChild copies the node state (SAINode.cpp:166-189), leafInfo(child)
+    // fields (LongReadCorrectByOverlap.h:172-203)
+    LRSC_WALK_FN __forceinline__ Leaf<P> make_child(const Leaf<P>& par, uint32_t i, uint32_t b, const Ext& e) const
+    {
+        Leaf<P> ch = par;
+        ch.flo = e.f.lo; ch.fhi = e.f.hi; ch.rlo = e.r.lo; ch.rhi = e.r.hi;
+        ch.kmerFrequency = e.freq;
+        ch.currOverlapLen++;
+        ch.queryOverlapLen++;
+        if(par.tailLetter == b) ch.tailLetterCount = par.tailLetterCount + 1;
+        else { ch.tailLetter = b; ch.tailLetterCount = 1; }
+        suf_push(ch, b);
+        ch.parent = (uint16_t)i;
+        ch.ext = (uint8_t)b;
+        ch.alive = 1;
+        return ch;
     }
 
     // ---- extendLeaves (.cpp:239-278) ------------------------------------------------------------------------
@@ -685,6 +692,19 @@ struct Walk {
     // ---- isTerminated for one leaf (.cpp:825-878); path given as (words, len) + optional extra char ------------
     LRSC_WALK_FN LRSC_WALK_NOINLINE void terminated_leaf(Leaf<P>& lf, const uint32_t* pw, uint32_t plen, int extra)
     {
+        const int hit = term_scan(lf);
+        if(hit < 0) return;
+        if(lf.res_first == -1) {                          // the first hit of the scan takes a result slot
+            if(n_results >= kMaxResults) { error = LRSC_WALK_ERR_RESULTS; return; }
+            ++n_results;
+            lf.res_first = (int)n_results;
+        }
+        lf.res_second = hit;
+        term_store(lf, hit, pw, plen, extra);
+    }
+    // the scan: the last target offset whose minOverlap-mer interval contains the leaf's (either strand), -1 if none
+    LRSC_WALK_FN __forceinline__ int term_scan(const Leaf<P>& lf) const
+    {
         const bool fvalid = lf.flo <= lf.fhi, rvalid = lf.rlo <= lf.rhi;
         // A non-empty interval of a k-mer K lies inside the interval of a k-mer w with |w| <= |K| only if K ends with w (fwd strand:
         // reverse(w) is a prefix of reverse(K); rvc strand: revcomp(w) is a prefix of revcomp(K)).  So if no target minOverlap-mer
@@ -693,7 +713,7 @@ struct Walk {
             const uint32_t L = minOverlap < 16 ? (uint32_t)minOverlap : 16u;
             const uint32_t code = (uint32_t)(lf.suf_lo & (L >= 16 ? 0xFFFFFFFFull : ((1ull << (2 * L)) - 1ull)));
             const uint32_t h = (code * 0x9E3779B1u) >> 25;
-            if((((h < 64 ? tmask0 : tmask1) >> (h & 63u)) & 1ull) == 0) return;
+            if((((h < 64 ? tmask0 : tmask1) >> (h & 63u)) & 1ull) == 0) return -1;
         }
         const uint64_t i0 = (uint64_t)(lf.res_second > 0 ? lf.res_second : 0);
         int hit = -1;
@@ -701,18 +721,13 @@ struct Walk {
             const P* t = term + i * 4;
             const bool isFwdTerminated = fvalid && lf.flo >= t[0] && lf.fhi <= t[1];
             const bool isRvcTerminated = rvalid && lf.rlo >= t[2] && lf.rhi <= t[3];
-            if(isFwdTerminated || isRvcTerminated) {
-                hit = (int)i;
-                if(lf.res_first == -1) {
-                    if(n_results >= kMaxResults) { error = LRSC_WALK_ERR_RESULTS; return; }
-                    ++n_results;
-                    lf.res_first = (int)n_results;
-                }
-                lf.res_second = (int)i;
-            }
+            if(isFwdTerminated || isRvcTerminated) hit = (int)i;
         }
-        if(hit < 0) return;
-        // results.at(first - 1) = STresult: thread = getFullString() (+ target.substr(i + minOverlap) appended at the end)
+        return hit;
+    }
+    // results.at(first - 1) = STresult: thread = getFullString() (+ target.substr(i + minOverlap) appended at the end)
+    LRSC_WALK_FN __forceinline__ void term_store(const Leaf<P>& lf, int hit, const uint32_t* pw, uint32_t plen, int extra)
+    {
         WalkResultRec& r = results[lf.res_first - 1];
         r.error_rate = lf.globalErr;
         r.match_i = (uint32_t)hit;
@@ -914,15 +929,6 @@ struct Walk {
             }
         }
         return 1;
-    }
-
-    // The memory-bound front of a step (extension + seed support) on whatever frontier `cur` points at, nothing committed: a helper
-    // lane of wp_extend_coop_kernel runs it on a private copy of ONE leaf ahead of the owner's real step, to have the rank blocks,
-    // table entries and 9-mer chains that leaf needs in the caches.  Writes: cur / nxt (private there) and this object's scalars.
-    LRSC_WALK_FN void warm()
-    {
-        extendLeaves();
-        if(!error) PrunedBySeedSupport();
     }
 
     // one iteration of extendOverlap's loop (.cpp:155-211); false when the loop is over (or on an internal error)

@@ -13,7 +13,7 @@
 //                          walks; a walk whose assumed source k-mer is not the true tail of the accumulated string is re-queued
 //
 // This translation unit compiles walk_device.h with ALL of the walk inlined into its kernels (the two defines below).  With the
-// big pieces of the walk as calls (the header's default, kept by extend.hip and wp_coop.hip) the Walk object's address escapes into
+// big pieces of the walk as calls (the header's default, kept by extend.hip) the Walk object's address escapes into
 // every call as `this`, so the object lives in scratch memory and every field access is a memory round trip of its own -- for a
 // lane that has nothing else in flight, most of a step's latency.  Counted on the ISA of wp_extend_kernel's call tree (narrow
 // layout): 1 864 FLAT + 1 012 scratch memory instructions with calls, 633 + 364 all inline, for 16 % more instructions (29 k).
@@ -26,6 +26,7 @@
 
 #include "walk_device.h"
 #include "wp.h"
+#include "wp_walk.h"
 
 namespace lrsc {
 
@@ -241,27 +242,6 @@ __global__ __launch_bounds__(64) void wp_materialize_kernel(WpArgs a)
 // ---------------------------------------------------------------------------------------
 // prepare + begin
 // ---------------------------------------------------------------------------------------
-template <bool WIDE>
-__device__ __forceinline__ void wp_bind_static(Walk<WIDE>& W, const WpArgs& a, const WpSlot& s)
-{
-    using P = typename Lay<WIDE>::pos_t;
-    const WpPrepLayout L = wp_prep_layout(s.lq, s.trg_len, a.seed_size, a.min_overlap, a.psz);
-    uint8_t* ws = s.prep;
-    W.q = s.q;
-    W.Lq = s.lq; W.initk = s.k; W.path_len = s.gap; W.trg_len = s.trg_len; W.dis = (int32_t)s.gap;
-    W.it9f = reinterpret_cast<SortItem*>(ws + L.item9f);
-    W.it9r = reinterpret_cast<SortItem*>(ws + L.item9r);
-    W.next9f = reinterpret_cast<uint16_t*>(ws + L.next9f);
-    W.next9r = reinterpret_cast<uint16_t*>(ws + L.next9r);
-    W.head9f = reinterpret_cast<uint16_t*>(ws + L.head9);
-    W.head9r = W.head9f + 256;
-    W.head5 = reinterpret_cast<uint16_t*>(ws + L.head5);
-    W.next5 = reinterpret_cast<uint16_t*>(ws + L.next5);
-    W.flags5 = ws + L.flags5;
-    W.term = reinterpret_cast<const P*>(ws + L.term);
-    W.n_term = s.trg_len >= a.min_overlap ? s.trg_len - a.min_overlap + 1 : 0;
-}
-
 template <bool WIDE>
 __global__ __launch_bounds__(64) void wp_prepare_kernel(FmIndexDev fm, WpArgs a)
 {

@@ -1,0 +1,542 @@
+// wp_wave.hip -- wp_extend_wave_kernel: the one-walk-per-wavefront extension launches (lane_stride 64) with the walk's frontier spread
+// over the wavefront.
+//
+// wp_extend_kernel at stride 64 runs a walk on lane 0 while 63 lanes wait.  Here the single-leaf fast step (Walk::step_fast) still runs
+// on lane 0, but the general step runs leaf i of the frontier on lane i and child c of the next frontier on lane c & 63 (two rounds
+// above 64 children): refine, getFMIndexExtensions with its per-leaf min_SA_threshold retry, SelectFreqsOfrange's searches,
+// PrunedBySeedSupport, isTerminated's scan, and the ring / path copies of a copied child (by the whole wavefront).  What crosses leaves
+// -- the error-rate minimum, the trim, the order of the children, the frequency maxima, the slot hand-out, the result slots -- goes
+// through ballots, shuffles and prefix counts, so that every decision, every value and every rank-query counter is the one of the
+// serial step (walk_device.h: the per-leaf pieces are the same member functions).
+//
+// The walk's scalars (currentLength, n_cur, ring_free, ...) sit in every lane's Walk object with the same value: every lane runs the
+// same cross-leaf code on them.  After a fast-step segment (lane 0 only) the ones it changed are broadcast from lane 0.  Leaves live
+// in the wavefront's workspace (wp_lane_layout) as in the serial kernel; a phase that reads what another lane wrote starts after
+// wave_sync().  Rank queries are counted per lane and summed over the wavefront (flush_counters).
+#define LRSC_WALK_FN __device__ __forceinline__
+#define LRSC_WALK_NOINLINE
+#include <hip/hip_runtime.h>
+
+#include "walk_device.h"
+#include "wp.h"
+#include "wp_walk.h"
+
+namespace lrsc {
+
+#ifndef LRSC_WP_EXTEND_OCC
+#define LRSC_WP_EXTEND_OCC 2          // wavefronts per SIMD, as wp_extend_kernel (capi.cpp sizes the launches for that)
+#endif
+
+namespace {
+
+// ---- wavefront helpers (call them with the whole wavefront active) ----------------------------------------------------------
+__device__ __forceinline__ uint64_t lanes_below(uint32_t lane) { return (1ull << lane) - 1ull; }
+__device__ __forceinline__ uint32_t popc64(uint64_t m) { return (uint32_t)__builtin_popcountll(m); }
+__device__ __forceinline__ uint32_t first_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+__device__ __forceinline__ uint64_t first_u64(uint64_t v) { return (uint64_t)first_u32((uint32_t)v) | ((uint64_t)first_u32((uint32_t)(v >> 32)) << 32); }
+__device__ __forceinline__ double first_f64(double v) { return __longlong_as_double((long long)first_u64((uint64_t)__double_as_longlong(v))); }
+// the value of lane l (l wave-uniform)
+__device__ __forceinline__ uint32_t lane_u32(uint32_t v, uint32_t l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l); }
+__device__ __forceinline__ double lane_f64(double v, uint32_t l)
+{
+    const uint64_t b = (uint64_t)__double_as_longlong(v);
+    return __longlong_as_double((long long)((uint64_t)lane_u32((uint32_t)b, l) | ((uint64_t)lane_u32((uint32_t)(b >> 32), l) << 32)));
+}
+__device__ __forceinline__ uint32_t wave_or(uint32_t v)
+{
+    for(int o = 32; o > 0; o >>= 1) v |= (uint32_t)__shfl_xor((int)v, o, 64);
+    return first_u32(v);
+}
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
+{
+    for(int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
+    return first_u32(v);
+}
+__device__ __forceinline__ int wave_max(int v)
+{
+    for(int o = 32; o > 0; o >>= 1) { const int w = __shfl_xor(v, o, 64); v = w > v ? w : v; }
+    return (int)first_u32((uint32_t)v);
+}
+// minimum of values that are not NaN (exact in any order)
+__device__ __forceinline__ double wave_min(double v)
+{
+    for(int o = 32; o > 0; o >>= 1) { const double w = __shfl_xor(v, o, 64); v = w < v ? w : v; }
+    return first_f64(v);
+}
+// what a lane stored before is visible to every lane of the wavefront after it
+__device__ __forceinline__ void wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+// the k-th lowest set bit of m (k = 0: the lowest): the slot that k rounds of `ctz, clear` leave at the front
+__device__ __forceinline__ uint32_t kth_bit(uint32_t m, uint32_t k)
+{
+    for(uint32_t j = 0; j < k; ++j) m &= m - 1u;
+    return m ? (uint32_t)__builtin_ctz(m) : 0u;          // (survivors <= maxLeaves <= 32 slots: never empty)
+}
+
+// ---- refineSAInterval (.cpp:355-369): leaf j on lane j & 63 ---------------------------------------------------------------
+template <bool WIDE>
+__device__ __forceinline__ void wave_refine(Walk<WIDE>& W, Leaf<typename Lay<WIDE>::pos_t>* leaves, uint32_t n, uint64_t newKmerSize, uint32_t lane)
+{
+    for(uint32_t j = lane; j < n; j += 64) W.find_suffix(leaves[j], (uint32_t)newKmerSize);
+    W.currentKmerSize = newKmerSize;
+}
+
+// ---- SelectFreqsOfrange (.cpp:281-331): leaf j on lane j & 63, a wavefront maximum per k-mer size -------------------------
+template <bool WIDE>
+__device__ __forceinline__ uint64_t wave_select(Walk<WIDE>& W, uint64_t LowerBound, uint64_t UpperBound, const Leaf<typename Lay<WIDE>::pos_t>* leaves,
+                                                uint32_t n, uint32_t lane)
+{
+    using P = typename Lay<WIDE>::pos_t;
+    const uint32_t U = (uint32_t)UpperBound, Lw = (uint32_t)LowerBound;
+    const bool h0 = lane < n, h1 = lane + 64 < n;
+    uint64_t s0lo = 0, s0hi = 0, s1lo = 0, s1hi = 0;
+    if(h0) { s0lo = leaves[lane].suf_lo; s0hi = leaves[lane].suf_hi; }
+    if(h1) { s1lo = leaves[lane + 64].suf_lo; s1hi = leaves[lane + 64].suf_hi; }
+    IvT<P> f0{}, r0{}, f1{}, r1{};
+    int mx = 0;                                          // tempmaxfmfreqs starts at 0
+    if(h0) { W.select_first(s0lo, s0hi, U, Lw, f0, r0); const int fr = (int)(isize(f0.lo, f0.hi) + isize(r0.lo, r0.hi)); mx = fr > mx ? fr : mx; }
+    if(h1) { W.select_first(s1lo, s1hi, U, Lw, f1, r1); const int fr = (int)(isize(f1.lo, f1.hi) + isize(r1.lo, r1.hi)); mx = fr > mx ? fr : mx; }
+    mx = wave_max(mx);
+    if(mx - (int)W.freqsOfKmerSize[LowerBound] < 5) return LowerBound;
+    for(uint64_t i = 1; i <= UpperBound - LowerBound; i++) {
+        const uint32_t t = (uint32_t)(UpperBound - LowerBound - i);
+        mx = 0;
+        if(h0) { W.select_next(s0lo, s0hi, U, t, f0, r0); const int fr = (int)(isize(f0.lo, f0.hi) + isize(r0.lo, r0.hi)); mx = fr > mx ? fr : mx; }
+        if(h1) { W.select_next(s1lo, s1hi, U, t, f1, r1); const int fr = (int)(isize(f1.lo, f1.hi) + isize(r1.lo, r1.hi)); mx = fr > mx ? fr : mx; }
+        mx = wave_max(mx);
+        if(mx - (int)W.freqsOfKmerSize[LowerBound + i] < 5) return LowerBound + i;
+    }
+    return UpperBound;
+}
+
+// ---- attempToExtend (.cpp:373-465) + updateLeaves (:468-488): leaf i on lane i (n_cur <= maxLeaves <= 32) ----------------
+template <bool WIDE>
+__device__ __forceinline__ void wave_attempt(Walk<WIDE>& W, uint32_t lane)
+{
+    using P = typename Lay<WIDE>::pos_t;
+    const uint32_t n = W.n_cur;
+    const bool have = lane < n;
+    Leaf<P> par = {};
+    if(have) par = W.cur[lane];
+    // minimumErrorRate starts at 1 and takes every smaller localErr
+    const double minimumErrorRate = wave_min(have && par.localErr < 1.0 ? par.localErr : 1.0);
+    // trim leaves whose error rate relative to the best one is high; the survivors keep their order
+    bool keep = false;
+    if(have) {
+        const double errorRateDiff = par.localErr - minimumErrorRate;
+        keep = !((errorRateDiff > 0.05 && W.currentLength > W.localK / 2) || (errorRateDiff > 0.1 && W.currentLength > 15));
+    }
+    W.ring_free |= wave_or(have && !keep ? 1u << par.ring : 0u);
+    W.path_free |= wave_or(have && !keep ? 1u << par.path : 0u);
+    const uint64_t below = lanes_below(lane);
+    const uint64_t km = __ballot(keep);
+    const uint32_t pos = popc64(km & below);
+    const uint32_t n_kept = popc64(km);
+    if(keep && pos != lane) W.cur[pos] = par;             // every lane has read its leaf: the compaction overwrites nothing unread
+    W.n_cur = n_kept;
+
+    // the extensions of each kept leaf; the threshold retry acts on this lane's copy of min_SA_threshold
+    const uint32_t nr0 = W.n_rank, nb0 = W.n_blk;
+    typename Walk<WIDE>::Ext ext[4];
+    uint32_t mask = 0;
+    if(keep) {
+        int count = 0;
+        while(count < 2) {
+            if(count == 1 && !(par.localErr == minimumErrorRate && n_kept > 1)) break;
+            uint64_t tc;
+            mask = W.getFMIndexExtensions_v(par.flo, par.fhi, par.rlo, par.rhi, par.tailLetterCount, par.suf_lo, ext, tc);
+            if(mask != 0) break;
+            W.min_SA_threshold--;
+            count++;
+        }
+        W.min_SA_threshold += (uint64_t)count;
+    }
+    // children in (parent, base) order: exclusive prefix of the accepted bases
+    uint32_t off = 0, total = 0;
+#pragma unroll
+    for(uint32_t b = 0; b < 4; ++b) {
+        const uint64_t m = __ballot(((mask >> b) & 1u) != 0);
+        off += popc64(m & below);
+        total += popc64(m);
+    }
+    // the serial loop stops at the child that would overflow nxt[]: a leaf after that one never ran its extensions
+    if(off > kMaxChildren) { W.n_rank = nr0; W.n_blk = nb0; }
+    if(total > kMaxChildren) { W.error = LRSC_WALK_ERR_CHILDREN; return; }
+    const int highfreqThreshold = W.PBcoverage > 60 ? (int)((uint64_t)(W.PBcoverage / 60) * 3) : 3;
+    uint32_t hf = 0, k = off;
+#pragma unroll
+    for(uint32_t b = 0; b < 4; ++b) {
+        if(!((mask >> b) & 1u)) continue;
+        const Leaf<P> ch = W.make_child(par, pos, b, ext[b]);
+        if(ch.kmerFrequency > highfreqThreshold) ++hf;
+        W.nxt[k++] = ch;
+    }
+    W.n_highfreq = wave_sum(hf);
+    W.n_nxt = total;
+    wave_sync();
+}
+
+// ---- extendLeaves (.cpp:239-278) ------------------------------------------------------------------------------------------
+template <bool WIDE>
+__device__ __forceinline__ void wave_extend(Walk<WIDE>& W, uint32_t lane)
+{
+    W.n_nxt = 0;
+    uint64_t t = W.tick();
+    if(W.currentKmerSize > W.maxOverlap) { wave_refine(W, W.cur, W.n_cur, W.maxOverlap, lane); wave_sync(); }
+    W.tock(1, t);
+    t = W.tick();
+    wave_attempt(W, lane);
+    W.tock(2, t);
+    if(W.error) return;
+    if(W.n_nxt == 0) {                                    // level 1: reduce the k-mer size
+        const uint64_t LowerBound = (W.currentKmerSize - 2) > W.minOverlap ? (W.currentKmerSize - 2) : W.minOverlap;
+        const uint64_t ReduceSize = wave_select(W, LowerBound, W.currentKmerSize, W.cur, W.n_cur, lane);
+        wave_refine(W, W.cur, W.n_cur, ReduceSize, lane);
+        wave_sync();
+        wave_attempt(W, lane);
+        if(W.error) return;
+        if(W.n_nxt == 0) {                                // level 2: reduce the threshold
+            W.min_SA_threshold--;
+            wave_attempt(W, lane);
+            W.min_SA_threshold++;
+            if(W.error) return;
+        }
+    }
+    if(W.n_nxt != 0) {
+        W.currentLength++;
+        W.currentKmerSize++;
+        if(W.isInsufficientFreqs(W.n_highfreq, W.n_nxt)) {   // frequencies are low: relax the k-mer size
+            const uint64_t LowerBound = (W.currentKmerSize - 2) > W.minOverlap ? (W.currentKmerSize - 2) : W.minOverlap;
+            const uint64_t ReduceSize = wave_select(W, LowerBound, W.currentKmerSize, W.nxt, W.n_nxt, lane);
+            wave_refine(W, W.nxt, W.n_nxt, ReduceSize, lane);
+        }
+    }
+}
+
+// ---- PrunedBySeedSupport (.cpp:491-563): child c on lane c & 63; the children stay in registers for the commit -------------
+template <bool WIDE>
+__device__ __forceinline__ void wave_prune(Walk<WIDE>& W, uint32_t lane, Leaf<typename Lay<WIDE>::pos_t>& c0, Leaf<typename Lay<WIDE>::pos_t>& c1)
+{
+    const uint64_t currSeedIdx = W.currentLength - W.seedSize;
+    const uint64_t indelOffset = W.seedSize + W.maxIndelSize;
+    const uint64_t smallSeedIdx = currSeedIdx <= indelOffset ? 0 : currSeedIdx - indelOffset;
+    const uint64_t largeSeedIdx = (currSeedIdx + indelOffset) >= (W.Lq - W.seedSize) ? (W.Lq - W.seedSize) : currSeedIdx + indelOffset;
+    const uint32_t n = W.n_nxt;
+    bool a0 = false, a1 = false;
+    uint32_t hc = 0;
+    // a child still carries its parent's ring id: the parent's error history, which no commit has touched yet
+    if(lane < n) {
+        c0 = W.nxt[lane];
+        W.template prune_leaf<true>(c0, W.rings + (uint64_t)c0.ring * 100, currSeedIdx, smallSeedIdx, largeSeedIdx);
+        W.nxt[lane] = c0;
+        a0 = c0.alive != 0;
+        if(a0) hc |= 1u << c0.parent;
+    }
+    if(lane + 64 < n) {
+        c1 = W.nxt[lane + 64];
+        W.template prune_leaf<true>(c1, W.rings + (uint64_t)c1.ring * 100, currSeedIdx, smallSeedIdx, largeSeedIdx);
+        W.nxt[lane + 64] = c1;
+        a1 = c1.alive != 0;
+        if(a1) hc |= 1u << c1.parent;
+    }
+    W.alive_lo = __ballot(a0);
+    W.alive_hi = __ballot(a1);
+    W.has_child = wave_or(hc);
+}
+
+// a further child's copies of its parent's ring and path, by the whole wavefront, with this step's own entries already in place
+// (the serial commit copies everything but the own ring entry, then writes that entry and sets the new path character)
+template <bool WIDE>
+__device__ __forceinline__ void wave_copy_slots(Walk<WIDE>& W, uint64_t further, const Leaf<typename Lay<WIDE>::pos_t>& ch, uint32_t new_ring,
+                                                uint32_t new_path, uint32_t lane)
+{
+    while(further) {
+        const uint32_t l = (uint32_t)__builtin_ctzll(further);
+        further &= further - 1ull;
+        const uint32_t sr = lane_u32(ch.ring, l), dr = lane_u32(new_ring, l), sp = lane_u32(ch.path, l), dp = lane_u32(new_path, l);
+        const uint32_t own = (lane_u32(ch.hist_size, l) - 1u) % 100u, plen = lane_u32(ch.path_len, l), ex = lane_u32(ch.ext, l);
+        const double ge = lane_f64(ch.globalErr, l);
+        const double* src = W.rings + (uint64_t)sr * 100;
+        double* dst = W.rings + (uint64_t)dr * 100;
+        for(uint32_t k = lane; k < 100; k += 64) dst[k] = k == own ? ge : src[k];
+        const uint32_t* ps = W.paths + (uint64_t)sp * W.pathw;
+        uint32_t* pd = W.paths + (uint64_t)dp * W.pathw;
+        const uint32_t nw = (plen + 16) >> 4, wi = plen >> 4, sh = 2 * (plen & 15u);
+        for(uint32_t k = lane; k < nw; k += 64) {
+            uint32_t v = ps[k];
+            if(k == wi) v = (v & ~(3u << sh)) | (ex << sh);
+            pd[k] = v;
+        }
+    }
+}
+
+// results.at(first - 1) of every leaf of `hits` (lanes in leaf order: a later leaf with the same result slot overwrites, as in the
+// serial loop): the record by lane 0, the path by the whole wavefront
+template <bool WIDE>
+__device__ __forceinline__ void wave_store_results(Walk<WIDE>& W, uint64_t hits, const Leaf<typename Lay<WIDE>::pos_t>& lf, int hit, uint32_t lane)
+{
+    while(hits) {
+        const uint32_t l = (uint32_t)__builtin_ctzll(hits);
+        hits &= hits - 1ull;
+        const uint32_t slot = lane_u32((uint32_t)lf.res_first, l) - 1u, path = lane_u32(lf.path, l), plen = lane_u32(lf.path_len, l);
+        const uint32_t mi = lane_u32((uint32_t)hit, l);
+        const double ge = lane_f64(lf.globalErr, l);
+        if(lane == 0) { WalkResultRec& r = W.results[slot]; r.error_rate = ge; r.match_i = mi; r.path_len = plen; }
+        const uint32_t* src = W.paths + (uint64_t)path * W.pathw;
+        uint32_t* dst = W.rpaths + (uint64_t)slot * W.pathw;
+        const uint32_t nw = (plen + 15) >> 4;
+        for(uint32_t k = lane; k < nw; k += 64) dst[k] = src[k];
+    }
+}
+
+// ---- the commit of step_body (walk_device.h) and isTerminated (.cpp:825-878) ------------------------------------------------
+template <bool WIDE>
+__device__ __forceinline__ void wave_commit(Walk<WIDE>& W, uint32_t lane, Leaf<typename Lay<WIDE>::pos_t>& c0, Leaf<typename Lay<WIDE>::pos_t>& c1)
+{
+    using P = typename Lay<WIDE>::pos_t;
+    uint64_t t = W.tick();
+    const uint64_t am0 = W.alive_lo, am1 = W.alive_hi;
+    const uint32_t survivors = popc64(am0) + popc64(am1);
+    ++W.steps;
+    if(survivors > W.maxLeaves) {
+        // the frontier overflows: the loop ends after this isTerminated (children in order, on lane 0 as in the serial step)
+        wave_sync();
+        if(lane == 0 && W.currentLength >= W.minLength)
+            for(uint32_t c = 0; c < W.n_nxt; ++c) {
+                if((((c < 64 ? am0 >> c : am1 >> (c - 64)) & 1ull)) == 0) continue;
+                const Leaf<P>& par = W.cur[W.nxt[c].parent];
+                W.terminated_leaf(W.nxt[c], W.paths + (uint64_t)par.path * W.pathw, par.path_len, (int)W.nxt[c].ext);
+                if(W.error) break;
+            }
+        W.n_results = first_u32(W.n_results);
+        W.error = (int)first_u32((uint32_t)W.error);
+        W.n_cur = survivors;
+        W.ended = true;
+        return;
+    }
+    const uint64_t below = lanes_below(lane);
+    // 1. the parents without a surviving child give their slots back
+    uint32_t fr = 0, fp = 0;
+    if(lane < W.n_cur && !((W.has_child >> lane) & 1u)) { fr = 1u << W.cur[lane].ring; fp = 1u << W.cur[lane].path; }
+    W.ring_free |= wave_or(fr);
+    W.path_free |= wave_or(fp);
+    // 2. the first surviving child of a parent takes over its slots; a further one is a child whose previous surviving child (the
+    //    children are in parent order) has the same parent
+    const bool a0 = ((am0 >> lane) & 1ull) != 0, a1 = ((am1 >> lane) & 1ull) != 0;
+    const uint32_t p0 = c0.parent, p1 = c1.parent;
+    const uint64_t m0 = am0 & below, m1 = am1 & below;
+    const uint32_t prev0 = (uint32_t)__shfl((int)p0, m0 ? 63 - __builtin_clzll(m0) : (int)lane, 64);
+    const uint32_t prev1 = (uint32_t)__shfl((int)p1, m1 ? 63 - __builtin_clzll(m1) : (int)lane, 64);
+    const uint32_t last0 = am0 ? lane_u32(p0, 63u - (uint32_t)__builtin_clzll(am0)) : 0xFFFFFFFFu;
+    const bool fur0 = a0 && m0 != 0 && prev0 == p0;
+    const bool fur1 = a1 && (m1 != 0 ? prev1 == p1 : last0 == p1);
+    // 3. the k-th further child in child order takes the k-th lowest free slot
+    const uint64_t f0 = __ballot(fur0), f1 = __ballot(fur1);
+    const uint32_t n_further = popc64(f0) + popc64(f1);
+    uint32_t r0 = c0.ring, q0 = c0.path, r1 = c1.ring, q1 = c1.path;
+    if(fur0) { const uint32_t k = popc64(f0 & below); r0 = kth_bit(W.ring_free, k); q0 = kth_bit(W.path_free, k); }
+    if(fur1) { const uint32_t k = popc64(f0) + popc64(f1 & below); r1 = kth_bit(W.ring_free, k); q1 = kth_bit(W.path_free, k); }
+    for(uint32_t j = 0; j < n_further; ++j) { W.ring_free &= W.ring_free - 1u; W.path_free &= W.path_free - 1u; }
+    // 4. copies for the further children (all but the own ring entry: it is written with the copy), then the in-place children's
+    //    GlobalErrorRateRecord.push_back and path character
+    wave_copy_slots(W, f0, c0, r0, q0, lane);
+    wave_copy_slots(W, f1, c1, r1, q1, lane);
+    if(a0 && !fur0) {
+        W.rings[(uint64_t)c0.ring * 100 + (c0.hist_size - 1) % 100] = c0.globalErr;
+        path_set(W.paths + (uint64_t)c0.path * W.pathw, c0.path_len, c0.ext);
+    }
+    if(a1 && !fur1) {
+        W.rings[(uint64_t)c1.ring * 100 + (c1.hist_size - 1) % 100] = c1.globalErr;
+        path_set(W.paths + (uint64_t)c1.path * W.pathw, c1.path_len, c1.ext);
+    }
+    c0.ring = (uint16_t)r0; c0.path = (uint16_t)q0; c0.path_len++;
+    c1.ring = (uint16_t)r1; c1.path = (uint16_t)q1; c1.path_len++;
+    W.tock(5, t);
+    t = W.tick();
+    // isTerminated over the new frontier in leaf order: the scans side by side, result slots by a prefix count of the leaves that
+    // need a new one
+    int hit0 = -1, hit1 = -1;
+    uint64_t h0 = 0, h1 = 0;
+    if(W.currentLength >= W.minLength) {
+        if(a0) hit0 = W.term_scan(c0);
+        if(a1) hit1 = W.term_scan(c1);
+        const bool need0 = hit0 >= 0 && c0.res_first == -1, need1 = hit1 >= 0 && c1.res_first == -1;
+        const uint64_t n0 = __ballot(need0), n1 = __ballot(need1);
+        bool bad = false;
+        if(need0) { const uint32_t k = W.n_results + popc64(n0 & below); if(k >= kMaxResults) bad = true; else c0.res_first = (int)k + 1; }
+        if(need1) { const uint32_t k = W.n_results + popc64(n0) + popc64(n1 & below); if(k >= kMaxResults) bad = true; else c1.res_first = (int)k + 1; }
+        if(hit0 >= 0) c0.res_second = hit0;
+        if(hit1 >= 0) c1.res_second = hit1;
+        if(__ballot(bad)) W.error = LRSC_WALK_ERR_RESULTS;
+        W.n_results += popc64(n0) + popc64(n1);
+        h0 = __ballot(hit0 >= 0);
+        h1 = __ballot(hit1 >= 0);
+    }
+    // 5. m_leaves = newLeaves (compaction in child order), into the buffer the serial swap rule leaves as `cur`
+    const bool swap = 4u * survivors <= (W.cur == W.leaf_small ? 32u : kMaxChildren);
+    Leaf<P>* dest = swap ? W.nxt : W.cur;
+    if(a0) dest[popc64(m0)] = c0;
+    if(a1) dest[popc64(am0) + popc64(m1)] = c1;
+    if(swap) { Leaf<P>* t2 = W.cur; W.cur = W.nxt; W.nxt = t2; }
+    W.n_cur = survivors;
+    wave_sync();
+    if(!W.error && (h0 | h1)) {
+        wave_store_results(W, h0, c0, hit0, lane);
+        wave_store_results(W, h1, c1, hit1, lane);
+        wave_sync();
+    }
+    W.tock(6, t);
+}
+
+// ---- one iteration of extendOverlap's loop (Walk::step) ---------------------------------------------------------------------
+template <bool WIDE>
+__device__ __forceinline__ bool wave_step(Walk<WIDE>& W, uint32_t lane)
+{
+    using P = typename Lay<WIDE>::pos_t;
+    if(W.ended || W.error || !(W.n_cur != 0 && W.n_cur <= W.maxLeaves && W.currentLength <= W.maxLength)) return false;
+    W.leaf_steps += W.n_cur;
+    if(W.n_cur > W.max_front) W.max_front = W.n_cur;
+    wave_sync();
+    uint64_t t = W.tick();
+    wave_extend(W, lane);
+    W.tock(0, t);
+    if(W.error) return true;
+    t = W.tick();
+    Leaf<P> c0 = {}, c1 = {};
+    wave_prune(W, lane, c0, c1);
+    W.tock(4, t);
+    wave_commit(W, lane, c0, c1);
+    return true;
+}
+
+} // namespace
+
+// ---------------------------------------------------------------------------------------
+// one walk per wavefront over a queue of walks (the same queue, workspace and results as wp_extend_kernel at stride 64)
+// ---------------------------------------------------------------------------------------
+template <bool WIDE>
+__global__ __launch_bounds__(64, LRSC_WP_EXTEND_OCC) void wp_extend_wave_kernel(FmIndexDev fm, WpArgs a)
+{
+    using P = typename Lay<WIDE>::pos_t;
+    __shared__ __attribute__((aligned(16))) uint32_t mtab[MaskTabSize<WIDE>::value];
+    init_mask_table<WIDE>(mtab);
+    const uint32_t lane = threadIdx.x;
+    const uint32_t wave = blockIdx.x;
+    Walk<WIDE> W;
+    W.sF = strand_consts<P>(fm.strand[LRSC_RBWT]);
+    W.sR = strand_consts<P>(fm.strand[LRSC_BWT]);
+    W.fm = &fm; W.mtab = mtab;
+    W.seedSize = a.seed_size; W.minOverlap = a.min_overlap; W.maxLeaves = a.max_leaves;
+    W.PBcoverage = a.pb_coverage; W.PacBioErrorRate = a.pacbio_error_rate; W.errorRate = 0.25; W.localK = 100;
+    W.freqsOfKmerSize = a.freqs_of_kmer_size;
+    const WpLaneLayout LL = wp_lane_layout(a.lbytes, a.lane_pathw);
+    uint8_t* lws = a.lane_ws + (uint64_t)(wave < a.n_lanes ? wave : 0u) * a.lane_ws_bytes;
+    Leaf<P>* const leaf_base = reinterpret_cast<Leaf<P>*>(lws + LL.leaves);
+    W.rings = reinterpret_cast<double*>(lws + LL.rings);
+    W.results = reinterpret_cast<WalkResultRec*>(lws + LL.results);
+    W.paths = reinterpret_cast<uint32_t*>(lws + LL.paths);
+    W.pathw = a.lane_pathw;
+    W.rpaths = W.paths + (uint64_t)32 * a.lane_pathw;
+    W.n_rank = 0; W.n_blk = 0; W.steps = 0; W.leaf_steps = 0; W.error = 0; W.cyc_setup = 0; W.cyc_loop = 0; W.prof = nullptr; W.profile = false;
+    const uint64_t min_SA = a.pb_coverage > 60 ? (uint64_t)((a.pb_coverage / 60) * 3) : 3;
+
+    Leaf<P> L;                                            // lane 0: the single-leaf fast path's leaf in registers
+    uint32_t pw = 0;
+    // profiling (a.prof): wall ticks of the wavefront in the step's regions (Walk::tock slots 0-6, 7 = fast steps), 8 = refill,
+    // 9 = finish, 10 = whole loop; lane 0 reports them
+    uint64_t pr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    uint64_t t_refill = 0, t_finish = 0, n_fast = 0;
+    const bool prof = a.prof != nullptr;
+    if(prof) W.prof = pr;
+    const uint64_t t_loop0 = prof ? __builtin_readcyclecounter() : 0;
+    if(wave < a.n_lanes)
+    while(true) {
+        const uint64_t tr0 = prof ? __builtin_readcyclecounter() : 0;
+        uint32_t i = 0;
+        if(lane == 0) i = atomicAdd(a.queue, 1u);
+        i = first_u32(i);
+        if(i >= a.n_list) break;
+        if(a.reqs && a.reqs[i].kind != kWpReqFm) continue;
+        const uint32_t si = a.list ? a.list[i] : (uint32_t)a.slot_base + i;
+        {
+            const WpSlot& s = a.slots[si];
+            if(s.flags & kWpGeomBad) continue;
+            wp_bind_static<WIDE>(W, a, s);
+            const WpStatic* H = reinterpret_cast<const WpStatic*>(s.prep);
+            W.n9f = H->n9f; W.n9r = H->n9r; W.tmask0 = H->tmask0; W.tmask1 = H->tmask1;
+            W.maxOverlap = (uint32_t)s.k + 2;
+            W.min_SA_threshold = min_SA;
+            // .cpp:55-58,78-79: double expressions truncated to size_t
+            if((int32_t)s.gap > 100) W.maxIndelSize = (uint64_t)((int32_t)s.gap * 0.2); else W.maxIndelSize = 20;
+            W.maxLength = (uint64_t)((1.2 * ((int32_t)s.gap + 10)) + (double)(2 * (uint64_t)s.k));
+            W.minLength = (uint64_t)((0.8 * ((int32_t)s.gap - 20)) + (double)(2 * (uint64_t)s.k));
+            W.cur = leaf_base; W.nxt = leaf_base + 32; W.leaf_small = leaf_base;
+            W.error = 0;
+            W.leaf_steps = 0; W.max_front = 1;
+            const P riv[4] = {(P)H->root[0], (P)H->root[1], (P)H->root[2], (P)H->root[3]};
+            W.begin_root(riv);                            // every lane: the same values into the same words
+        }
+        const uint64_t steps0 = W.steps;
+        if(prof) t_refill += __builtin_readcyclecounter() - tr0;
+        while(true) {
+            int r = 2;
+            if(W.can_fast()) {
+                wave_sync();
+                const uint64_t tq = prof ? __builtin_readcyclecounter() : 0;
+                if(lane == 0) {
+                    W.enter_fast(L, pw);
+                    do { r = W.step_fast(L, pw); if(prof && r == 1) ++n_fast; } while(r == 1);
+                }
+                if(prof) pr[7] += __builtin_readcyclecounter() - tq;
+                // what a fast step changes, from lane 0 (rank-query counters stay per lane)
+                r = (int)first_u32((uint32_t)r);
+                W.currentLength = first_u64(W.currentLength); W.currentKmerSize = first_u64(W.currentKmerSize);
+                W.steps = first_u64(W.steps); W.leaf_steps = first_u32(W.leaf_steps);
+                W.n_cur = first_u32(W.n_cur); W.n_results = first_u32(W.n_results); W.error = (int)first_u32((uint32_t)W.error);
+            }
+            if(r == 2) r = wave_step(W, lane) ? 1 : 0;
+            if(r == 0) break;
+        }
+        const uint64_t tf0 = prof ? __builtin_readcyclecounter() : 0;
+        wave_sync();
+        if(lane == 0) {
+            WpSlot& s = a.slots[si];
+            uint32_t plen = 0, mi = 0;
+            const int code = W.finish(&plen, s.path, &mi);
+            s.code = code; s.path_len = plen; s.match_i = mi; s.steps = (uint32_t)(W.steps - steps0); s.leaf_steps = W.leaf_steps; s.max_front = (uint8_t)W.max_front;
+            s.flags |= (uint8_t)kWpFmValid;
+            if(code <= 0 && code > LRSC_WALK_ERR_CHILDREN && a.auto_dp && s.next == 0) {
+                const uint32_t j = atomicAdd(a.n_dp_items, 1u);
+                if(j < a.dp_items_cap) {
+                    WpDpItem d; d.q = (uint64_t)s.dpq; d.slot = si; d.lq = s.dp_lq; d.k = s.dp_k; d.total_freq = s.dp_total_freq;
+                    a.dp_items[j] = d;
+                }
+            }
+        }
+        if(prof) t_finish += __builtin_readcyclecounter() - tf0;
+    }
+    if(prof && wave < a.n_lanes && lane == 0) {
+        for(int j = 0; j < 8; ++j) atomicAdd(&a.prof[j], (unsigned long long)pr[j]);
+        atomicAdd(&a.prof[8], (unsigned long long)t_refill);
+        atomicAdd(&a.prof[9], (unsigned long long)t_finish);
+        atomicAdd(&a.prof[10], (unsigned long long)(__builtin_readcyclecounter() - t_loop0));
+        atomicAdd(&a.prof[11], (unsigned long long)W.steps);
+        atomicAdd(&a.prof[12], (unsigned long long)n_fast);
+    }
+    flush_counters(a.ctr, W.n_rank, W.n_blk);
+}
+
+hipError_t launch_wp_extend_wave(const FmIndexDev& fm, const WpArgs& a, hipStream_t stream)
+{
+    if(a.n_list == 0 || a.n_lanes == 0) return hipSuccess;
+    // n_lanes = walks in flight = wavefronts (lane_stride 64)
+    if(fm.wide) hipLaunchKernelGGL(wp_extend_wave_kernel<true>, dim3(a.n_lanes), dim3(64), 0, stream, fm, a);
+    else        hipLaunchKernelGGL(wp_extend_wave_kernel<false>, dim3(a.n_lanes), dim3(64), 0, stream, fm, a);
+    return hipGetLastError();
+}
+
+} // namespace lrsc
