@@ -92,7 +92,8 @@ typedef struct lrsc_params {
     int32_t radius;             /* 100 (LongReadProbe.h:32)                        */
     float   hh_ratio;           /* 0.6f (LongReadProbe.h:33)                       */
     int32_t next_target;        /* -n, default 1                                   */
-    int32_t max_leaves;         /* -l, default 32                                  */
+    int32_t max_leaves;         /* -l, default 32; 1..256 (above 32: the walks that outgrow 32 leaves run again in a
+                                 * wide launch with room for -l leaves, LRSC_K_EXTEND_WIDE)                       */
     int32_t idmer_len;          /* -i, default 9                                   */
     int32_t min_kmer_len;       /* -s, default 13                                  */
     int32_t split;              /* --split                                         */
@@ -264,7 +265,7 @@ enum lrsc_read_status {
     LRSC_READ_OK = 0,
     LRSC_READ_WALK_QUERY_TOO_LONG = 1,   /* a walk's query (k-mer + gap between two seeds + target seed) >= 65535 bases  */
     LRSC_READ_TOO_LONG = 2,              /* the read's output slot would exceed 4 GB                                     */
-    LRSC_READ_FRONTIER_LIMIT = 3,        /* more than 160 terminated lineages / 128 children in one walk                 */
+    LRSC_READ_FRONTIER_LIMIT = 3,        /* more than 160 terminated lineages (5 x max_leaves above 32) in one walk      */
     LRSC_READ_GEOMETRY = 4,              /* seeds overlap / an extension k-mer above 59 or below the idmer size          */
     LRSC_READ_DP_LIMIT = 5,              /* DP fallback: a pile-up beyond its column / consensus capacity (a long query is not a
                                           * limit: alignments beyond the kernel's LDS stage run from a global workspace)   */
@@ -346,7 +347,9 @@ typedef struct lrsc_kernel_stats {
     uint64_t block_loads;       /* rank-block loads (lower-1/upper in one block count 1) */
     uint64_t table_loads;       /* k-mer interval table look-ups (one 64-byte line each)  */
 } lrsc_kernel_stats;
-enum { LRSC_K_RANK = 0, LRSC_K_FIND = 1, LRSC_K_GRID = 2, LRSC_K_SEEDS = 3, LRSC_K_EXTEND = 4, LRSC_K_LF = 5, LRSC_K_DP = 6, LRSC_K_MSA = 7, LRSC_K_COUNT = 8 };
+/* LRSC_K_EXTEND_WIDE: the wide walk launches of max_leaves above 32 (one per round with escalated walks; none at <= 32) */
+enum { LRSC_K_RANK = 0, LRSC_K_FIND = 1, LRSC_K_GRID = 2, LRSC_K_SEEDS = 3, LRSC_K_EXTEND = 4, LRSC_K_LF = 5, LRSC_K_DP = 6, LRSC_K_MSA = 7,
+       LRSC_K_EXTEND_WIDE = 8, LRSC_K_COUNT = 9 };
 int lrsc_ctx_stats(lrsc_ctx* ctx, int kernel, lrsc_kernel_stats* out);
 int lrsc_ctx_stats_reset(lrsc_ctx* ctx);
 /* Block until everything queued on the ctx stream is done. */

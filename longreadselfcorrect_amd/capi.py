@@ -118,7 +118,7 @@ class KernelStats(C.Structure):
     ]
 
 
-K_RANK, K_FIND, K_GRID, K_SEEDS, K_EXTEND, K_LF, K_DP, K_MSA = range(8)
+K_RANK, K_FIND, K_GRID, K_SEEDS, K_EXTEND, K_LF, K_DP, K_MSA, K_EXTEND_WIDE = range(9)
 SEED_DTYPE = np.dtype([("start", "<i4"), ("len", "<i4"), ("max_freq", "<i4"), ("repeat", "<i4"), ("start_k", "<i4"),
                        ("end_k", "<i4"), ("start_freq", "<i4"), ("end_freq", "<i4")])
 BWT, RBWT = 0, 1

@@ -1016,6 +1016,8 @@ extern "C" int lrsc_batch_walk_log(lrsc_ctx* ctx, lrsc_batch* b, uint8_t* log, u
 // FM-extend
 // ---------------------------------------------------------------------------------------
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+static const char* const kMaxLeavesMsg = "max_leaves must be 1..256";        // 256 = kWideMaxLeaves
+static_assert(kWideMaxLeaves == 256, "kMaxLeavesMsg names the cap");
 
 extern "C" int lrsc_extend_walks(lrsc_ctx* ctx, const char* seq, uint64_t seq_len, const lrsc_walk_desc* walks, uint32_t n,
                                  lrsc_walk_result* results, char* out_arena, uint64_t arena_cap, uint64_t* arena_used)
@@ -1024,13 +1026,15 @@ extern "C" int lrsc_extend_walks(lrsc_ctx* ctx, const char* seq, uint64_t seq_le
     *arena_used = 0;
     if(n == 0) return LRSC_OK;
     const lrsc_params& p = ctx->params;
-    if(p.max_leaves < 1 || p.max_leaves > 32) return fail(LRSC_ERR_UNSUPPORTED, "max_leaves must be 1..32");
+    if(p.max_leaves < 1 || p.max_leaves > (int)kWideMaxLeaves) return fail(LRSC_ERR_UNSUPPORTED, kMaxLeavesMsg);
     if(p.idmer_len < 5 || p.idmer_len > 16) return fail(LRSC_ERR_UNSUPPORTED, "idmer_len must be 5..16");
     if(p.min_kmer_len < p.idmer_len || p.min_kmer_len > 62) return fail(LRSC_ERR_UNSUPPORTED, "min_kmer_len out of range");
     HIP_TRY(hipSetDevice(ctx->device));
     const bool wide = ctx->fm.wide != 0;
     const size_t psz = wide ? 8 : 4;
     const size_t lbytes = leaf_bytes(wide);
+    // -l above 32: every walk goes straight to the wide kernel (one walk per wavefront, room for -l leaves)
+    const bool wide_walks = p.max_leaves > (int)kNarrowLeaves;
 
     // ---- geometry, codes, workspace plan --------------------------------------------------------------
     std::vector<WalkWork> work(n);
@@ -1060,10 +1064,15 @@ extern "C" int lrsc_extend_walks(lrsc_ctx* ctx, const char* seq, uint64_t seq_le
         ww.o_item9f = (uint32_t)o; o += (size_t)n9 * sizeof(SortItem);
         ww.o_item9r = (uint32_t)o; o += (size_t)n9 * sizeof(SortItem);
         ww.o_term = (uint32_t)o;   o = align_up(o + (size_t)nT * 4 * psz, 16);
-        ww.o_leaves = (uint32_t)o; o = align_up(o + (size_t)(32 + kMaxChildren) * lbytes, 16);
-        ww.o_rings = (uint32_t)o;  o += (size_t)32 * 100 * sizeof(double);
-        ww.o_results = (uint32_t)o; o += (size_t)kMaxResults * sizeof(WalkResultRec);
-        ww.o_paths = (uint32_t)o;  o += (size_t)(32 + kMaxResults) * ww.pathw * 4;
+        if(wide_walks) {
+            ww.o_leaves = (uint32_t)o; o = align_up(o + wp_wide_layout((uint32_t)lbytes, ww.pathw, (uint32_t)p.max_leaves).total, 64);
+            ww.o_rings = ww.o_results = ww.o_paths = 0;
+        } else {
+            ww.o_leaves = (uint32_t)o; o = align_up(o + (size_t)(32 + kMaxChildren) * lbytes, 16);
+            ww.o_rings = (uint32_t)o;  o += (size_t)32 * 100 * sizeof(double);
+            ww.o_results = (uint32_t)o; o += (size_t)kMaxResults * sizeof(WalkResultRec);
+            ww.o_paths = (uint32_t)o;  o += (size_t)(32 + kMaxResults) * ww.pathw * 4;
+        }
         ww.o_next9f = (uint32_t)o; o += (size_t)n9 * 2;
         ww.o_next9r = (uint32_t)o; o += (size_t)n9 * 2;
         ww.o_head9 = (uint32_t)o;  o += 512 * 2;
@@ -1134,11 +1143,19 @@ extern "C" int lrsc_extend_walks(lrsc_ctx* ctx, const char* seq, uint64_t seq_le
     a.pb_coverage = (uint64_t)p.pb_coverage; a.pacbio_error_rate = p.error_rate;
     a.freqs_of_kmer_size = d_freqs.p;
     a.ctr = ctx->d_ctr;
-    const int st = timed_launch(ctx, LRSC_K_EXTEND, [&]() {
-        hipError_t e2 = launch_walk_prepare(ctx->fm, a, ctx->stream);
-        if(e2 == hipSuccess) e2 = launch_walk_extend(ctx->fm, a, ctx->stream);
-        return e2;
-    });
+    int st;
+    if(wide_walks) {
+        int cus = 256;
+        (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device);
+        st = timed_launch(ctx, LRSC_K_EXTEND, [&]() { return launch_walk_prepare(ctx->fm, a, ctx->stream); });
+        if(st == LRSC_OK)
+            st = timed_launch(ctx, LRSC_K_EXTEND_WIDE, [&]() { return launch_walk_extend_wide(ctx->fm, a, (uint32_t)cus * 8u, ctx->stream); });
+    } else
+        st = timed_launch(ctx, LRSC_K_EXTEND, [&]() {
+            hipError_t e2 = launch_walk_prepare(ctx->fm, a, ctx->stream);
+            if(e2 == hipSuccess) e2 = launch_walk_extend(ctx->fm, a, ctx->stream);
+            return e2;
+        });
     if(st != LRSC_OK) return st;
 
     std::vector<WalkOut> out(n);
@@ -1494,7 +1511,8 @@ struct WpScratch {
     DevBuf<DevCounters> d_ctr2;
     hipEvent_t ev_side_t0 = nullptr, ev_side_t1 = nullptr;
     DevBuf<WpRequest> d_req;
-    DevBuf<uint8_t> d_prep, d_lane, d_lane_side, d_lane_side2, d_ctx[2];
+    DevBuf<uint8_t> d_prep, d_lane, d_lane_side, d_lane_side2, d_ctx[2], d_lane_wide;
+    DevBuf<uint32_t> d_wide_list;          // the escalated walks of a round (-l above the narrow cap)
     hipStream_t side[2] = {nullptr, nullptr};
     hipEvent_t ev_side[2] = {nullptr, nullptr}, ev_ready = nullptr;
     DevBuf<unsigned long long> d_prof;
@@ -1595,6 +1613,12 @@ static int batch_correct_wp(lrsc_ctx* ctx, lrsc_batch* b, lrsc_read_result* res,
     a.n_reads = n; a.min_k = b->min_k;
     a.work = ws.d_work.p; a.reads = ws.d_reads.p; a.slots = ws.d_slots.p; a.n_slots = n_slots;
     a.seed_size = (uint32_t)p.idmer_len; a.min_overlap = (uint32_t)p.min_kmer_len; a.max_leaves = (uint32_t)p.max_leaves;
+    // -l above the narrow cap (32; LRSC_WP_WIDE_CAP lowers it, a test hook): the narrow launches run every walk with the cap, and a
+    // walk that outgrows it runs again in the wide launch with the true -l (escalate_walks below)
+    uint32_t narrow_cap = kNarrowLeaves;
+    if(const char* ev = std::getenv("LRSC_WP_WIDE_CAP")) narrow_cap = (uint32_t)std::min<int>((int)kNarrowLeaves, std::max(1, std::atoi(ev)));
+    const bool escalate = (uint32_t)p.max_leaves > narrow_cap;
+    if(escalate) { a.max_leaves = narrow_cap; a.escalate = 1; }
     a.start_kmer_len = p.start_kmer_len; a.next_target = p.next_target; a.split = p.split; a.no_dp = p.no_dp;
     a.pb_coverage = (uint64_t)p.pb_coverage; a.pacbio_error_rate = p.error_rate;
     a.freqs_of_kmer_size = cs.d_freqs.p;
@@ -1755,6 +1779,35 @@ static int batch_correct_wp(lrsc_ctx* ctx, lrsc_batch* b, lrsc_read_result* res,
         return e2;
     };
 
+    // The escalated walks of a round (entries of a.list / the range whose narrow walk ended with LRSC_WALK_NEEDS_WIDE) run again
+    // from their start with the true -l, one walk per wavefront (wp_wide.hip); their failures join the round's DP items.  A
+    // wavefront's workspace is wp_wide_layout(pathw, -l): the launch takes as many of them as lane_budget / 4 holds.
+    uint64_t n_escalated = 0;
+    auto escalate_walks = [&](const WpArgs& x0, uint32_t n_ent, uint32_t pathw) -> int {
+        HIP_TRY(ws.d_wide_list.reserve(n_ent));
+        uint32_t* d_count = ws.d_small.p + 14;
+        HIP_TRY(hipMemsetAsync(d_count, 0, sizeof(uint32_t), ctx->stream));
+        hipError_t e2 = launch_wp_wide_collect(x0, ws.d_wide_list.p, d_count, ctx->stream);
+        if(e2 != hipSuccess) return hip_fail(e2, "wp_wide_collect");
+        uint32_t n_wide = 0;
+        HIP_TRY(hipMemcpyAsync(&n_wide, d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if(n_wide > n_ent) return fail(LRSC_ERR_LIMIT, "walk-parallel flow: escalation list overflow");
+        n_escalated += n_wide;
+        if(n_wide == 0) return LRSC_OK;
+        WpArgs x = x0;
+        x.max_leaves = (uint32_t)p.max_leaves; x.escalate = 0;
+        x.list = ws.d_wide_list.p; x.reqs = nullptr; x.n_list = n_wide;
+        const WpWideLayout WL = wp_wide_layout(lbytes, pathw, x.max_leaves);
+        uint64_t waves = std::min<uint64_t>(n_wide, max_lanes / 64);
+        waves = std::max<uint64_t>(1, std::min<uint64_t>(waves, (lane_budget / 4) / WL.total));
+        HIP_TRY(ws.d_lane_wide.reserve(waves * WL.total));
+        x.lane_ws = ws.d_lane_wide.p; x.lane_ws_bytes = WL.total; x.lane_pathw = pathw; x.n_lanes = (uint32_t)waves; x.lane_stride = 64;
+        x.queue = ws.d_small.p + 13;
+        HIP_TRY(hipMemsetAsync(x.queue, 0, sizeof(uint32_t), ctx->stream));
+        return timed_launch(ctx, LRSC_K_EXTEND_WIDE, [&]() { return launch_wp_extend_wide(ctx->fm, x, ctx->stream); });
+    };
+
     // ---- read ranges whose prepared tables fit the budget (about 40 bytes per query character + 6 KB per walk) -------------------
     DpStage& stage = cs.stage;
     std::vector<WpDpItem> items;
@@ -1853,7 +1906,7 @@ static int batch_correct_wp(lrsc_ctx* ctx, lrsc_batch* b, lrsc_read_result* res,
             // long_mode 2: the long-gap walks start FIRST, on the side stream with a small share of the wavefront slots (their launch is as
             // long as its longest single walk, not as its walk count), the bulk beside them with the rest; the bulk's failures go to the
             // DP stage while the long walks are still running, theirs in a second call
-            const bool long_first = round == 0 && long_mode == 2 && !use_sched && !p.no_dp && n_mid != 0 && n_mid < n_ent;
+            const bool long_first = round == 0 && long_mode == 2 && !use_sched && !p.no_dp && !escalate && n_mid != 0 && n_mid < n_ent;
             WpArgs xl_first = a;
             if(long_first) {
                 HIP_TRY(ws.d_items2.reserve(n_mid));
@@ -1897,7 +1950,8 @@ static int batch_correct_wp(lrsc_ctx* ctx, lrsc_batch* b, lrsc_read_result* res,
                     }
                     e2 = extend_range(a, ext_list + n_mid, nullptr, n_ent - n_mid, std::min(stats[2], kWpPathwSmall), ctx->stream, 0, 1);
                     if(e2 != hipSuccess || n_mid == 0) return e2;
-                    if(p.no_dp) return extend_range(a, ext_list, nullptr, n_mid, stats[2], ctx->stream, 0, mid_stride);
+                    // (escalating: the wide launch takes their overflows after them, before the DP call)
+                    if(p.no_dp || escalate) return extend_range(a, ext_list, nullptr, n_mid, stats[2], ctx->stream, 0, mid_stride);
                     // with the DP fallback on they start on a side stream once the bulk is through and share the device with the DP
                     // stage of the bulk's failed walks (own DP item list; half of the wavefront slots)
                     long_launch = true;
@@ -1922,6 +1976,10 @@ static int batch_correct_wp(lrsc_ctx* ctx, lrsc_batch* b, lrsc_read_result* res,
                 return e2;
             });
             if(st != LRSC_OK) return st;
+            if(escalate) {
+                const int sw = escalate_walks(a, n_ent, std::max(stats[2], 1u));
+                if(sw != LRSC_OK) return sw;
+            }
             if(long_launch) {
                 long_launch = false;
                 n_long_cap = n_mid;
@@ -2057,9 +2115,9 @@ static int batch_correct_wp(lrsc_ctx* ctx, lrsc_batch* b, lrsc_read_result* res,
                              hs[ord[qs[2]]].leaf_steps, hs[ord[qs[3]]].leaf_steps, hs[ord[qs[4]]].leaf_steps);
             }
             if(verbose)
-                std::fprintf(stderr, "[lrsc] wp reads [%u, %u) round %u: %u entries, %u DP requests (%llu strings), arenas q %.1f MB prep %.1f MB path %.1f MB, %llu schedule rounds so far\n",
+                std::fprintf(stderr, "[lrsc] wp reads [%u, %u) round %u: %u entries, %u DP requests (%llu strings), arenas q %.1f MB prep %.1f MB path %.1f MB, %llu schedule rounds so far, %llu walks escalated so far\n",
                              r0, r1, round, n_ent, n_items, (unsigned long long)stage.n_strings, tot[0] / 1048576.0, tot[1] / 1048576.0, tot[2] / 1048576.0,
-                             (unsigned long long)sched_rounds);
+                             (unsigned long long)sched_rounds, (unsigned long long)n_escalated);
             if(round > 100000) return fail(LRSC_ERR_LIMIT, "walk-parallel flow: too many rounds");
         }
         r0 = r1;
@@ -2147,7 +2205,7 @@ extern "C" int lrsc_batch_correct(lrsc_ctx* ctx, lrsc_batch* b, lrsc_read_result
     if(!ctx || !b || b->ctx != ctx || !res || !n_pieces_out || !out_used) return fail(LRSC_ERR_ARG, "null / foreign batch");
     *n_pieces_out = 0; *out_used = 0;
     const lrsc_params& p = ctx->params;
-    if(p.max_leaves < 1 || p.max_leaves > 32) return fail(LRSC_ERR_UNSUPPORTED, "max_leaves must be 1..32");
+    if(p.max_leaves < 1 || p.max_leaves > (int)kWideMaxLeaves) return fail(LRSC_ERR_UNSUPPORTED, kMaxLeavesMsg);
     if(p.idmer_len < 5 || p.idmer_len > 16) return fail(LRSC_ERR_UNSUPPORTED, "idmer_len must be 5..16");
     if(p.min_kmer_len < p.idmer_len || p.min_kmer_len > 62) return fail(LRSC_ERR_UNSUPPORTED, "min_kmer_len out of range");
     if(p.next_target < 1) return fail(LRSC_ERR_ARG, "next_target must be >= 1");

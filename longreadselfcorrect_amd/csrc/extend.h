@@ -10,6 +10,13 @@ namespace lrsc {
 constexpr uint32_t kMaxChildren = 128;       // 4 extensions x 32 leaves
 constexpr uint32_t kMaxResults = 160;        // result slots per walk (one per terminated lineage)
 enum { LRSC_WALK_ERR_CHILDREN = -101, LRSC_WALK_ERR_RESULTS = -102 };
+// -l above 32: every walk first runs with the narrow capacity (32 leaves, or LRSC_WP_WIDE_CAP); one that outgrows it ends with
+// LRSC_WALK_NEEDS_WIDE (an internal code: never a walk's result) and runs again from its start in a wide launch (wp_wide.hip)
+// with room for -l leaves, 4 x -l children and 5 x -l result slots.
+constexpr uint32_t kNarrowLeaves = 32;
+constexpr uint32_t kWideMaxLeaves = 256;     // the largest -l the walks support
+enum { LRSC_WALK_NEEDS_WIDE = -107 };
+__host__ __device__ inline uint32_t wide_results(uint32_t cap) { return 5u * cap; }
 
 struct WalkResultRec {
     double error_rate;
@@ -58,5 +65,8 @@ struct ExtendArgs {
 size_t leaf_bytes(bool wide);
 hipError_t launch_walk_prepare(const FmIndexDev& fm, const ExtendArgs& a, hipStream_t stream);
 hipError_t launch_walk_extend(const FmIndexDev& fm, const ExtendArgs& a, hipStream_t stream);
+// -l above 32 (wp_wide.hip): walk_extend_kernel's walks one per wavefront, the per-walk region at WalkWork::o_leaves laid out by
+// wp_wide_layout(leaf_bytes, pathw, max_leaves)
+hipError_t launch_walk_extend_wide(const FmIndexDev& fm, const ExtendArgs& a, uint32_t n_waves, hipStream_t stream);
 
 } // namespace lrsc

@@ -172,8 +172,34 @@ __host__ __device__ __forceinline__ void path_set(uint32_t* p, uint32_t i, uint3
     p[i >> 4] = (p[i >> 4] & ~(3u << sh)) | (c << sh);
 }
 
-template <bool WIDE>
-struct Walk {
+// Bitsets of the frontier's slot masks when they outgrow a register (Walk<WIDE, true>): bit i of word i >> 6
+__host__ __device__ __forceinline__ uint32_t bits_words(uint32_t n) { return (n + 63u) >> 6; }
+__host__ __device__ __forceinline__ void bits_set(uint64_t* b, uint32_t i) { b[i >> 6] |= 1ull << (i & 63u); }
+__host__ __device__ __forceinline__ bool bits_get(const uint64_t* b, uint32_t i) { return ((b[i >> 6] >> (i & 63u)) & 1ull) != 0; }
+__host__ __device__ __forceinline__ void bits_clear_all(uint64_t* b, uint32_t n) { for(uint32_t w = 0; w < bits_words(n); ++w) b[w] = 0; }
+// the lowest set bit, cleared (the set is never empty where it is called)
+__host__ __device__ __forceinline__ uint32_t bits_take_lowest(uint64_t* b, uint32_t n)
+{
+    for(uint32_t w = 0; w < bits_words(n); ++w)
+        if(b[w]) { const uint32_t s = (uint32_t)__builtin_ctzll(b[w]); b[w] &= b[w] - 1ull; return w * 64u + s; }
+    return 0;
+}
+
+// The frontier's capacity.  Walk<WIDE> (BIG = false) is the 32-leaf walk: 32 ring / path slots with their masks in 32-bit words,
+// kMaxChildren children, kMaxResults result slots.  Walk<WIDE, true> takes its capacity from `cap` at run time -- cap leaves, ring
+// and path slots, 4 cap children, cap_results >= 5 cap result slots -- and keeps its slot masks as bitsets in memory.
+template <bool BIG> struct WalkCap {};
+template <> struct WalkCap<true> {
+    uint32_t cap, cap_children, cap_results;
+    uint64_t* ring_bits;              // bit s: ring slot s is free              [bits_words(cap)]
+    uint64_t* path_bits;              // bit s: path slot s is free              [bits_words(cap)]
+    uint64_t* alive_bits;             // PrunedBySeedSupport: child c survived   [bits_words(cap_children)]
+    uint64_t* child_bits;             // ... leaf i of cur[] has a surviving child [bits_words(cap)]
+    uint64_t* seen_bits;              // the commit: parent i has had its first child [bits_words(cap)]
+};
+
+template <bool WIDE, bool BIG = false>
+struct Walk : WalkCap<BIG> {
     using P = typename Lay<WIDE>::pos_t;
     // index
     StrandC<P> sF, sR;
@@ -202,7 +228,7 @@ struct Walk {
     uint32_t n_term;
     uint64_t tmask0, tmask1;          // 128-bit filter over the target seed's minOverlap-mers (hash of their last <= 16 characters)
     Leaf<P>* cur;  uint32_t n_cur;
-    Leaf<P>* leaf_small;              // the 32-slot leaf buffer (the other one holds kMaxChildren); cur / nxt swap between them
+    Leaf<P>* leaf_small;              // the small_cap()-slot leaf buffer (the other one holds max_children()); cur / nxt swap between them
     Leaf<P>* nxt;  uint32_t n_nxt;
     double* rings;                    // [32][100]
     uint32_t* paths;  uint32_t pathw; // [32][pathw]
@@ -464,10 +490,18 @@ struct Walk {
         return mask;
     }
 
+    // capacities: the leaf buffer `leaf_small`, the children of a step, the result slots
+    LRSC_WALK_FN __forceinline__ uint32_t small_cap() const { if constexpr(BIG) return this->cap; else return 32u; }
+    LRSC_WALK_FN __forceinline__ uint32_t max_children() const { if constexpr(BIG) return this->cap_children; else return kMaxChildren; }
+    LRSC_WALK_FN __forceinline__ uint32_t max_results() const { if constexpr(BIG) return this->cap_results; else return kMaxResults; }
+
     LRSC_WALK_FN void free_leaf_slots(const Leaf<P>& lf)
     {
-        ring_free |= 1u << lf.ring;
-        path_free |= 1u << lf.path;
+        if constexpr(BIG) { bits_set(this->ring_bits, lf.ring); bits_set(this->path_bits, lf.path); }
+        else {
+            ring_free |= 1u << lf.ring;
+            path_free |= 1u << lf.path;
+        }
     }
 
     // ---- attempToExtend (.cpp:373-465) + updateLeaves (:468-488) -------------------------------------------
@@ -516,7 +550,7 @@ struct Walk {
             // updateLeaves: children in base order; leafInfo(child) fields (LongReadCorrectByOverlap.h:172-203)
             for(uint32_t b = 0; b < 4; ++b) {
                 if(!(mask & (1u << b))) continue;
-                if(n_nxt >= kMaxChildren) { error = LRSC_WALK_ERR_CHILDREN; return; }
+                if(n_nxt >= max_children()) { error = LRSC_WALK_ERR_CHILDREN; return; }
                 const Leaf<P> ch = make_child(par, i, b, ext[b]);
                 if(ch.kmerFrequency > highfreqThreshold) n_highfreq++;      // for isInsufficientFreqs, which looks at exactly these values
                 nxt[n_nxt++] = ch;
@@ -680,12 +714,14 @@ struct Walk {
         const uint64_t smallSeedIdx = currSeedIdx <= indelOffset ? 0 : currSeedIdx - indelOffset;
         const uint64_t largeSeedIdx = (currSeedIdx + indelOffset) >= (Lq - seedSize) ? (Lq - seedSize) : currSeedIdx + indelOffset;
         alive_lo = 0; alive_hi = 0; has_child = 0;
+        if constexpr(BIG) { bits_clear_all(this->alive_bits, n_nxt); bits_clear_all(this->child_bits, n_cur); }
         for(uint32_t c = 0; c < n_nxt; ++c) {
             Leaf<P> leaf = nxt[c];                               // in registers for the whole evaluation, one burst each way
             // createChild copied the parent's ring id into the child: cur[leaf.parent].ring == leaf.ring until the commit
             prune_leaf<true>(leaf, rings + (uint64_t)leaf.ring * 100, currSeedIdx, smallSeedIdx, largeSeedIdx);
             nxt[c] = leaf;
-            if(leaf.alive) { if(c < 64) alive_lo |= 1ull << c; else alive_hi |= 1ull << (c - 64); has_child |= 1u << leaf.parent; }
+            if constexpr(BIG) { if(leaf.alive) { bits_set(this->alive_bits, c); bits_set(this->child_bits, leaf.parent); } }
+            else if(leaf.alive) { if(c < 64) alive_lo |= 1ull << c; else alive_hi |= 1ull << (c - 64); has_child |= 1u << leaf.parent; }
         }
     }
 
@@ -695,7 +731,7 @@ struct Walk {
         const int hit = term_scan(lf);
         if(hit < 0) return;
         if(lf.res_first == -1) {                          // the first hit of the scan takes a result slot
-            if(n_results >= kMaxResults) { error = LRSC_WALK_ERR_RESULTS; return; }
+            if(n_results >= max_results()) { error = LRSC_WALK_ERR_RESULTS; return; }
             ++n_results;
             lf.res_first = (int)n_results;
         }
@@ -751,6 +787,9 @@ struct Walk {
 
     bool ended;                        // the frontier overflowed maxLeaves: the loop ends after this isTerminated
     bool profile = false;              // per-step tick counters on (LRSC_CORRECT_PROFILE)
+    // maxLeaves is a narrow launch's capacity below the walk's true -l: overflowing it (or the result slots) is not the walk's end
+    // but LRSC_WALK_NEEDS_WIDE from finish()
+    bool escalate = false;
 
     // The constructor's per-walk tables that stay fixed during the walk (.cpp:90-94,127-152 after the bulk look-ups of
     // prepare_offset): the interval "trees" as sorted k-mer chains, the 5-mer chains, the isTerminated filter.
@@ -807,6 +846,12 @@ struct Walk {
     LRSC_WALK_FN LRSC_WALK_NOINLINE void begin_root(const P* root_iv)
     {
         ring_free = 0xFFFFFFFEu; path_free = 0xFFFFFFFEu;
+        if constexpr(BIG)
+            for(uint32_t w = 0; w < bits_words(this->cap); ++w) {
+                const uint32_t n = this->cap - w * 64u;
+                const uint64_t m = n >= 64 ? ~0ull : (1ull << n) - 1ull;
+                this->ring_bits[w] = w ? m : m & ~1ull; this->path_bits[w] = w ? m : m & ~1ull;
+            }
         Leaf<P>& root = cur[0];
         root.suf_lo = 0; root.suf_hi = 0;
         for(uint32_t t = 0; t < initk; ++t) suf_push(root, q[t]);
@@ -957,8 +1002,12 @@ struct Walk {
             PrunedBySeedSupport();
             tock(4, t);
             t = tick();
-            const uint32_t survivors = (uint32_t)(__builtin_popcountll(alive_lo) + __builtin_popcountll(alive_hi));
-            auto is_alive = [&](uint32_t c) -> bool { return ((c < 64 ? alive_lo >> c : alive_hi >> (c - 64)) & 1ull) != 0; };
+            uint32_t survivors = (uint32_t)(__builtin_popcountll(alive_lo) + __builtin_popcountll(alive_hi));
+            if constexpr(BIG) { survivors = 0; for(uint32_t w = 0; w < bits_words(n_nxt); ++w) survivors += (uint32_t)__builtin_popcountll(this->alive_bits[w]); }
+            auto is_alive = [&](uint32_t c) -> bool {
+                if constexpr(BIG) return bits_get(this->alive_bits, c);
+                else return ((c < 64 ? alive_lo >> c : alive_hi >> (c - 64)) & 1ull) != 0;
+            };
             ++steps;
             if(survivors > maxLeaves) {
                 // the frontier overflows: the loop ends after this isTerminated, no leaf state is needed any more
@@ -977,18 +1026,27 @@ struct Walk {
             // in place (SAINode::extend), further ones get copies (createChild).  A child still carries its parent's
             // ring / path ids and path length (createChild copied them), so the parent need not be read again.
             // has_child (from PrunedBySeedSupport): bit i = leaf i of cur[] has a surviving child (n_cur <= 32)
-            for(uint32_t i = 0; i < n_cur; ++i) if(!((has_child >> i) & 1u)) free_leaf_slots(cur[i]);
+            if constexpr(BIG) { for(uint32_t i = 0; i < n_cur; ++i) if(!bits_get(this->child_bits, i)) free_leaf_slots(cur[i]); }
+            else for(uint32_t i = 0; i < n_cur; ++i) if(!((has_child >> i) & 1u)) free_leaf_slots(cur[i]);
             const bool want_term = currentLength >= minLength;
             uint32_t seen = 0, w = 0;
+            if constexpr(BIG) bits_clear_all(this->seen_bits, n_cur);
             for(uint32_t c = 0; c < n_nxt; ++c) {
                 if(!is_alive(c)) continue;
                 Leaf<P> ch = nxt[c];                             // registers: one burst in, one out
-                if((seen >> ch.parent) & 1u) {
+                bool further;
+                if constexpr(BIG) further = bits_get(this->seen_bits, ch.parent); else further = ((seen >> ch.parent) & 1u) != 0;
+                if(further) {
                     // a further child of this parent: copies of the ring and of the path as they are BEFORE this step's appends
                     // (the in-place child of the parent has only written slots the copies do not read: see below)
                     const uint16_t pr = ch.ring, pp = ch.path;
-                    ch.ring = (uint16_t)__builtin_ctz(ring_free); ring_free &= ring_free - 1u;     // survivors <= 32 slots: never empty here
-                    ch.path = (uint16_t)__builtin_ctz(path_free); path_free &= path_free - 1u;
+                    if constexpr(BIG) {                                                  // survivors <= cap slots: never empty here
+                        ch.ring = (uint16_t)bits_take_lowest(this->ring_bits, this->cap);
+                        ch.path = (uint16_t)bits_take_lowest(this->path_bits, this->cap);
+                    } else {
+                        ch.ring = (uint16_t)__builtin_ctz(ring_free); ring_free &= ring_free - 1u;     // survivors <= 32 slots: never empty here
+                        ch.path = (uint16_t)__builtin_ctz(path_free); path_free &= path_free - 1u;
+                    }
                     const double* src = rings + (uint64_t)pr * 100;
                     double* dst = rings + (uint64_t)ch.ring * 100;
                     const uint32_t own = (ch.hist_size - 1) % 100;                 // the slot this child overwrites anyway
@@ -998,7 +1056,7 @@ struct Walk {
                     const uint32_t nw = (ch.path_len + 16) >> 4;
                     for(uint32_t k = 0; k < nw; ++k) pd[k] = ps[k];
                 }
-                seen |= 1u << ch.parent;
+                if constexpr(BIG) bits_set(this->seen_bits, ch.parent); else seen |= 1u << ch.parent;
                 rings[(uint64_t)ch.ring * 100 + (ch.hist_size - 1) % 100] = ch.globalErr;     // GlobalErrorRateRecord.push_back
                 path_set(paths + (uint64_t)ch.path * pathw, ch.path_len, ch.ext);
                 ch.path_len++;
@@ -1008,7 +1066,7 @@ struct Walk {
             (void)want_term;
             // m_leaves = newLeaves: the two leaf buffers trade places when the old `cur` region (32 or kMaxChildren slots) can take
             // the next step's children (4 per survivor); otherwise the survivors are copied down as before
-            if(4u * w <= (cur == leaf_small ? 32u : kMaxChildren)) { Leaf<P>* t2 = cur; cur = nxt; nxt = t2; }
+            if(4u * w <= (cur == leaf_small ? small_cap() : max_children())) { Leaf<P>* t2 = cur; cur = nxt; nxt = t2; }
             else for(uint32_t i = 0; i < w; ++i) cur[i] = nxt[i];
             n_cur = w;
             tock(5, t);
@@ -1024,6 +1082,8 @@ struct Walk {
 
     LRSC_WALK_FN LRSC_WALK_NOINLINE int finish(uint32_t* out_len, uint32_t* out_words, uint32_t* out_match_i)
     {
+        // a walk that outgrew the narrow capacity of an escalating launch goes to the wide launch (the same walk from its start)
+        if(escalate && (ended || error == LRSC_WALK_ERR_RESULTS)) return LRSC_WALK_NEEDS_WIDE;
         if(error) return error;
         // --- findTheBestPath (.cpp:214-236) ---
         if(n_results > 0) {

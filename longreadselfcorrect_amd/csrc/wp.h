@@ -90,6 +90,21 @@ __host__ __device__ inline WpLaneLayout wp_lane_layout(uint32_t lbytes, uint32_t
     return L;
 }
 
+// per-wavefront workspace of the wide extension kernels (wp_wide.hip) for a capacity of `cap` leaves: leaf buffers of cap and 4 cap,
+// cap error-history rings, wide_results(cap) result records, cap path slots + one per result
+struct WpWideLayout { uint32_t leaves, rings, results, paths, total; };
+__host__ __device__ inline WpWideLayout wp_wide_layout(uint32_t lbytes, uint32_t pathw, uint32_t cap)
+{
+    WpWideLayout L;
+    uint32_t o = 0;
+    L.leaves = o;  o = (o + 5u * cap * lbytes + 15u) & ~15u;
+    L.rings = o;   o += cap * 100u * 8u;
+    L.results = o; o += wide_results(cap) * (uint32_t)sizeof(WalkResultRec);
+    L.paths = o;   o += (cap + wide_results(cap)) * pathw * 4u;
+    L.total = (o + 63u) & ~63u;
+    return L;
+}
+
 // per-read layout: its slots, its output slot
 struct WpReadWork {
     uint64_t out_off;            // into out_codes
@@ -177,6 +192,7 @@ struct WpArgs {
     uint8_t* walk_log;
     DevCounters* ctr;
     unsigned long long* prof;    // LRSC_CORRECT_PROFILE: 16 tick totals of the extension kernel (per-lane wall ticks summed over lanes)
+    uint32_t escalate;           // max_leaves is the narrow cap below the true -l: a walk that outgrows it ends with LRSC_WALK_NEEDS_WIDE
 };
 
 constexpr uint32_t kWpPathwSmall = 64, kWpPathwMid = 256;
@@ -227,6 +243,10 @@ hipError_t launch_wp_begin(const FmIndexDev& fm, const WpArgs& a, hipStream_t st
 hipError_t launch_wp_extend(const FmIndexDev& fm, const WpArgs& a, hipStream_t stream);
 // lane_stride 64 launches with the frontier across the wavefront (wp_wave.hip): one wavefront per walk in flight (a.n_lanes of them)
 hipError_t launch_wp_extend_wave(const FmIndexDev& fm, const WpArgs& a, hipStream_t stream);
+// -l above the narrow cap (wp_wide.hip): the slots of a.list whose walk ended with LRSC_WALK_NEEDS_WIDE, and their wide launch with
+// a.max_leaves = the true -l, one walk per wavefront (a.n_lanes of them, wp_wide_layout workspaces)
+hipError_t launch_wp_wide_collect(const WpArgs& a, uint32_t* out, uint32_t* n_out, hipStream_t stream);
+hipError_t launch_wp_extend_wide(const FmIndexDev& fm, const WpArgs& a, hipStream_t stream);
 // one round of the two-class schedule: fast kernel, list rotation, general kernel, list rotation
 hipError_t launch_wp_sched_init(const WpSchedArgs& sa, uint32_t* list_storage, uint32_t n_fresh, hipStream_t stream);
 hipError_t launch_wp_sched_round(const FmIndexDev& fm, const WpArgs& a, const WpSchedArgs& fast, const WpSchedArgs& general, uint32_t n_lanes_fast,

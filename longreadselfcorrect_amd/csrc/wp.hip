@@ -313,7 +313,7 @@ __global__ __launch_bounds__(64, LRSC_WP_EXTEND_OCC) void wp_extend_kernel(FmInd
     W.sF = strand_consts<P>(fm.strand[LRSC_RBWT]);
     W.sR = strand_consts<P>(fm.strand[LRSC_BWT]);
     W.fm = &fm; W.mtab = mtab;
-    W.seedSize = a.seed_size; W.minOverlap = a.min_overlap; W.maxLeaves = a.max_leaves;
+    W.seedSize = a.seed_size; W.minOverlap = a.min_overlap; W.maxLeaves = a.max_leaves; W.escalate = a.escalate != 0;
     W.PBcoverage = a.pb_coverage; W.PacBioErrorRate = a.pacbio_error_rate; W.errorRate = 0.25; W.localK = 100;
     W.freqsOfKmerSize = a.freqs_of_kmer_size;
     const WpLaneLayout LL = wp_lane_layout(a.lbytes, a.lane_pathw);
@@ -454,7 +454,7 @@ __device__ __forceinline__ void wp_walk_consts(Walk<WIDE>& W, const FmIndexDev& 
     W.sF = strand_consts<P>(fm.strand[LRSC_RBWT]);
     W.sR = strand_consts<P>(fm.strand[LRSC_BWT]);
     W.fm = &fm; W.mtab = mtab;
-    W.seedSize = a.seed_size; W.minOverlap = a.min_overlap; W.maxLeaves = a.max_leaves;
+    W.seedSize = a.seed_size; W.minOverlap = a.min_overlap; W.maxLeaves = a.max_leaves; W.escalate = a.escalate != 0;
     W.PBcoverage = a.pb_coverage; W.PacBioErrorRate = a.pacbio_error_rate; W.errorRate = 0.25; W.localK = 100;
     W.freqsOfKmerSize = a.freqs_of_kmer_size;
     W.n_rank = 0; W.n_blk = 0; W.steps = 0; W.leaf_steps = 0; W.max_front = 1; W.error = 0; W.cyc_setup = 0; W.cyc_loop = 0; W.prof = nullptr; W.profile = false;

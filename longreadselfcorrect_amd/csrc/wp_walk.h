@@ -5,8 +5,8 @@
 namespace lrsc {
 
 // the walk's fixed inputs: the query and the tables wp_prepare_kernel / wp_begin_kernel built in the slot's prepared workspace
-template <bool WIDE>
-__device__ __forceinline__ void wp_bind_static(Walk<WIDE>& W, const WpArgs& a, const WpSlot& s)
+template <bool WIDE, bool BIG>
+__device__ __forceinline__ void wp_bind_static(Walk<WIDE, BIG>& W, const WpArgs& a, const WpSlot& s)
 {
     using P = typename Lay<WIDE>::pos_t;
     const WpPrepLayout L = wp_prep_layout(s.lq, s.trg_len, a.seed_size, a.min_overlap, a.psz);
