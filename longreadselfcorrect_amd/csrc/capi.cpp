@@ -1511,23 +1511,18 @@ struct WpScratch {
     DevBuf<DevCounters> d_ctr2;
     hipEvent_t ev_side_t0 = nullptr, ev_side_t1 = nullptr;
     DevBuf<WpRequest> d_req;
-    DevBuf<uint8_t> d_prep, d_lane, d_lane_side, d_lane_side2, d_ctx[2], d_lane_wide;
+    DevBuf<uint8_t> d_prep, d_lane, d_lane_side, d_lane_wide;
     DevBuf<uint32_t> d_wide_list;          // the escalated walks of a round (-l above the narrow cap)
-    hipStream_t side[2] = {nullptr, nullptr};
-    hipEvent_t ev_side[2] = {nullptr, nullptr}, ev_ready = nullptr;
+    hipStream_t side = nullptr;
+    hipEvent_t ev_ready = nullptr;
     DevBuf<unsigned long long> d_prof;
-    DevBuf<WpSched> d_sched;
-    DevBuf<uint32_t> d_sched_lists[2];
     DevArena persist;
     void* cub_tmp = nullptr;
     size_t cub_cap = 0;
     ~WpScratch()
     {
         if(cub_tmp) (void)hipFree(cub_tmp);
-        for(int i = 0; i < 2; ++i) {
-            if(side[i]) { (void)hipStreamSynchronize(side[i]); (void)hipStreamDestroy(side[i]); }
-            if(ev_side[i]) (void)hipEventDestroy(ev_side[i]);
-        }
+        if(side) { (void)hipStreamSynchronize(side); (void)hipStreamDestroy(side); }
         if(ev_ready) (void)hipEventDestroy(ev_ready);
         if(ev_side_t0) (void)hipEventDestroy(ev_side_t0);
         if(ev_side_t1) (void)hipEventDestroy(ev_side_t1);
@@ -1628,8 +1623,6 @@ static int batch_correct_wp(lrsc_ctx* ctx, lrsc_batch* b, lrsc_read_result* res,
     a.out_codes = cs.d_codes_out.p; a.piece_start = cs.d_pieces.p;
     a.auto_dp = (!p.no_dp && p.next_target == 1) ? 1u : 0u;
     a.general_quorum_pct = 70; a.general_max_wait = 6;
-    size_t dp_split_pct = 100;               // share of the bulk's failed walks in the first DP call when long-gap walks run beside it (100: theirs alone in the second)
-    if(const char* ev = std::getenv("LRSC_WP_DP_SPLIT")) dp_split_pct = (size_t)std::min(100, std::max(10, std::atoi(ev)));
     if(const char* ev = std::getenv("LRSC_WP_GEN_QUORUM")) a.general_quorum_pct = (uint32_t)std::min(100, std::max(0, std::atoi(ev)));
     if(const char* ev = std::getenv("LRSC_WP_GEN_WAIT")) a.general_max_wait = (uint32_t)std::max(0, std::atoi(ev));
     a.ctr = ctx->d_ctr;
@@ -1653,130 +1646,38 @@ static int batch_correct_wp(lrsc_ctx* ctx, lrsc_batch* b, lrsc_read_result* res,
     if(const char* ev = std::getenv("LRSC_WP_PREP_MB")) prep_budget = std::max<uint64_t>(1, (uint64_t)std::atoll(ev)) << 20;
     if(const char* ev = std::getenv("LRSC_WP_LANE_MB")) lane_budget = std::max<uint64_t>(1, (uint64_t)std::atoll(ev)) << 20;
 
-    // side streams: the few walks across long gaps and the mid-size class run beside the bulk instead of before it (each is
-    // latency-bound on its own: a walk is a chain of dependent steps)
-    for(int i = 0; i < 2; ++i) {
-        if(!ws.side[i]) HIP_TRY(hipStreamCreateWithFlags(&ws.side[i], hipStreamNonBlocking));
-        if(!ws.ev_side[i]) HIP_TRY(hipEventCreateWithFlags(&ws.ev_side[i], hipEventDisableTiming));
-    }
+    // side stream: the few walks across long gaps run beside the DP stage of the bulk's failed walks instead of before it (they are
+    // latency-bound on their own: a walk is a chain of dependent steps)
+    if(!ws.side) HIP_TRY(hipStreamCreateWithFlags(&ws.side, hipStreamNonBlocking));
     if(!ws.ev_ready) HIP_TRY(hipEventCreateWithFlags(&ws.ev_ready, hipEventDisableTiming));
 
-    uint32_t mid_stride = 64, long_mode = 0;
-    if(const char* ev = std::getenv("LRSC_WP_LONG_MODE")) long_mode = (uint32_t)std::atoi(ev);
     // one-walk-per-wavefront launches: 1 = the frontier across the wavefront (wp_extend_wave_kernel), 0 = lane 0 walks alone
     // (wp_extend_kernel); 2 = test hook: every extension launch goes through wp_extend_wave_kernel at stride 64
     uint32_t wave_mode = 1;
     if(const char* ev = std::getenv("LRSC_WP_WAVE")) wave_mode = (uint32_t)std::min(2, std::max(0, std::atoi(ev)));
-    uint32_t leaves_in_lds = 0;                      // measured: 77.5-77.7 vs 79.1-80.3 corrected Mbases/s with the leaves in LDS (the DP stage beside it wants the LDS)
-    if(const char* ev = std::getenv("LRSC_WP_LEAVES_LDS")) leaves_in_lds = std::atoi(ev) != 0;
-    uint32_t long_first_div = 8;
-    if(const char* ev = std::getenv("LRSC_WP_SIDE_DIV")) long_first_div = (uint32_t)std::min(64, std::max(2, std::atoi(ev)));
-    if(const char* ev = std::getenv("LRSC_WP_MID_STRIDE")) { const int v = std::atoi(ev); if(v == 1 || v == 2 || v == 4 || v == 8 || v == 16 || v == 32 || v == 64) mid_stride = (uint32_t)v; }
-    // One launch of the one-kernel form (wp_extend_kernel: every lane runs both kinds of step) over `count` list entries;
-    // stride 64 = one walk per wavefront
-    bool reserve_side = false;
-    uint64_t side_div = 2;                                                   // the side launch's share of the wavefront slots: 1 / side_div
-    auto extend_range = [&](WpArgs x, const uint32_t* list, const WpRequest* reqs, uint32_t count, uint32_t pathw, hipStream_t st, int which, uint32_t stride) -> hipError_t {
+    // One launch of the extension over `count` list entries, stride 64 = one walk per wavefront.  The side launch (side: the long-gap
+    // walks beside the DP stage) and the launches on ctx->stream are persistent and share the device, so the side launch gets half of
+    // the resident wavefronts and a quarter of the lane budget -- a launch that fills every slot first would keep the others out
+    // until it ends.
+    auto extend_range = [&](WpArgs x, const uint32_t* list, const WpRequest* reqs, uint32_t count, uint32_t pathw, hipStream_t st, bool side, uint32_t stride) -> hipError_t {
         if(count == 0) return hipSuccess;
         if(wave_mode == 2) stride = 64;
         const WpLaneLayout LL = wp_lane_layout(lbytes, pathw);
-        // wavefront slots: the side launches (which != 0) and the bulk launch are persistent and share the device, so each gets a share
-        // of the resident wavefronts -- a launch that fills every slot first would keep the others out until it ends
         const uint64_t slots = max_lanes / 64;                                        // resident wavefronts of these kernels
-        const uint64_t side_part = std::max<uint64_t>(1, slots / side_div);
-        const uint64_t share = which == 1 ? side_part : which == 2 ? slots / 4 : (reserve_side ? slots - side_part : slots);
+        const uint64_t share = side ? std::max<uint64_t>(1, slots / 2) : slots;
         uint64_t lanes = std::min<uint64_t>(stride == 1 ? (((uint64_t)count + 63) & ~63ull) : count, share * 64 / stride);
-        lanes = std::max<uint64_t>(1, std::min<uint64_t>(lanes, (lane_budget / (which ? 4 : 1)) / LL.total));
+        lanes = std::max<uint64_t>(1, std::min<uint64_t>(lanes, (lane_budget / (side ? 4 : 1)) / LL.total));
         if(stride == 1) lanes = std::max<uint64_t>(64, lanes & ~63ull);
-        DevBuf<uint8_t>& buf = which == 2 ? ws.d_lane_side2 : which ? ws.d_lane_side : ws.d_lane;
+        DevBuf<uint8_t>& buf = side ? ws.d_lane_side : ws.d_lane;
         hipError_t e2 = buf.reserve(lanes * LL.total);
         if(e2 != hipSuccess) return e2;
         x.list = list; x.reqs = reqs; x.n_list = count;
         x.lane_ws = buf.p; x.lane_ws_bytes = LL.total; x.lane_pathw = pathw; x.n_lanes = (uint32_t)lanes; x.lane_stride = stride;
-        x.leaves_in_lds = leaves_in_lds;
-        x.queue = ws.d_small.p + 8 + which;
+        x.queue = ws.d_small.p + (side ? 9 : 8);
         e2 = hipMemsetAsync(x.queue, 0, sizeof(uint32_t), st);
         if(e2 != hipSuccess) return e2;
         if(stride == 64 && wave_mode != 0) return launch_wp_extend_wave(ctx->fm, x, st);
         return launch_wp_extend(ctx->fm, x, st);
-    };
-
-    // The two-class schedule (wp_fast_kernel / wp_general_kernel): contexts = walks in flight.  Up to two pools (result-path
-    // classes) advance side by side, each on its own stream.
-    bool use_sched = false;
-    if(const char* ev = std::getenv("LRSC_WP_SCHED")) use_sched = std::atoi(ev) != 0;
-    uint32_t sched_budget_fast = 32, sched_budget_general = 24, sched_quorum = 25;
-    if(const char* ev = std::getenv("LRSC_WP_BUDGET_FAST")) sched_budget_fast = (uint32_t)std::max(1, std::atoi(ev));
-    if(const char* ev = std::getenv("LRSC_WP_BUDGET_GENERAL")) sched_budget_general = (uint32_t)std::max(1, std::atoi(ev));
-    if(const char* ev = std::getenv("LRSC_WP_QUORUM")) sched_quorum = (uint32_t)std::min(100, std::max(0, std::atoi(ev)));
-    uint64_t sched_rounds = 0;
-    struct Pool { WpSchedArgs sf, sg; uint32_t count = 0, lanes = 0; hipStream_t st = nullptr; bool done = true; };
-    auto pool_setup = [&](Pool& P, int which, const uint32_t* list, uint32_t count, uint32_t pathw, uint64_t budget_bytes, hipStream_t st) -> hipError_t {
-        P.count = count; P.st = st; P.done = count == 0;
-        if(count == 0) return hipSuccess;
-        const WpLaneLayout LL = wp_lane_layout(lbytes, pathw);
-        WpSchedArgs sa{};
-        sa.ctx_bytes = 64 + LL.total; sa.ctx_pathw = pathw;
-        uint64_t n_ctx = std::min<uint64_t>(count, 2ull * max_lanes);
-        n_ctx = std::max<uint64_t>(1, std::min<uint64_t>(n_ctx, budget_bytes / sa.ctx_bytes));
-        sa.n_ctx = (uint32_t)n_ctx;
-        hipError_t e2 = ws.d_ctx[which].reserve(n_ctx * sa.ctx_bytes);
-        if(e2 == hipSuccess) e2 = ws.d_sched.reserve(2);
-        if(e2 == hipSuccess) e2 = ws.d_sched_lists[which].reserve((size_t)kWpLists * n_ctx);
-        if(e2 != hipSuccess) return e2;
-        sa.sched = ws.d_sched.p + which; sa.fresh = list; sa.ctx_ws = ws.d_ctx[which].p;
-        sa.quorum_pct = sched_quorum;
-        e2 = launch_wp_sched_init(sa, ws.d_sched_lists[which].p, count, st);
-        if(e2 != hipSuccess) return e2;
-        P.lanes = (uint32_t)std::min<uint64_t>((n_ctx + 63) & ~63ull, max_lanes);
-        P.sf = sa; P.sg = sa;
-        P.sf.budget = sched_budget_fast; P.sg.budget = sched_budget_general;
-        return hipSuccess;
-    };
-    auto pools_run = [&](const WpArgs& x, Pool* pools, int n_pools) -> hipError_t {
-        for(uint32_t iter = 0;; ++iter) {
-            bool any = false;
-            for(int i = 0; i < n_pools; ++i) {
-                Pool& P = pools[i];
-                if(P.done) continue;
-                any = true;
-                // one round = fast kernel, general kernel (the two differ in their budget: steps / leaf-steps per pull)
-                hipError_t e2 = launch_wp_sched_round(ctx->fm, x, P.sf, P.sg, P.lanes, P.lanes, P.st);
-                if(e2 != hipSuccess) return e2;
-                ++sched_rounds;
-            }
-            if(!any) break;
-            if((iter & 3u) == 3u) {
-                uint32_t fin[2] = {0, 0};
-                for(int i = 0; i < n_pools; ++i)
-                    if(!pools[i].done) {
-                        hipError_t e2 = hipMemcpyAsync(&fin[i], &pools[i].sf.sched->finished, sizeof(uint32_t), hipMemcpyDeviceToHost, pools[i].st);
-                        if(e2 != hipSuccess) return e2;
-                    }
-                for(int i = 0; i < n_pools; ++i)
-                    if(!pools[i].done) {
-                        hipError_t e2 = hipStreamSynchronize(pools[i].st);
-                        if(e2 != hipSuccess) return e2;
-                        if(fin[i] >= pools[i].count) pools[i].done = true;
-                    }
-                if(iter > 4000000u) return hipErrorLaunchFailure;
-            }
-        }
-        return hipSuccess;
-    };
-    // everything on the side streams starts after what is on ctx->stream now, and ctx->stream goes on after them
-    auto side_begin = [&]() -> hipError_t {
-        hipError_t e2 = hipEventRecord(ws.ev_ready, ctx->stream);
-        for(int i = 0; i < 2 && e2 == hipSuccess; ++i) e2 = hipStreamWaitEvent(ws.side[i], ws.ev_ready, 0);
-        return e2;
-    };
-    auto side_join = [&]() -> hipError_t {
-        hipError_t e2 = hipSuccess;
-        for(int i = 0; i < 2 && e2 == hipSuccess; ++i) {
-            e2 = hipEventRecord(ws.ev_side[i], ws.side[i]);
-            if(e2 == hipSuccess) e2 = hipStreamWaitEvent(ctx->stream, ws.ev_side[i], 0);
-        }
-        return e2;
     };
 
     // The escalated walks of a round (entries of a.list / the range whose narrow walk ended with LRSC_WALK_NEEDS_WIDE) run again
@@ -1891,7 +1792,7 @@ static int batch_correct_wp(lrsc_ctx* ctx, lrsc_batch* b, lrsc_read_result* res,
 
             // launch order of round 0: long walks first (the few walks across long gaps need bigger path slots: own launches)
             const uint32_t* ext_list = a.list;
-            uint32_t n_big = 0, n_mid = 0, n_long_cap = 0;
+            uint32_t n_mid = 0;
             bool long_launch = false, long_pending = false;
             if(round == 0) {
                 // list_tmp = slot_base + i
@@ -1901,78 +1802,23 @@ static int batch_correct_wp(lrsc_ctx* ctx, lrsc_batch* b, lrsc_read_result* res,
                 e = wp_sort_list(ws.d_key.p, ws.d_key_tmp.p, ws.d_list.p, ws.d_list_tmp.p, n_ent, &ws.cub_tmp, &ws.cub_cap, ctx->stream);
                 if(e != hipSuccess) return hip_fail(e, "wp_sort_list");
                 ext_list = ws.d_list.p;
-                n_mid = stats[0]; n_big = stats[1];
-            }
-            // long_mode 2: the long-gap walks start FIRST, on the side stream with a small share of the wavefront slots (their launch is as
-            // long as its longest single walk, not as its walk count), the bulk beside them with the rest; the bulk's failures go to the
-            // DP stage while the long walks are still running, theirs in a second call
-            const bool long_first = round == 0 && long_mode == 2 && !use_sched && !p.no_dp && !escalate && n_mid != 0 && n_mid < n_ent;
-            WpArgs xl_first = a;
-            if(long_first) {
-                HIP_TRY(ws.d_items2.reserve(n_mid));
-                xl_first.dp_items = ws.d_items2.p; xl_first.n_dp_items = ws.d_small.p + 12; xl_first.dp_items_cap = n_mid;
-                HIP_TRY(ws.d_ctr2.reserve(kCtrShards));
-                HIP_TRY(hipMemsetAsync(ws.d_ctr2.p, 0, kCtrShards * sizeof(DevCounters), ctx->stream));
-                xl_first.ctr = ws.d_ctr2.p;
-                if(!ws.ev_side_t0) HIP_TRY(hipEventCreate(&ws.ev_side_t0));
+                n_mid = stats[0];
             }
             const int st = timed_launch(ctx, LRSC_K_EXTEND, [&]() -> hipError_t {
                 hipError_t e2 = launch_wp_prepare(ctx->fm, a, ctx->stream);
                 if(e2 == hipSuccess) e2 = launch_wp_begin(ctx->fm, a, ctx->stream);
                 if(e2 != hipSuccess) return e2;
-                if(long_first) {
-                    e2 = side_begin();
-                    if(e2 == hipSuccess) e2 = hipEventRecord(ws.ev_side_t0, ws.side[0]);
-                    side_div = long_first_div;
-                    reserve_side = true;
-                    if(e2 == hipSuccess) e2 = extend_range(xl_first, ext_list, nullptr, n_mid, stats[2], ws.side[0], 1, mid_stride);
-                    if(e2 == hipSuccess) e2 = extend_range(a, ext_list + n_mid, nullptr, n_ent - n_mid, std::min(stats[2], kWpPathwSmall), ctx->stream, 0, 1);
-                    reserve_side = false;
-                    side_div = 2;
-                    n_long_cap = n_mid;
-                    long_pending = e2 == hipSuccess;
-                    return e2;
-                }
-                if(!use_sched) {
-                    if(round != 0) return extend_range(a, a.list, a.reqs, n_ent, std::max(stats[2], 1u), ctx->stream, 0, n_ent <= 16384 ? 64u : n_ent <= 65536 ? 16u : 1u);
-                    // the walks across long gaps (the first n_mid of the launch order) run thinly spread over wavefronts: a lane-per-walk
-                    // wavefront advances at the pace of its slowest lane, and these are thousands of wide steps long.  They follow the bulk
-                    // (both launches are persistent and want every wavefront slot).
-                    if(long_mode == 1 && n_mid != 0) {
-                        // beside the bulk from the start, each launch with half of the wavefront slots; one DP round for all failures
-                        e2 = side_begin();
-                        reserve_side = true;
-                        if(e2 == hipSuccess) e2 = extend_range(a, ext_list, nullptr, n_mid, stats[2], ws.side[0], 1, mid_stride);
-                        if(e2 == hipSuccess) e2 = extend_range(a, ext_list + n_mid, nullptr, n_ent - n_mid, std::min(stats[2], kWpPathwSmall), ctx->stream, 0, 1);
-                        reserve_side = false;
-                        if(e2 == hipSuccess) e2 = side_join();
-                        return e2;
-                    }
-                    e2 = extend_range(a, ext_list + n_mid, nullptr, n_ent - n_mid, std::min(stats[2], kWpPathwSmall), ctx->stream, 0, 1);
-                    if(e2 != hipSuccess || n_mid == 0) return e2;
-                    // (escalating: the wide launch takes their overflows after them, before the DP call)
-                    if(p.no_dp || escalate) return extend_range(a, ext_list, nullptr, n_mid, stats[2], ctx->stream, 0, mid_stride);
-                    // with the DP fallback on they start on a side stream once the bulk is through and share the device with the DP
-                    // stage of the bulk's failed walks (own DP item list; half of the wavefront slots)
-                    long_launch = true;
-                    return e2;
-                }
-                Pool pools[2];
-                e2 = side_begin();
-                if(e2 != hipSuccess) return e2;
-                if(round == 0) {
-                    // the few walks across the longest gaps: one-kernel form on a side stream; the mid class: its own pool on the other
-                    e2 = extend_range(a, ext_list, nullptr, n_big, stats[2], ws.side[0], 1, 64);
-                    if(e2 == hipSuccess) e2 = pool_setup(pools[0], 0, ext_list + n_mid, n_ent - n_mid, std::max(1u, std::min(stats[2], kWpPathwSmall)), lane_budget, ctx->stream);
-                    if(e2 == hipSuccess) e2 = pool_setup(pools[1], 1, ext_list + n_big, n_mid - n_big, std::max(1u, std::min(stats[2], kWpPathwMid)), lane_budget / 4, ws.side[1]);
-                } else if(stats[2] > kWpPathwMid)
-                    e2 = extend_range(a, a.list, a.reqs, n_ent, stats[2], ctx->stream, 0, 64);
-                else {
-                    // later rounds: a handful of re-queued walks, one pool (entries that are DP requests or carry a bad geometry end at once)
-                    e2 = pool_setup(pools[0], 0, a.list, n_ent, std::max(1u, stats[2]), lane_budget, ctx->stream);
-                }
-                if(e2 == hipSuccess) e2 = pools_run(a, pools, 2);
-                if(e2 == hipSuccess) e2 = side_join();
+                // later rounds: the re-queued walks, spread thinner the fewer they are (64 / 16 / 1 lanes per walk)
+                if(round != 0) return extend_range(a, a.list, a.reqs, n_ent, std::max(stats[2], 1u), ctx->stream, false, n_ent <= 16384 ? 64u : n_ent <= 65536 ? 16u : 1u);
+                // round 0: the bulk, one walk per lane
+                e2 = extend_range(a, ext_list + n_mid, nullptr, n_ent - n_mid, std::min(stats[2], kWpPathwSmall), ctx->stream, false, 1);
+                if(e2 != hipSuccess || n_mid == 0) return e2;
+                // then the walks across long gaps (the first n_mid of the launch order), one walk per wavefront: a lane-per-walk wavefront
+                // advances at the pace of its slowest lane, and these are thousands of wide steps long.  With --nodp, or escalating (the
+                // wide launch takes their overflows before the DP call), they follow the bulk here; with the DP fallback on they start on
+                // the side stream below, beside the DP stage of the bulk's failed walks
+                if(p.no_dp || escalate) return extend_range(a, ext_list, nullptr, n_mid, stats[2], ctx->stream, false, 64);
+                long_launch = true;
                 return e2;
             });
             if(st != LRSC_OK) return st;
@@ -1981,8 +1827,6 @@ static int batch_correct_wp(lrsc_ctx* ctx, lrsc_batch* b, lrsc_read_result* res,
                 if(sw != LRSC_OK) return sw;
             }
             if(long_launch) {
-                long_launch = false;
-                n_long_cap = n_mid;
                 HIP_TRY(ws.d_items2.reserve(n_mid));
                 WpArgs xl = a;
                 xl.dp_items = ws.d_items2.p; xl.n_dp_items = ws.d_small.p + 12; xl.dp_items_cap = n_mid;
@@ -1991,10 +1835,12 @@ static int batch_correct_wp(lrsc_ctx* ctx, lrsc_batch* b, lrsc_read_result* res,
                 HIP_TRY(hipMemsetAsync(ws.d_ctr2.p, 0, kCtrShards * sizeof(DevCounters), ctx->stream));
                 xl.ctr = ws.d_ctr2.p;
                 if(a.prof) xl.prof = a.prof + 16;
-                HIP_TRY(side_begin());
+                // the side stream starts after what is on ctx->stream now
+                HIP_TRY(hipEventRecord(ws.ev_ready, ctx->stream));
+                HIP_TRY(hipStreamWaitEvent(ws.side, ws.ev_ready, 0));
                 if(!ws.ev_side_t0) HIP_TRY(hipEventCreate(&ws.ev_side_t0));
-                HIP_TRY(hipEventRecord(ws.ev_side_t0, ws.side[0]));
-                e = extend_range(xl, ext_list, nullptr, n_mid, stats[2], ws.side[0], 1, mid_stride);
+                HIP_TRY(hipEventRecord(ws.ev_side_t0, ws.side));
+                e = extend_range(xl, ext_list, nullptr, n_mid, stats[2], ws.side, true, 64);
                 if(e != hipSuccess) return hip_fail(e, "wp_extend (long walks)");
                 long_pending = true;
             }
@@ -2051,18 +1897,12 @@ static int batch_correct_wp(lrsc_ctx* ctx, lrsc_batch* b, lrsc_read_result* res,
             {
                 int sd = fetch_items(ws.d_items, a.n_dp_items, n_ent, items);
                 if(sd != LRSC_OK) return sd;
-                if(!long_pending) sd = dp_call(items);
-                else {
-                    // The long-gap walks are running on the side stream.  The bulk's failed walks go to the DP stage in two calls: the
-                    // first 60 % now; the rest together with the long walks' failures, which are in by then -- their few, long
-                    // alignments and pile-ups (latency-bound on their own) then overlap the second call's bulk instead of trailing it.
-                    const size_t cut = items.size() * dp_split_pct / 100;
-                    std::vector<WpDpItem> second(items.begin() + (ptrdiff_t)cut, items.end());
-                    items.resize(cut);
-                    sd = dp_call(items);
-                    if(sd != LRSC_OK) return sd;
+                sd = dp_call(items);
+                if(sd == LRSC_OK && long_pending) {
+                    // The long-gap walks ran on the side stream beside that DP call; their failures go to the DP stage in a call of
+                    // their own.
                     if(!ws.ev_side_t1) HIP_TRY(hipEventCreate(&ws.ev_side_t1));
-                    HIP_TRY(hipEventRecord(ws.ev_side_t1, ws.side[0]));
+                    HIP_TRY(hipEventRecord(ws.ev_side_t1, ws.side));
                     HIP_TRY(hipEventSynchronize(ws.ev_side_t1));
                     float ms = 0.f;
                     HIP_TRY(hipEventElapsedTime(&ms, ws.ev_side_t0, ws.ev_side_t1));
@@ -2076,13 +1916,10 @@ static int batch_correct_wp(lrsc_ctx* ctx, lrsc_batch* b, lrsc_read_result* res,
                             ctx->stats[LRSC_K_EXTEND].table_loads += dcn.table_loads;
                         }
                     }
-                    long_pending = false;
                     std::vector<WpDpItem> longs;
-                    sd = fetch_items(ws.d_items2, ws.d_small.p + 12, n_long_cap, longs);
+                    sd = fetch_items(ws.d_items2, ws.d_small.p + 12, n_mid, longs);
                     if(sd != LRSC_OK) return sd;
-                    second.insert(second.end(), longs.begin(), longs.end());
-                    std::sort(second.begin(), second.end(), [](const WpDpItem& x, const WpDpItem& y) { return x.slot < y.slot; });
-                    sd = dp_call(second);
+                    sd = dp_call(longs);
                 }
                 if(sd != LRSC_OK) return sd;
             }
@@ -2115,9 +1952,9 @@ static int batch_correct_wp(lrsc_ctx* ctx, lrsc_batch* b, lrsc_read_result* res,
                              hs[ord[qs[2]]].leaf_steps, hs[ord[qs[3]]].leaf_steps, hs[ord[qs[4]]].leaf_steps);
             }
             if(verbose)
-                std::fprintf(stderr, "[lrsc] wp reads [%u, %u) round %u: %u entries, %u DP requests (%llu strings), arenas q %.1f MB prep %.1f MB path %.1f MB, %llu schedule rounds so far, %llu walks escalated so far\n",
+                std::fprintf(stderr, "[lrsc] wp reads [%u, %u) round %u: %u entries, %u DP requests (%llu strings), arenas q %.1f MB prep %.1f MB path %.1f MB, %llu walks escalated so far\n",
                              r0, r1, round, n_ent, n_items, (unsigned long long)stage.n_strings, tot[0] / 1048576.0, tot[1] / 1048576.0, tot[2] / 1048576.0,
-                             (unsigned long long)sched_rounds, (unsigned long long)n_escalated);
+                             (unsigned long long)n_escalated);
             if(round > 100000) return fail(LRSC_ERR_LIMIT, "walk-parallel flow: too many rounds");
         }
         r0 = r1;
@@ -2126,7 +1963,7 @@ static int batch_correct_wp(lrsc_ctx* ctx, lrsc_batch* b, lrsc_read_result* res,
     if(a.prof) {
         unsigned long long prs[32];
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        for(int i = 0; i < 2; ++i) HIP_TRY(hipStreamSynchronize(ws.side[i]));
+        HIP_TRY(hipStreamSynchronize(ws.side));
         HIP_TRY(hipMemcpy(prs, ws.d_prof.p, sizeof(prs), hipMemcpyDeviceToHost));
         for(int part = 0; part < 2; ++part) {
             const unsigned long long* pr = prs + 16 * part;

@@ -68,31 +68,7 @@ __global__ __launch_bounds__(64, 2) void walk_extend_kernel(FmIndexDev fm, Exten
         const WalkWork ww = a.work[w];
         uint8_t* ws = a.workspace + ww.ws_off;
         Walk<WIDE> W;
-        W.sF = strand_consts<P>(fm.strand[LRSC_RBWT]);
-        W.sR = strand_consts<P>(fm.strand[LRSC_BWT]);
-        W.fm = &fm;
-        W.mtab = mtab;
-        W.q = a.codes + ww.codes_off;
-        W.Lq = ww.lq; W.initk = ww.initk; W.path_len = ww.path_len; W.trg_len = ww.trg_len; W.dis = ww.dis;
-        W.seedSize = a.seed_size; W.minOverlap = a.min_overlap; W.maxOverlap = ww.max_overlap; W.maxLeaves = a.max_leaves;
-        W.min_SA_threshold = ww.min_sa;
-        W.PBcoverage = a.pb_coverage; W.PacBioErrorRate = a.pacbio_error_rate; W.errorRate = 0.25; W.localK = 100;
-        W.freqsOfKmerSize = a.freqs_of_kmer_size;
-        // .cpp:55-58,78-79: double expressions truncated to size_t
-        if(ww.dis > 100) W.maxIndelSize = (uint64_t)(ww.dis * 0.2); else W.maxIndelSize = 20;
-        W.maxLength = (uint64_t)((1.2 * (ww.dis + 10)) + (double)(2 * (uint64_t)ww.initk));
-        W.minLength = (uint64_t)((0.8 * (ww.dis - 20)) + (double)(2 * (uint64_t)ww.initk));
-        W.it9f = reinterpret_cast<SortItem*>(ws + ww.o_item9f);
-        W.it9r = reinterpret_cast<SortItem*>(ws + ww.o_item9r);
-        W.next9f = reinterpret_cast<uint16_t*>(ws + ww.o_next9f);
-        W.next9r = reinterpret_cast<uint16_t*>(ws + ww.o_next9r);
-        W.head9f = reinterpret_cast<uint16_t*>(ws + ww.o_head9);
-        W.head9r = W.head9f + 256;
-        W.head5 = reinterpret_cast<uint16_t*>(ws + ww.o_head5);
-        W.next5 = reinterpret_cast<uint16_t*>(ws + ww.o_next5);
-        W.flags5 = ws + ww.o_flags5;
-        W.term = reinterpret_cast<const P*>(ws + ww.o_term);
-        W.n_term = ww.trg_len >= a.min_overlap ? ww.trg_len - a.min_overlap + 1 : 0;
+        walk_bind_work(W, fm, mtab, a, ww, ws);
         W.cur = reinterpret_cast<Leaf<P>*>(ws + ww.o_leaves);
         W.nxt = W.cur + 32;
         W.leaf_small = W.cur;

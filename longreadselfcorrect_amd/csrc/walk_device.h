@@ -791,6 +791,15 @@ struct Walk : WalkCap<BIG> {
     // but LRSC_WALK_NEEDS_WIDE from finish()
     bool escalate = false;
 
+    // The constructor's lengths of a walk across a gap of `dis` characters from a k-mer of initk characters (.cpp:55-58,78-79: double
+    // expressions truncated to size_t)
+    LRSC_WALK_FN __forceinline__ void set_lengths(int32_t dis, uint32_t initk)
+    {
+        if(dis > 100) maxIndelSize = (uint64_t)(dis * 0.2); else maxIndelSize = 20;
+        maxLength = (uint64_t)((1.2 * (dis + 10)) + (double)(2 * (uint64_t)initk));
+        minLength = (uint64_t)((0.8 * (dis - 20)) + (double)(2 * (uint64_t)initk));
+    }
+
     // The constructor's per-walk tables that stay fixed during the walk (.cpp:90-94,127-152 after the bulk look-ups of
     // prepare_offset): the interval "trees" as sorted k-mer chains, the 5-mer chains, the isTerminated filter.
     LRSC_WALK_FN LRSC_WALK_NOINLINE void begin_static()
@@ -1105,6 +1114,37 @@ struct Walk : WalkCap<BIG> {
         return -4;
     }
 };
+
+// A walk of lrsc_extend_walks (walk_extend_kernel, walk_extend_wide_kernel): the index, walk ww's query, parameters and lengths, and
+// the tables walk_prepare_kernel left in its workspace ws.  The leaf, ring, path and result regions are the kernel's to bind.
+template <bool WIDE, bool BIG>
+__device__ __forceinline__ void walk_bind_work(Walk<WIDE, BIG>& W, const FmIndexDev& fm, const uint32_t* mtab, const ExtendArgs& a,
+                                               const WalkWork& ww, uint8_t* ws)
+{
+    using P = typename Lay<WIDE>::pos_t;
+    W.sF = strand_consts<P>(fm.strand[LRSC_RBWT]);
+    W.sR = strand_consts<P>(fm.strand[LRSC_BWT]);
+    W.fm = &fm;
+    W.mtab = mtab;
+    W.q = a.codes + ww.codes_off;
+    W.Lq = ww.lq; W.initk = ww.initk; W.path_len = ww.path_len; W.trg_len = ww.trg_len; W.dis = ww.dis;
+    W.seedSize = a.seed_size; W.minOverlap = a.min_overlap; W.maxOverlap = ww.max_overlap; W.maxLeaves = a.max_leaves;
+    W.min_SA_threshold = ww.min_sa;
+    W.PBcoverage = a.pb_coverage; W.PacBioErrorRate = a.pacbio_error_rate; W.errorRate = 0.25; W.localK = 100;
+    W.freqsOfKmerSize = a.freqs_of_kmer_size;
+    W.set_lengths(ww.dis, ww.initk);
+    W.it9f = reinterpret_cast<SortItem*>(ws + ww.o_item9f);
+    W.it9r = reinterpret_cast<SortItem*>(ws + ww.o_item9r);
+    W.next9f = reinterpret_cast<uint16_t*>(ws + ww.o_next9f);
+    W.next9r = reinterpret_cast<uint16_t*>(ws + ww.o_next9r);
+    W.head9f = reinterpret_cast<uint16_t*>(ws + ww.o_head9);
+    W.head9r = W.head9f + 256;
+    W.head5 = reinterpret_cast<uint16_t*>(ws + ww.o_head5);
+    W.next5 = reinterpret_cast<uint16_t*>(ws + ww.o_next5);
+    W.flags5 = ws + ww.o_flags5;
+    W.term = reinterpret_cast<const P*>(ws + ww.o_term);
+    W.n_term = ww.trg_len >= a.min_overlap ? ww.trg_len - a.min_overlap + 1 : 0;
+}
 
 
 } // namespace lrsc

@@ -29,60 +29,17 @@ namespace lrsc {
 
 namespace {
 
-// ---- wavefront helpers (call them with the whole wavefront active) ----------------------------------------------------------
-__device__ __forceinline__ uint64_t lanes_below(uint32_t lane) { return (1ull << lane) - 1ull; }
-__device__ __forceinline__ uint32_t popc64(uint64_t m) { return (uint32_t)__builtin_popcountll(m); }
-__device__ __forceinline__ uint32_t first_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uint64_t first_u64(uint64_t v) { return (uint64_t)first_u32((uint32_t)v) | ((uint64_t)first_u32((uint32_t)(v >> 32)) << 32); }
-__device__ __forceinline__ double first_f64(double v) { return __longlong_as_double((long long)first_u64((uint64_t)__double_as_longlong(v))); }
-// the value of lane l (l wave-uniform)
-__device__ __forceinline__ uint32_t lane_u32(uint32_t v, uint32_t l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l); }
-__device__ __forceinline__ double lane_f64(double v, uint32_t l)
-{
-    const uint64_t b = (uint64_t)__double_as_longlong(v);
-    return __longlong_as_double((long long)((uint64_t)lane_u32((uint32_t)b, l) | ((uint64_t)lane_u32((uint32_t)(b >> 32), l) << 32)));
-}
+// ---- wavefront helpers of this kernel (the shared ones are in wp_walk.h; call them with the whole wavefront active) -------------
 __device__ __forceinline__ uint32_t wave_or(uint32_t v)
 {
     for(int o = 32; o > 0; o >>= 1) v |= (uint32_t)__shfl_xor((int)v, o, 64);
     return first_u32(v);
-}
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-    for(int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
-    return first_u32(v);
-}
-__device__ __forceinline__ int wave_max(int v)
-{
-    for(int o = 32; o > 0; o >>= 1) { const int w = __shfl_xor(v, o, 64); v = w > v ? w : v; }
-    return (int)first_u32((uint32_t)v);
-}
-// minimum of values that are not NaN (exact in any order)
-__device__ __forceinline__ double wave_min(double v)
-{
-    for(int o = 32; o > 0; o >>= 1) { const double w = __shfl_xor(v, o, 64); v = w < v ? w : v; }
-    return first_f64(v);
-}
-// what a lane stored before is visible to every lane of the wavefront after it
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 // the k-th lowest set bit of m (k = 0: the lowest): the slot that k rounds of `ctz, clear` leave at the front
 __device__ __forceinline__ uint32_t kth_bit(uint32_t m, uint32_t k)
 {
     for(uint32_t j = 0; j < k; ++j) m &= m - 1u;
     return m ? (uint32_t)__builtin_ctz(m) : 0u;          // (survivors <= maxLeaves <= 32 slots: never empty)
-}
-
-// ---- refineSAInterval (.cpp:355-369): leaf j on lane j & 63 ---------------------------------------------------------------
-template <bool WIDE>
-__device__ __forceinline__ void wave_refine(Walk<WIDE>& W, Leaf<typename Lay<WIDE>::pos_t>* leaves, uint32_t n, uint64_t newKmerSize, uint32_t lane)
-{
-    for(uint32_t j = lane; j < n; j += 64) W.find_suffix(leaves[j], (uint32_t)newKmerSize);
-    W.currentKmerSize = newKmerSize;
 }
 
 // ---- SelectFreqsOfrange (.cpp:281-331): leaf j on lane j & 63, a wavefront maximum per k-mer size -------------------------
@@ -248,51 +205,6 @@ __device__ __forceinline__ void wave_prune(Walk<WIDE>& W, uint32_t lane, Leaf<ty
     W.has_child = wave_or(hc);
 }
 
-// a further child's copies of its parent's ring and path, by the whole wavefront, with this step's own entries already in place
-// (the serial commit copies everything but the own ring entry, then writes that entry and sets the new path character)
-template <bool WIDE>
-__device__ __forceinline__ void wave_copy_slots(Walk<WIDE>& W, uint64_t further, const Leaf<typename Lay<WIDE>::pos_t>& ch, uint32_t new_ring,
-                                                uint32_t new_path, uint32_t lane)
-{
-    while(further) {
-        const uint32_t l = (uint32_t)__builtin_ctzll(further);
-        further &= further - 1ull;
-        const uint32_t sr = lane_u32(ch.ring, l), dr = lane_u32(new_ring, l), sp = lane_u32(ch.path, l), dp = lane_u32(new_path, l);
-        const uint32_t own = (lane_u32(ch.hist_size, l) - 1u) % 100u, plen = lane_u32(ch.path_len, l), ex = lane_u32(ch.ext, l);
-        const double ge = lane_f64(ch.globalErr, l);
-        const double* src = W.rings + (uint64_t)sr * 100;
-        double* dst = W.rings + (uint64_t)dr * 100;
-        for(uint32_t k = lane; k < 100; k += 64) dst[k] = k == own ? ge : src[k];
-        const uint32_t* ps = W.paths + (uint64_t)sp * W.pathw;
-        uint32_t* pd = W.paths + (uint64_t)dp * W.pathw;
-        const uint32_t nw = (plen + 16) >> 4, wi = plen >> 4, sh = 2 * (plen & 15u);
-        for(uint32_t k = lane; k < nw; k += 64) {
-            uint32_t v = ps[k];
-            if(k == wi) v = (v & ~(3u << sh)) | (ex << sh);
-            pd[k] = v;
-        }
-    }
-}
-
-// results.at(first - 1) of every leaf of `hits` (lanes in leaf order: a later leaf with the same result slot overwrites, as in the
-// serial loop): the record by lane 0, the path by the whole wavefront
-template <bool WIDE>
-__device__ __forceinline__ void wave_store_results(Walk<WIDE>& W, uint64_t hits, const Leaf<typename Lay<WIDE>::pos_t>& lf, int hit, uint32_t lane)
-{
-    while(hits) {
-        const uint32_t l = (uint32_t)__builtin_ctzll(hits);
-        hits &= hits - 1ull;
-        const uint32_t slot = lane_u32((uint32_t)lf.res_first, l) - 1u, path = lane_u32(lf.path, l), plen = lane_u32(lf.path_len, l);
-        const uint32_t mi = lane_u32((uint32_t)hit, l);
-        const double ge = lane_f64(lf.globalErr, l);
-        if(lane == 0) { WalkResultRec& r = W.results[slot]; r.error_rate = ge; r.match_i = mi; r.path_len = plen; }
-        const uint32_t* src = W.paths + (uint64_t)path * W.pathw;
-        uint32_t* dst = W.rpaths + (uint64_t)slot * W.pathw;
-        const uint32_t nw = (plen + 15) >> 4;
-        for(uint32_t k = lane; k < nw; k += 64) dst[k] = src[k];
-    }
-}
-
 // ---- the commit of step_body (walk_device.h) and isTerminated (.cpp:825-878) ------------------------------------------------
 template <bool WIDE>
 __device__ __forceinline__ void wave_commit(Walk<WIDE>& W, uint32_t lane, Leaf<typename Lay<WIDE>::pos_t>& c0, Leaf<typename Lay<WIDE>::pos_t>& c1)
@@ -427,12 +339,7 @@ __global__ __launch_bounds__(64, LRSC_WP_EXTEND_OCC) void wp_extend_wave_kernel(
     const uint32_t lane = threadIdx.x;
     const uint32_t wave = blockIdx.x;
     Walk<WIDE> W;
-    W.sF = strand_consts<P>(fm.strand[LRSC_RBWT]);
-    W.sR = strand_consts<P>(fm.strand[LRSC_BWT]);
-    W.fm = &fm; W.mtab = mtab;
-    W.seedSize = a.seed_size; W.minOverlap = a.min_overlap; W.maxLeaves = a.max_leaves; W.escalate = a.escalate != 0;
-    W.PBcoverage = a.pb_coverage; W.PacBioErrorRate = a.pacbio_error_rate; W.errorRate = 0.25; W.localK = 100;
-    W.freqsOfKmerSize = a.freqs_of_kmer_size;
+    wp_walk_consts(W, fm, a, mtab);
     const WpLaneLayout LL = wp_lane_layout(a.lbytes, a.lane_pathw);
     uint8_t* lws = a.lane_ws + (uint64_t)(wave < a.n_lanes ? wave : 0u) * a.lane_ws_bytes;
     Leaf<P>* const leaf_base = reinterpret_cast<Leaf<P>*>(lws + LL.leaves);
@@ -441,8 +348,6 @@ __global__ __launch_bounds__(64, LRSC_WP_EXTEND_OCC) void wp_extend_wave_kernel(
     W.paths = reinterpret_cast<uint32_t*>(lws + LL.paths);
     W.pathw = a.lane_pathw;
     W.rpaths = W.paths + (uint64_t)32 * a.lane_pathw;
-    W.n_rank = 0; W.n_blk = 0; W.steps = 0; W.leaf_steps = 0; W.error = 0; W.cyc_setup = 0; W.cyc_loop = 0; W.prof = nullptr; W.profile = false;
-    const uint64_t min_SA = a.pb_coverage > 60 ? (uint64_t)((a.pb_coverage / 60) * 3) : 3;
 
     Leaf<P> L;                                            // lane 0: the single-leaf fast path's leaf in registers
     uint32_t pw = 0;
@@ -462,61 +367,20 @@ __global__ __launch_bounds__(64, LRSC_WP_EXTEND_OCC) void wp_extend_wave_kernel(
         if(i >= a.n_list) break;
         if(a.reqs && a.reqs[i].kind != kWpReqFm) continue;
         const uint32_t si = a.list ? a.list[i] : (uint32_t)a.slot_base + i;
-        {
-            const WpSlot& s = a.slots[si];
-            if(s.flags & kWpGeomBad) continue;
-            wp_bind_static<WIDE>(W, a, s);
-            const WpStatic* H = reinterpret_cast<const WpStatic*>(s.prep);
-            W.n9f = H->n9f; W.n9r = H->n9r; W.tmask0 = H->tmask0; W.tmask1 = H->tmask1;
-            W.maxOverlap = (uint32_t)s.k + 2;
-            W.min_SA_threshold = min_SA;
-            // .cpp:55-58,78-79: double expressions truncated to size_t
-            if((int32_t)s.gap > 100) W.maxIndelSize = (uint64_t)((int32_t)s.gap * 0.2); else W.maxIndelSize = 20;
-            W.maxLength = (uint64_t)((1.2 * ((int32_t)s.gap + 10)) + (double)(2 * (uint64_t)s.k));
-            W.minLength = (uint64_t)((0.8 * ((int32_t)s.gap - 20)) + (double)(2 * (uint64_t)s.k));
-            W.cur = leaf_base; W.nxt = leaf_base + 32; W.leaf_small = leaf_base;
-            W.error = 0;
-            W.leaf_steps = 0; W.max_front = 1;
-            const P riv[4] = {(P)H->root[0], (P)H->root[1], (P)H->root[2], (P)H->root[3]};
-            W.begin_root(riv);                            // every lane: the same values into the same words
-        }
+        if(a.slots[si].flags & kWpGeomBad) continue;
+        W.cur = leaf_base; W.nxt = leaf_base + 32; W.leaf_small = leaf_base;
+        wp_walk_bind(W, a, a.slots[si]);                  // every lane: the same values into the same words
         const uint64_t steps0 = W.steps;
         if(prof) t_refill += __builtin_readcyclecounter() - tr0;
         while(true) {
             int r = 2;
-            if(W.can_fast()) {
-                wave_sync();
-                const uint64_t tq = prof ? __builtin_readcyclecounter() : 0;
-                if(lane == 0) {
-                    W.enter_fast(L, pw);
-                    do { r = W.step_fast(L, pw); if(prof && r == 1) ++n_fast; } while(r == 1);
-                }
-                if(prof) pr[7] += __builtin_readcyclecounter() - tq;
-                // what a fast step changes, from lane 0 (rank-query counters stay per lane)
-                r = (int)first_u32((uint32_t)r);
-                W.currentLength = first_u64(W.currentLength); W.currentKmerSize = first_u64(W.currentKmerSize);
-                W.steps = first_u64(W.steps); W.leaf_steps = first_u32(W.leaf_steps);
-                W.n_cur = first_u32(W.n_cur); W.n_results = first_u32(W.n_results); W.error = (int)first_u32((uint32_t)W.error);
-            }
+            if(W.can_fast()) r = wave_fast_steps(W, L, pw, lane, prof, pr[7], n_fast);
             if(r == 2) r = wave_step(W, lane) ? 1 : 0;
             if(r == 0) break;
         }
         const uint64_t tf0 = prof ? __builtin_readcyclecounter() : 0;
         wave_sync();
-        if(lane == 0) {
-            WpSlot& s = a.slots[si];
-            uint32_t plen = 0, mi = 0;
-            const int code = W.finish(&plen, s.path, &mi);
-            s.code = code; s.path_len = plen; s.match_i = mi; s.steps = (uint32_t)(W.steps - steps0); s.leaf_steps = W.leaf_steps; s.max_front = (uint8_t)W.max_front;
-            s.flags |= (uint8_t)kWpFmValid;
-            if(code <= 0 && code > LRSC_WALK_ERR_CHILDREN && a.auto_dp && s.next == 0) {
-                const uint32_t j = atomicAdd(a.n_dp_items, 1u);
-                if(j < a.dp_items_cap) {
-                    WpDpItem d; d.q = (uint64_t)s.dpq; d.slot = si; d.lq = s.dp_lq; d.k = s.dp_k; d.total_freq = s.dp_total_freq;
-                    a.dp_items[j] = d;
-                }
-            }
-        }
+        if(lane == 0) wp_walk_finish(W, a, si, steps0);
         if(prof) t_finish += __builtin_readcyclecounter() - tf0;
     }
     if(prof && wave < a.n_lanes && lane == 0) {

@@ -30,40 +30,7 @@ namespace {
 
 constexpr uint32_t kBitsLeaf = kWideMaxLeaves / 64, kBitsChild = 4 * kWideMaxLeaves / 64;
 
-// ---- wavefront helpers (call them with the whole wavefront active) ----------------------------------------------------------
-__device__ __forceinline__ uint64_t lanes_below(uint32_t lane) { return (1ull << lane) - 1ull; }
-__device__ __forceinline__ uint32_t popc64(uint64_t m) { return (uint32_t)__builtin_popcountll(m); }
-__device__ __forceinline__ uint32_t first_u32(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-__device__ __forceinline__ uint64_t first_u64(uint64_t v) { return (uint64_t)first_u32((uint32_t)v) | ((uint64_t)first_u32((uint32_t)(v >> 32)) << 32); }
-__device__ __forceinline__ double first_f64(double v) { return __longlong_as_double((long long)first_u64((uint64_t)__double_as_longlong(v))); }
-__device__ __forceinline__ uint32_t lane_u32(uint32_t v, uint32_t l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, (int)l); }
-__device__ __forceinline__ double lane_f64(double v, uint32_t l)
-{
-    const uint64_t b = (uint64_t)__double_as_longlong(v);
-    return __longlong_as_double((long long)((uint64_t)lane_u32((uint32_t)b, l) | ((uint64_t)lane_u32((uint32_t)(b >> 32), l) << 32)));
-}
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v)
-{
-    for(int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
-    return first_u32(v);
-}
-__device__ __forceinline__ int wave_max(int v)
-{
-    for(int o = 32; o > 0; o >>= 1) { const int w = __shfl_xor(v, o, 64); v = w > v ? w : v; }
-    return (int)first_u32((uint32_t)v);
-}
-// minimum of values that are not NaN (exact in any order)
-__device__ __forceinline__ double wave_min(double v)
-{
-    for(int o = 32; o > 0; o >>= 1) { const double w = __shfl_xor(v, o, 64); v = w < v ? w : v; }
-    return first_f64(v);
-}
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
+// ---- bitsets of this kernel (the wavefront helpers are in wp_walk.h) -----------------------------------------------------------
 // the k-th lowest set bit of the bitset (k = 0: the lowest), n bits; wave-uniform words
 __device__ __forceinline__ uint32_t bits_kth(const uint64_t* b, uint32_t n, uint32_t k)
 {
@@ -90,14 +57,6 @@ __device__ __forceinline__ void bits_take(uint64_t* b, uint32_t n, uint32_t k)
 
 template <bool WIDE> using WWalk = Walk<WIDE, true>;
 template <bool WIDE> using WLeaf = Leaf<typename Lay<WIDE>::pos_t>;
-
-// ---- refineSAInterval (.cpp:355-369): leaf j on lane j & 63 ---------------------------------------------------------------
-template <bool WIDE>
-__device__ __forceinline__ void wide_refine(WWalk<WIDE>& W, WLeaf<WIDE>* leaves, uint32_t n, uint64_t newKmerSize, uint32_t lane)
-{
-    for(uint32_t j = lane; j < n; j += 64) W.find_suffix(leaves[j], (uint32_t)newKmerSize);
-    W.currentKmerSize = newKmerSize;
-}
 
 // ---- SelectFreqsOfrange (.cpp:281-331): leaf j on lane j & 63 (its intervals in the leaf's tf* fields), a wavefront maximum per size
 template <bool WIDE>
@@ -218,12 +177,12 @@ template <bool WIDE>
 __device__ __forceinline__ void wide_extend(WWalk<WIDE>& W, uint32_t lane)
 {
     W.n_nxt = 0;
-    if(W.currentKmerSize > W.maxOverlap) { wide_refine(W, W.cur, W.n_cur, W.maxOverlap, lane); wave_sync(); }
+    if(W.currentKmerSize > W.maxOverlap) { wave_refine(W, W.cur, W.n_cur, W.maxOverlap, lane); wave_sync(); }
     wide_attempt(W, lane);
     if(W.n_nxt == 0) {                                    // level 1: reduce the k-mer size
         const uint64_t LowerBound = (W.currentKmerSize - 2) > W.minOverlap ? (W.currentKmerSize - 2) : W.minOverlap;
         const uint64_t ReduceSize = wide_select(W, LowerBound, W.currentKmerSize, W.cur, W.n_cur, lane);
-        wide_refine(W, W.cur, W.n_cur, ReduceSize, lane);
+        wave_refine(W, W.cur, W.n_cur, ReduceSize, lane);
         wave_sync();
         wide_attempt(W, lane);
         if(W.n_nxt == 0) {                                // level 2: reduce the threshold
@@ -238,7 +197,7 @@ __device__ __forceinline__ void wide_extend(WWalk<WIDE>& W, uint32_t lane)
         if(W.isInsufficientFreqs(W.n_highfreq, W.n_nxt)) {   // frequencies are low: relax the k-mer size
             const uint64_t LowerBound = (W.currentKmerSize - 2) > W.minOverlap ? (W.currentKmerSize - 2) : W.minOverlap;
             const uint64_t ReduceSize = wide_select(W, LowerBound, W.currentKmerSize, W.nxt, W.n_nxt, lane);
-            wide_refine(W, W.nxt, W.n_nxt, ReduceSize, lane);
+            wave_refine(W, W.nxt, W.n_nxt, ReduceSize, lane);
         }
     }
     wave_sync();
@@ -271,49 +230,6 @@ __device__ __forceinline__ void wide_prune(WWalk<WIDE>& W, uint32_t lane)
         if(lane == 0) W.alive_bits[r0 >> 6] = m;
     }
     wave_sync();
-}
-
-// a further child's copies of its parent's ring and path, by the whole wavefront, with this step's own entries already in place
-template <bool WIDE>
-__device__ __forceinline__ void wide_copy_slots(WWalk<WIDE>& W, uint64_t further, const WLeaf<WIDE>& ch, uint32_t new_ring, uint32_t new_path, uint32_t lane)
-{
-    while(further) {
-        const uint32_t l = (uint32_t)__builtin_ctzll(further);
-        further &= further - 1ull;
-        const uint32_t sr = lane_u32(ch.ring, l), dr = lane_u32(new_ring, l), sp = lane_u32(ch.path, l), dp = lane_u32(new_path, l);
-        const uint32_t own = (lane_u32(ch.hist_size, l) - 1u) % 100u, plen = lane_u32(ch.path_len, l), ex = lane_u32(ch.ext, l);
-        const double ge = lane_f64(ch.globalErr, l);
-        const double* src = W.rings + (uint64_t)sr * 100;
-        double* dst = W.rings + (uint64_t)dr * 100;
-        for(uint32_t k = lane; k < 100; k += 64) dst[k] = k == own ? ge : src[k];
-        const uint32_t* ps = W.paths + (uint64_t)sp * W.pathw;
-        uint32_t* pd = W.paths + (uint64_t)dp * W.pathw;
-        const uint32_t nw = (plen + 16) >> 4, wi = plen >> 4, sh = 2 * (plen & 15u);
-        for(uint32_t k = lane; k < nw; k += 64) {
-            uint32_t v = ps[k];
-            if(k == wi) v = (v & ~(3u << sh)) | (ex << sh);
-            pd[k] = v;
-        }
-    }
-}
-
-// results.at(first - 1) of every leaf of `hits` (lanes in leaf order: a later leaf with the same result slot overwrites, as in the
-// serial loop): the record by lane 0, the path by the whole wavefront
-template <bool WIDE>
-__device__ __forceinline__ void wide_store_results(WWalk<WIDE>& W, uint64_t hits, const WLeaf<WIDE>& lf, int hit, uint32_t lane)
-{
-    while(hits) {
-        const uint32_t l = (uint32_t)__builtin_ctzll(hits);
-        hits &= hits - 1ull;
-        const uint32_t slot = lane_u32((uint32_t)lf.res_first, l) - 1u, path = lane_u32(lf.path, l), plen = lane_u32(lf.path_len, l);
-        const uint32_t mi = lane_u32((uint32_t)hit, l);
-        const double ge = lane_f64(lf.globalErr, l);
-        if(lane == 0) { WalkResultRec& r = W.results[slot]; r.error_rate = ge; r.match_i = mi; r.path_len = plen; }
-        const uint32_t* src = W.paths + (uint64_t)path * W.pathw;
-        uint32_t* dst = W.rpaths + (uint64_t)slot * W.pathw;
-        const uint32_t nw = (plen + 15) >> 4;
-        for(uint32_t k = lane; k < nw; k += 64) dst[k] = src[k];
-    }
 }
 
 // ---- the commit of step_body (walk_device.h) and isTerminated (.cpp:825-878) ------------------------------------------------
@@ -376,7 +292,7 @@ __device__ __forceinline__ void wide_commit(WWalk<WIDE>& W, uint32_t lane)
             pp = bits_kth(W.path_bits, W.cap, k);
         }
         n_further += popc64(fm);
-        wide_copy_slots(W, fm, ch, rr, pp, lane);
+        wave_copy_slots(W, fm, ch, rr, pp, lane);
         if(a && !fur) {
             W.rings[(uint64_t)ch.ring * 100 + (ch.hist_size - 1) % 100] = ch.globalErr;
             path_set(W.paths + (uint64_t)ch.path * W.pathw, ch.path_len, ch.ext);
@@ -409,7 +325,7 @@ __device__ __forceinline__ void wide_commit(WWalk<WIDE>& W, uint32_t lane)
             W.n_results += popc64(nm);
             if(W.error) break;
             const uint64_t hm = __ballot(hit >= 0);
-            if(hm) { wide_store_results(W, hm, lf, hit, lane); }
+            if(hm) { wave_store_results(W, hm, lf, hit, lane); }
         }
         wave_sync();
     }
@@ -437,20 +353,10 @@ __device__ __forceinline__ void wide_run(WWalk<WIDE>& W, uint32_t lane)
     using P = typename Lay<WIDE>::pos_t;
     Leaf<P> L;
     uint32_t pw = 0;
+    uint64_t no_ticks = 0, no_steps = 0;                  // (no profile counters)
     while(true) {
         int r = 2;
-        if(W.can_fast()) {
-            wave_sync();
-            if(lane == 0) {
-                W.enter_fast(L, pw);
-                do { r = W.step_fast(L, pw); } while(r == 1);
-            }
-            // what a fast step changes, from lane 0 (rank-query counters stay per lane)
-            r = (int)first_u32((uint32_t)r);
-            W.currentLength = first_u64(W.currentLength); W.currentKmerSize = first_u64(W.currentKmerSize);
-            W.steps = first_u64(W.steps); W.leaf_steps = first_u32(W.leaf_steps);
-            W.n_cur = first_u32(W.n_cur); W.n_results = first_u32(W.n_results); W.error = (int)first_u32((uint32_t)W.error);
-        }
+        if(W.can_fast()) r = wave_fast_steps(W, L, pw, lane, false, no_ticks, no_steps);
         if(r == 2) r = wide_step(W, lane) ? 1 : 0;
         if(r == 0) break;
     }
@@ -483,22 +389,14 @@ __device__ __forceinline__ void wide_bind_ws(WWalk<WIDE>& W, uint8_t* lws, uint3
 template <bool WIDE>
 __global__ __launch_bounds__(64, LRSC_WP_WIDE_OCC) void wp_extend_wide_kernel(FmIndexDev fm, WpArgs a)
 {
-    using P = typename Lay<WIDE>::pos_t;
     __shared__ __attribute__((aligned(16))) uint32_t mtab[MaskTabSize<WIDE>::value];
     __shared__ uint64_t bits[4 * kBitsLeaf + kBitsChild];
     init_mask_table<WIDE>(mtab);
     const uint32_t lane = threadIdx.x;
     const uint32_t wave = blockIdx.x;
     WWalk<WIDE> W;
-    W.sF = strand_consts<P>(fm.strand[LRSC_RBWT]);
-    W.sR = strand_consts<P>(fm.strand[LRSC_BWT]);
-    W.fm = &fm; W.mtab = mtab;
-    W.seedSize = a.seed_size; W.minOverlap = a.min_overlap; W.maxLeaves = a.max_leaves;
-    W.PBcoverage = a.pb_coverage; W.PacBioErrorRate = a.pacbio_error_rate; W.errorRate = 0.25; W.localK = 100;
-    W.freqsOfKmerSize = a.freqs_of_kmer_size;
+    wp_walk_consts(W, fm, a, mtab);
     wide_bind_ws<WIDE>(W, a.lane_ws + (uint64_t)(wave < a.n_lanes ? wave : 0u) * a.lane_ws_bytes, a.max_leaves, a.lbytes, a.lane_pathw, bits);
-    W.n_rank = 0; W.n_blk = 0; W.steps = 0; W.leaf_steps = 0; W.error = 0; W.cyc_setup = 0; W.cyc_loop = 0; W.prof = nullptr; W.profile = false;
-    const uint64_t min_SA = a.pb_coverage > 60 ? (uint64_t)((a.pb_coverage / 60) * 3) : 3;
     if(wave < a.n_lanes)
     while(true) {
         uint32_t i = 0;
@@ -506,41 +404,11 @@ __global__ __launch_bounds__(64, LRSC_WP_WIDE_OCC) void wp_extend_wide_kernel(Fm
         i = first_u32(i);
         if(i >= a.n_list) break;
         const uint32_t si = a.list[i];
-        {
-            const WpSlot& s = a.slots[si];
-            wp_bind_static<WIDE>(W, a, s);
-            const WpStatic* H = reinterpret_cast<const WpStatic*>(s.prep);
-            W.n9f = H->n9f; W.n9r = H->n9r; W.tmask0 = H->tmask0; W.tmask1 = H->tmask1;
-            W.maxOverlap = (uint32_t)s.k + 2;
-            W.min_SA_threshold = min_SA;
-            // .cpp:55-58,78-79: double expressions truncated to size_t
-            if((int32_t)s.gap > 100) W.maxIndelSize = (uint64_t)((int32_t)s.gap * 0.2); else W.maxIndelSize = 20;
-            W.maxLength = (uint64_t)((1.2 * ((int32_t)s.gap + 10)) + (double)(2 * (uint64_t)s.k));
-            W.minLength = (uint64_t)((0.8 * ((int32_t)s.gap - 20)) + (double)(2 * (uint64_t)s.k));
-            W.cur = W.leaf_small; W.nxt = W.leaf_small + W.cap;
-            W.error = 0;
-            W.leaf_steps = 0; W.max_front = 1;
-            const P riv[4] = {(P)H->root[0], (P)H->root[1], (P)H->root[2], (P)H->root[3]};
-            wave_sync();
-            W.begin_root(riv);                            // every lane: the same values into the same words
-        }
+        W.cur = W.leaf_small; W.nxt = W.leaf_small + W.cap;
+        wp_walk_bind(W, a, a.slots[si], true);            // every lane: the same values into the same words
         const uint64_t steps0 = W.steps;
         wide_run(W, lane);
-        if(lane == 0) {
-            WpSlot& s = a.slots[si];
-            uint32_t plen = 0, mi = 0;
-            const int code = W.finish(&plen, s.path, &mi);
-            s.code = code; s.path_len = plen; s.match_i = mi; s.steps = (uint32_t)(W.steps - steps0); s.leaf_steps = W.leaf_steps;
-            s.max_front = (uint8_t)(W.max_front < 255u ? W.max_front : 255u);
-            s.flags |= (uint8_t)kWpFmValid;
-            if(code <= 0 && code > LRSC_WALK_ERR_CHILDREN && a.auto_dp && s.next == 0) {
-                const uint32_t j = atomicAdd(a.n_dp_items, 1u);
-                if(j < a.dp_items_cap) {
-                    WpDpItem d; d.q = (uint64_t)s.dpq; d.slot = si; d.lq = s.dp_lq; d.k = s.dp_k; d.total_freq = s.dp_total_freq;
-                    a.dp_items[j] = d;
-                }
-            }
-        }
+        if(lane == 0) wp_walk_finish(W, a, si, steps0);
     }
     flush_counters(a.ctr, W.n_rank, W.n_blk);
 }
@@ -562,29 +430,7 @@ __global__ __launch_bounds__(64, LRSC_WP_WIDE_OCC) void walk_extend_wide_kernel(
         const WalkWork ww = a.work[w];
         uint8_t* ws = a.workspace + ww.ws_off;
         WWalk<WIDE> W;
-        W.sF = strand_consts<P>(fm.strand[LRSC_RBWT]);
-        W.sR = strand_consts<P>(fm.strand[LRSC_BWT]);
-        W.fm = &fm; W.mtab = mtab;
-        W.q = a.codes + ww.codes_off;
-        W.Lq = ww.lq; W.initk = ww.initk; W.path_len = ww.path_len; W.trg_len = ww.trg_len; W.dis = ww.dis;
-        W.seedSize = a.seed_size; W.minOverlap = a.min_overlap; W.maxOverlap = ww.max_overlap; W.maxLeaves = a.max_leaves;
-        W.min_SA_threshold = ww.min_sa;
-        W.PBcoverage = a.pb_coverage; W.PacBioErrorRate = a.pacbio_error_rate; W.errorRate = 0.25; W.localK = 100;
-        W.freqsOfKmerSize = a.freqs_of_kmer_size;
-        if(ww.dis > 100) W.maxIndelSize = (uint64_t)(ww.dis * 0.2); else W.maxIndelSize = 20;
-        W.maxLength = (uint64_t)((1.2 * (ww.dis + 10)) + (double)(2 * (uint64_t)ww.initk));
-        W.minLength = (uint64_t)((0.8 * (ww.dis - 20)) + (double)(2 * (uint64_t)ww.initk));
-        W.it9f = reinterpret_cast<SortItem*>(ws + ww.o_item9f);
-        W.it9r = reinterpret_cast<SortItem*>(ws + ww.o_item9r);
-        W.next9f = reinterpret_cast<uint16_t*>(ws + ww.o_next9f);
-        W.next9r = reinterpret_cast<uint16_t*>(ws + ww.o_next9r);
-        W.head9f = reinterpret_cast<uint16_t*>(ws + ww.o_head9);
-        W.head9r = W.head9f + 256;
-        W.head5 = reinterpret_cast<uint16_t*>(ws + ww.o_head5);
-        W.next5 = reinterpret_cast<uint16_t*>(ws + ww.o_next5);
-        W.flags5 = ws + ww.o_flags5;
-        W.term = reinterpret_cast<const P*>(ws + ww.o_term);
-        W.n_term = ww.trg_len >= a.min_overlap ? ww.trg_len - a.min_overlap + 1 : 0;
+        walk_bind_work(W, fm, mtab, a, ww, ws);
         wide_bind_ws<WIDE>(W, ws + ww.o_leaves, a.max_leaves, (uint32_t)sizeof(Leaf<P>), ww.pathw, bits);
         W.n_rank = 0; W.n_blk = 0; W.steps = 0; W.leaf_steps = 0; W.max_front = 1; W.error = 0; W.cyc_setup = 0; W.cyc_loop = 0;
         W.prof = nullptr; W.profile = false;

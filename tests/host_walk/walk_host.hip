@@ -138,9 +138,7 @@ static int run_walk(HostIndex* ix, const HwParams& p, const uint8_t* codes, uint
     W.min_SA_threshold = min_sa;
     W.PBcoverage = (uint64_t)p.pb_coverage; W.PacBioErrorRate = p.error_rate; W.errorRate = 0.25; W.localK = 100;
     W.freqsOfKmerSize = freqs;
-    if(dis > 100) W.maxIndelSize = (uint64_t)(dis * 0.2); else W.maxIndelSize = 20;
-    W.maxLength = (uint64_t)((1.2 * (dis + 10)) + (double)(2 * (uint64_t)initk));
-    W.minLength = (uint64_t)((0.8 * (dis - 20)) + (double)(2 * (uint64_t)initk));
+    W.set_lengths(dis, initk);
     W.it9f = it9f.data(); W.it9r = it9r.data();
     W.next9f = next9f.data(); W.next9r = next9r.data();
     W.head9f = head9.data(); W.head9r = head9.data() + 256;
