@@ -1206,6 +1206,48 @@ static uint32_t dp_wave_count(const lrsc_ctx* ctx)
     return (uint32_t)cus * 8u;
 }
 
+// The launches of one set of alignments: one per non-empty staging-size class (dp_dev.h), each with the LDS, the traceback stride and
+// the wavefront count of its own largest alignment, then the global-workspace variant for what is beyond the LDS stage.
+struct DpAlignClasses {
+    struct Class { uint32_t max_s1 = 0, stage_max = 0; uint64_t jobs = 0; } cls[kDpAlignClasses + 1];
+    void add(uint32_t s1_len, uint32_t stage_bytes, uint64_t n_jobs)
+    {
+        Class& c = cls[dp_align_class(stage_bytes)];
+        c.max_s1 = std::max(c.max_s1, s1_len); c.stage_max = std::max(c.stage_max, stage_bytes); c.jobs += n_jobs;
+    }
+    // `al`: everything but the per-launch fields; lds_waves: wavefronts of an LDS launch (the traceback scratch is capped at 4 GB)
+    int launch(lrsc_ctx* ctx, DpAlignArgs al, uint32_t lds_waves, DevBuf<uint8_t>& d_trace, DevBuf<uint8_t>& d_seq_ws) const
+    {
+        uint32_t nw[kDpAlignClasses + 1] = {};
+        uint64_t stride[kDpAlignClasses + 1] = {}, trace_bytes = 0, ws_bytes = 0;
+        for(uint32_t k = 0; k <= kDpAlignClasses; ++k) {
+            const Class& c = cls[k];
+            if(!c.jobs) continue;
+            stride[k] = (uint64_t)(c.max_s1 + 17) * kDpTraceStride;
+            const uint64_t want = k < kDpAlignClasses ? lds_waves : 1024;
+            nw[k] = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(want, c.jobs), (4ull << 30) / stride[k]));
+            trace_bytes = std::max(trace_bytes, stride[k] * nw[k]);
+            if(k == kDpAlignClasses) ws_bytes = (((uint64_t)c.stage_max + 255) & ~255ull) * nw[k];
+        }
+        HIP_TRY(d_trace.reserve(std::max<uint64_t>(trace_bytes, 64)));
+        if(ws_bytes) HIP_TRY(d_seq_ws.reserve(ws_bytes));
+        al.trace = d_trace.p;
+        for(uint32_t k = 0; k <= kDpAlignClasses; ++k) {
+            if(!nw[k]) continue;
+            al.stage_lo = k ? kDpAlignClassCap[k - 1] : 0;
+            al.stage_hi = k < kDpAlignClasses ? kDpAlignClassCap[k] : 0xFFFFFFFFu;
+            al.stage_max = cls[k].stage_max;
+            al.trace_stride = stride[k];
+            al.seq_ws = k < kDpAlignClasses ? nullptr : d_seq_ws.p;
+            al.seq_ws_stride = k < kDpAlignClasses ? 0 : ((uint64_t)cls[k].stage_max + 255) & ~255ull;
+            const uint32_t n = nw[k];
+            const int st = timed_launch(ctx, LRSC_K_DP, [&]() { return launch_dp_align(al, n, ctx->stream); });
+            if(st != LRSC_OK) return st;
+        }
+        return LRSC_OK;
+    }
+};
+
 // The DP stage for a set of requests whose queries are already on the device: seeds -> (chunked by memory)
 // retrieve -> align -> MSA.  Results stay on the device (d_msa[i], consensus codes at d_cons + reqs[i].cons_off).
 struct DpStage {
@@ -1236,8 +1278,6 @@ struct DpStage {
         const uint32_t n = (uint32_t)reqs.size();
         n_strings = 0; cons_total = 0;
         if(n == 0) return LRSC_OK;
-        std::vector<uint8_t> too_long(n, 0);
-        bool any_too_long = false;
         for(DpRequest& r : reqs) {
             if(r.k == 0 || r.lq < r.k) return fail(LRSC_ERR_ARG, "dp request: kmer_len must satisfy 1 <= kmer_len <= query length");
             if(r.coverage > 1000) return fail(LRSC_ERR_UNSUPPORTED, "dp request: coverage above 1000 (12-bit column counters)");
@@ -1248,9 +1288,6 @@ struct DpStage {
             r.w_cols = dp_msa_columns(r.lq);
             r.cons_off = cons_total;
             cons_total += r.cons_cap;
-            // beyond the alignment kernel's LDS staging (query + one retrieved string: about 30 kb of query): its alignments go through the
-            // global-workspace variant of the kernel in a second launch
-            if(dp_align_stage_bytes(r.lq, r.str_cap) > kDpAlignLdsCap) too_long[(size_t)(&r - reqs.data())] = 1;
         }
         HIP_TRY(d_reqs.reserve(n));
         HIP_TRY(d_msa.reserve(n));
@@ -1268,19 +1305,17 @@ struct DpStage {
         const uint32_t n_waves = dp_wave_count(ctx);
         uint32_t begin = 0;
         while(begin < n) {
-            uint32_t end = begin, max1 = 1, max2 = 1, lds = 0, max1_long = 0, max2_long = 0;
-            uint64_t jobs_long = 0;
+            uint32_t end = begin, lds = 0;
             uint64_t jobs = 0, sbytes = 0, obytes = 0;
+            DpAlignClasses classes;
             while(end < n) {
                 DpRequest& r = reqs[end];
                 r.n_str = r.cnt[0] + r.cnt[1] + r.cnt[2] + r.cnt[3];
-                any_too_long = any_too_long || too_long[end];
                 const uint64_t sb = (uint64_t)r.n_str * r.str_cap, ob = (uint64_t)r.n_str * r.ops_cap;
                 if(end > begin && sbytes + obytes + sb + ob + (jobs + r.n_str) * (sizeof(DpJob) + sizeof(DpAlignOut)) > budget) break;
                 r.job_first = jobs; r.str_off = sbytes; r.ops_off = obytes;
                 jobs += r.n_str; sbytes += sb; obytes += ob;
-                if(!too_long[end]) { max1 = std::max(max1, r.lq); max2 = std::max(max2, r.str_cap); }
-                else { max1_long = std::max(max1_long, r.lq); max2_long = std::max(max2_long, r.str_cap); jobs_long += r.n_str; }
+                classes.add(r.lq, dp_align_stage_bytes(r.lq, r.str_cap), r.n_str);
                 lds = std::max(lds, dp_msa_lds_bytes(r.w_cols, r.lq, r.str_cap, r.ops_cap, r.n_str));
                 ++end;
             }
@@ -1301,39 +1336,21 @@ struct DpStage {
                 DpAlignArgs al{};
                 al.codes = d_query_codes; al.strings = d_strings.p; al.jobs = d_jobs.p; al.n_jobs = (uint32_t)jobs;
                 al.band_width = 200; al.match_score = 1; al.gap_penalty = -1; al.mismatch_penalty = -8;   // LongReadOverlap.cpp:635-643
-                al.ops = d_ops.p; al.out = d_align.p; al.max_s1 = max1; al.max_s2 = max2; al.reqs = c.reqs;
-                al.trace_stride = (uint64_t)(max1 + 17) * kDpTraceStride;
-                // 8 wavefronts per SIMD hide the scan's cross-lane latency; the traceback scratch is capped at 4 GB
-                uint64_t nw64 = std::min<uint64_t>((uint64_t)n_waves * 4, jobs);
-                nw64 = std::max<uint64_t>(1, std::min<uint64_t>(nw64, (4ull << 30) / al.trace_stride));
-                const uint32_t nw = (uint32_t)nw64;
-                HIP_TRY(d_trace.reserve(al.trace_stride * nw));
-                al.trace = d_trace.p;
-                al.lds_cap = kDpAlignLdsCap;
-                st = timed_launch(ctx, LRSC_K_DP, [&]() { return launch_dp_align(al, nw, ctx->stream); });
+                al.ops = d_ops.p; al.out = d_align.p; al.reqs = c.reqs;
+                // 8 wavefronts per SIMD hide the scan's cross-lane latency
+                st = classes.launch(ctx, al, (uint32_t)std::min<uint64_t>((uint64_t)n_waves * 4, jobs), d_trace, d_seq_ws);
                 if(st != LRSC_OK) return st;
-                if(jobs_long) {
-                    // the alignments of requests beyond the LDS stage: same kernel, sequences staged in a global slice per wavefront
-                    DpAlignArgs gl = al;
-                    gl.max_s1 = max1_long; gl.max_s2 = max2_long; gl.only_long = 1;
-                    gl.trace_stride = (uint64_t)(max1_long + 17) * kDpTraceStride;
-                    gl.seq_ws_stride = (dp_align_stage_bytes(max1_long, max2_long) + 255) & ~255ull;
-                    const uint32_t nwl = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(jobs_long, 1024), (4ull << 30) / gl.trace_stride));
-                    HIP_TRY(d_trace.reserve(gl.trace_stride * nwl));
-                    HIP_TRY(d_seq_ws.reserve(gl.seq_ws_stride * nwl));
-                    gl.trace = d_trace.p; gl.seq_ws = d_seq_ws.p;
-                    st = timed_launch(ctx, LRSC_K_DP, [&]() { return launch_dp_align(gl, nwl, ctx->stream); });
-                    if(st != LRSC_OK) return st;
-                }
             }
             if(std::getenv("LRSC_CORRECT_PROFILE") && begin == 0 && jobs) {
                 std::vector<DpAlignOut> ao(jobs);
                 (void)hipMemcpy(ao.data(), d_align.p, jobs * sizeof(DpAlignOut), hipMemcpyDeviceToHost);
                 double tf = 0, tt = 0, cols = 0, na = 0;
                 for(const DpAlignOut& o : ao) if(!o.skipped) { tf += o.t_fill; tt += o.t_trace; cols += o.total_columns; na += 1; }
-                std::fprintf(stderr, "[lrsc] align: %llu jobs (%.0f aligned), %.0f columns avg, per job %.0f ticks fill + %.0f ticks traceback; lds %u B, %u waves\n",
+                std::fprintf(stderr, "[lrsc] align: %llu jobs (%.0f aligned), %.0f columns avg, per job %.0f ticks fill + %.0f ticks traceback; %u waves; jobs / lds B per class:",
                              (unsigned long long)jobs, na, cols / std::max(na, 1.0), tf / std::max(na, 1.0), tt / std::max(na, 1.0),
-                             ((max1 + 2 + 3) & ~3u) + max2 + 8, (unsigned)std::min<uint64_t>((uint64_t)n_waves * 4, jobs));
+                             (unsigned)std::min<uint64_t>((uint64_t)n_waves * 4, jobs));
+                for(const DpAlignClasses::Class& k : classes.cls) std::fprintf(stderr, " %llu / %u", (unsigned long long)k.jobs, k.stage_max);
+                std::fprintf(stderr, " (the last from global memory)\n");
             }
             if(std::getenv("LRSC_DP_DEBUG")) {
                 std::vector<DpAlignOut> ao(jobs);
@@ -1450,7 +1467,6 @@ struct DpStage {
             n_strings += jobs;
             begin = end;
         }
-        (void)any_too_long;
         return LRSC_OK;
     }
 };
@@ -2074,7 +2090,7 @@ extern "C" int lrsc_dp_align(lrsc_ctx* ctx, const char* seq, uint64_t seq_len, c
     if(st != LRSC_OK) return st;
     std::vector<DpJob> dj(n);
     uint64_t ops_total = 0;
-    uint32_t max1 = 1, max2 = 1;
+    DpAlignClasses classes;
     for(uint32_t i = 0; i < n; ++i) {
         const lrsc_dp_job& j = jobs[i];
         if(j.s1_off + j.s1_len > seq_len || j.s2_off + j.s2_len > seq_len) return fail(LRSC_ERR_ARG, "dp job: sequence out of range");
@@ -2083,33 +2099,24 @@ extern "C" int lrsc_dp_align(lrsc_ctx* ctx, const char* seq, uint64_t seq_len, c
         d.s1_off = j.s1_off; d.s2_off = j.s2_off; d.s1_len = j.s1_len; d.s2_len = j.s2_len; d.start1 = j.start1; d.start2 = j.start2;
         d.mode = 0; d.req = 0; d.ops_off = ops_total;
         ops_total += (uint64_t)j.s1_len + j.s2_len + 1;
-        max1 = std::max(max1, j.s1_len); max2 = std::max(max2, j.s2_len);
+        classes.add(j.s1_len, dp_align_stage_bytes(j.s1_len, j.s2_len), 1);
     }
-    // sequences beyond the 64 KB LDS stage: the same kernel with its staging in a global slice per wavefront (fewer wavefronts)
-    const bool global_stage = dp_align_stage_bytes(max1, max2) > kDpAlignLdsCap;
-    const uint64_t stage_stride = (dp_align_stage_bytes(max1, max2) + 255) & ~255ull;
-    const uint32_t n_waves = std::min<uint32_t>(global_stage ? 1024u : dp_wave_count(ctx), n);
     DevBuf<uint8_t> d_codes, d_ops, d_trace, d_stage;
     DevBuf<DpJob> d_jobs;
     DevBuf<DpAlignOut> d_out;
     DpAlignArgs a{};
-    a.trace_stride = (uint64_t)(max1 + 17) * kDpTraceStride;
     HIP_TRY(d_codes.reserve(std::max<uint64_t>(seq_len, 1)));
     HIP_TRY(d_ops.reserve(ops_total));
-    HIP_TRY(d_trace.reserve(a.trace_stride * n_waves));
     HIP_TRY(d_jobs.reserve(n));
     HIP_TRY(d_out.reserve(n));
     HIP_TRY(hipMemcpyAsync(d_codes.p, codes.data(), seq_len, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(d_jobs.p, dj.data(), (size_t)n * sizeof(DpJob), hipMemcpyHostToDevice, ctx->stream));
     a.codes = d_codes.p; a.strings = d_codes.p; a.jobs = d_jobs.p; a.n_jobs = n; a.band_width = (uint32_t)band_width;
     a.match_score = match_score; a.gap_penalty = gap_penalty; a.mismatch_penalty = mismatch_penalty;
-    a.ops = d_ops.p; a.out = d_out.p; a.trace = d_trace.p; a.max_s1 = max1; a.max_s2 = max2;
-    a.lds_cap = kDpAlignLdsCap;
-    if(global_stage) {
-        HIP_TRY(d_stage.reserve(stage_stride * n_waves));
-        a.seq_ws = d_stage.p; a.seq_ws_stride = stage_stride; a.only_long = 0;
-    }
-    st = timed_launch(ctx, LRSC_K_DP, [&]() { return launch_dp_align(a, n_waves, ctx->stream); });
+    a.ops = d_ops.p; a.out = d_out.p;
+    // one launch per staging-size class; sequences beyond the 64 KB LDS stage: the same kernel with its staging in a global slice per
+    // wavefront (fewer wavefronts)
+    st = classes.launch(ctx, a, dp_wave_count(ctx), d_trace, d_stage);
     if(st != LRSC_OK) return st;
     std::vector<DpAlignOut> out(n);
     std::vector<uint8_t> ops(ops_total);

@@ -6,7 +6,9 @@
 // lane in registers.  The in-column dependency cell[j] = max(A[j], cell[j-1] + gap) is a prefix maximum of
 // A[j] - gap*j, so a column costs one wave scan instead of a serial chain.  The reference's quirks are kept:
 // the first computed row of a column ignores "up", the last computed row ignores "left" (:476,:506-512),
-// never-written cells read as 0.
+// never-written cells read as 0.  Cells are stored with gap*(band row) already subtracted, and the columns run
+// in turns of four, each turn in the code of its class (outside the matrix / interior / cut by a matrix edge):
+// straight-line code under wave-uniform branches only (dp_column).
 // Traceback: which neighbour the traceback takes at a cell (:604-661) depends only on that cell (its
 // score, the three neighbour scores as _getBandedCellScore sees them, and the two homopolymer tests), so
 // the fill stores the decision itself -- 2 bits per cell, one 64-byte line per column -- and the traceback
@@ -29,42 +31,183 @@ __device__ __forceinline__ int imax(int a, int b) { return a > b ? a : b; }
 template <int CTRL, int ROW_MASK = 0xF>
 __device__ __forceinline__ int dpp(int old, int x) { return __builtin_amdgcn_update_dpp(old, x, CTRL, ROW_MASK, 0xF, false); }
 
-// inclusive prefix max over the wave (lane order): Kogge-Stone inside each row of 16, then two row broadcasts
+// inclusive prefix max over the wave (lane order): Kogge-Stone inside each row of 16, then two row broadcasts; a lane without a
+// source takes the maximum with the identity, which lets each step be one v_max_i32 with a DPP operand
 __device__ __forceinline__ int wave_prefix_max(int x)
 {
-    x = imax(x, dpp<0x111>(kNeg, x));
-    x = imax(x, dpp<0x112>(kNeg, x));
-    x = imax(x, dpp<0x114>(kNeg, x));
-    x = imax(x, dpp<0x118>(kNeg, x));
-    x = imax(x, dpp<0x142, 0xA>(kNeg, x));
-    x = imax(x, dpp<0x143, 0xC>(kNeg, x));
+    x = imax(x, dpp<0x111>(kIntMin, x));
+    x = imax(x, dpp<0x112>(kIntMin, x));
+    x = imax(x, dpp<0x114>(kIntMin, x));
+    x = imax(x, dpp<0x118>(kIntMin, x));
+    x = imax(x, dpp<0x142, 0xA>(kIntMin, x));
+    x = imax(x, dpp<0x143, 0xC>(kIntMin, x));
     return x;
 }
+__device__ __forceinline__ uint32_t uni(uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); }
+__device__ __forceinline__ uint64_t uni64(uint64_t x) { return (uint64_t)uni((uint32_t)(x >> 32)) << 32 | uni((uint32_t)x); }
 __device__ __forceinline__ int lane_below(int old, int x) { return dpp<0x138>(old, x); }     // value of lane - 1
 __device__ __forceinline__ int lane_above(int old, int x) { return dpp<0x130>(old, x); }     // value of lane + 1
+
+// The traceback's choice at a cell (overlapper.cpp:604-661) as the reference's decision tree: 0 = M, 1 = M over a mismatch, 2 = I, 3 = D.
+constexpr uint32_t dp_dir_tree(bool eq_diag, bool eq_up, bool eq_left, bool h1, bool h2, bool mismatch)
+{
+    uint32_t dir = 0;
+    if(h2) dir = eq_up ? 2u : eq_left ? 3u : 0u;
+    else if(h1) dir = eq_left ? 3u : eq_up ? 2u : 0u;
+    else dir = eq_diag ? 0u : eq_left ? 3u : 2u;
+    if(dir == 0u && mismatch) dir = 1u;
+    return dir;
+}
+// The same function as two boolean expressions, one per bit of the code: on lane predicates these are scalar mask operations, where
+// the tree is a nest of exec-mask regions.
+// (a choice c ? a : b between predicates is written b ^ (c & (a ^ b)): as a select the compiler takes it through vector registers)
+constexpr bool dp_pick(bool c, bool a, bool b) { return b ^ (c & (a ^ b)); }
+constexpr bool dp_dir_bit1(bool eq_diag, bool eq_up, bool eq_left, bool h1, bool h2)
+{
+    return dp_pick(h1 | h2, eq_up | eq_left, !eq_diag);
+}
+constexpr bool dp_dir_bit0(bool eq_diag, bool eq_up, bool eq_left, bool h1, bool h2, bool mismatch)
+{
+    return dp_pick(h2, !eq_up & (eq_left | mismatch), dp_pick(h1, eq_left | (!eq_up & mismatch), dp_pick(eq_diag, mismatch, eq_left)));
+}
+constexpr bool dp_dir_bits_match_tree()
+{
+    for(uint32_t m = 0; m < 64; ++m) {
+        const bool d = m & 1, u = m & 2, l = m & 4, h1 = m & 8, h2 = m & 16, x = m & 32;
+        if(dp_dir_tree(d, u, l, h1, h2, x) != ((uint32_t)dp_dir_bit1(d, u, l, h1, h2) << 1 | (uint32_t)dp_dir_bit0(d, u, l, h1, h2, x))) return false;
+    }
+    return true;
+}
+static_assert(dp_dir_bits_match_tree(), "the two-bit form of the traceback decision differs from the reference's tree");
+
+// What a lane knows about its four band rows r0 .. r0 + 3 for the whole launch.
+struct DpLane {
+    int r0;
+    int zero[4];                  // a never-written cell in the form the fill keeps (see dp_column): score 0 in the band, kNeg above it
+    bool top1, top3;              // row r0 + 1 / r0 + 3 is row bw, the first above the band (bw is odd)
+};
+struct DpScores { int ms, mx, g, g2; };
+
+// Columns K .. of a turn of four.  Cells are kept BIASED: H[t] = score - gap * r for band row r = r0 + t.  A cell's diagonal neighbour
+// has the same r in the previous column and its left neighbour r + 1, so diag = Hp[t] + match/mismatch and left = Hp[t + 1] + 2 gap in
+// biased form, the in-column chain cell[j] = max(A[j], cell[j - 1] + gap) is a plain prefix maximum, and "came from above" is
+// Hc[t] == Hc[t - 1].  Row bw, just above the band, is kept at kNeg in every column: row bw - 1 then never takes "left" and never equals
+// it, which is the reference's r + 1 < bw test; rows beyond hold values nothing reads.  Row 0 compares "up" with kIntMin.
+// EDGE = false: an interior column (band rows 0 .. bw - 1 all inside the matrix, row L2 not among them): every band row is computed, the
+// first is row 0 and the last row bw - 1.  EDGE = true: rows [rlo, rhi) are computed (wave-uniform; empty = a skipped column); rlast is
+// the last of them unless it is also the first, else -1: the row that ignores "left" (overlapper.cpp:476,:506-512; the first computed
+// row never takes "up" because the rows below it are masked out of the scan).
+// c1 / h1: this column's s1 character and its homopolymer test (wave-uniform); e[K .. K + 4]: s2 characters of rows r0 .. r0 + 4;
+// h2[K + t]: e[K + t] == e[K + t + 1].  Returns the lane's four 2-bit traceback codes.
+template <bool EDGE, int K>
+__device__ __forceinline__ uint32_t dp_column(const DpLane& C, const DpScores& sc, const int (&Hp)[4], int (&Hc)[4], uint32_t c1, bool h1,
+                                              const uint32_t (&e)[8], const bool (&h2)[7], int rlo, int rhi, int rlast)
+{
+    const int hp4 = lane_above(0, Hp[0]);
+    int diag[4], leftg[4], B[4];
+    bool inr[4], mis[4];
+#pragma unroll
+    for(int t = 0; t < 4; ++t) {
+        const int r = C.r0 + t;
+        mis[t] = c1 != e[K + t];
+        diag[t] = Hp[t] + (mis[t] ? sc.mx : sc.ms);
+        leftg[t] = (t < 3 ? Hp[t + 1] : hp4) + sc.g2;
+        if(EDGE) {
+            inr[t] = (r >= rlo) & (r < rhi);
+            const int A = imax(diag[t], r == rlast ? kNeg : leftg[t]);
+            B[t] = inr[t] ? A : kNeg;
+        } else {
+            B[t] = imax(diag[t], leftg[t]);
+        }
+    }
+    const int p0 = B[0], p1 = imax(p0, B[1]), p2 = imax(p1, B[2]), p3 = imax(p2, B[3]);
+    const int incl = wave_prefix_max(p3);
+    const int excl = lane_below(kNeg, incl);
+    const int P[4] = {imax(p0, excl), imax(p1, excl), imax(p2, excl), imax(p3, excl)};
+#pragma unroll
+    for(int t = 0; t < 4; ++t) Hc[t] = EDGE ? (inr[t] ? P[t] : C.zero[t]) : P[t];
+    if(!EDGE) { Hc[1] = C.top1 ? kNeg : Hc[1]; Hc[3] = C.top3 ? kNeg : Hc[3]; }
+    const int below = lane_below(kIntMin, Hc[3]);               // band row r0 - 1 of this column
+    uint32_t flags = 0;
+#pragma unroll
+    for(int t = 0; t < 4; ++t) {
+        const bool eq_diag = Hc[t] == diag[t];
+        const bool eq_up = Hc[t] == (t > 0 ? Hc[t - 1] : below);
+        const bool eq_left = Hc[t] == leftg[t];
+        bool b1 = dp_dir_bit1(eq_diag, eq_up, eq_left, h1, h2[K + t]);
+        bool b0 = dp_dir_bit0(eq_diag, eq_up, eq_left, h1, h2[K + t], mis[t]);
+        if(EDGE) { b1 = b1 & inr[t]; b0 = b0 & inr[t]; }        // interior: the codes of rows >= bw are never read
+        flags |= (b0 ? 1u << (2 * t) : 0u) | (b1 ? 2u << (2 * t) : 0u);
+    }
+    return flags;
+}
+
+// Column K of a turn whose band is cut by the first or the last matrix row, or holds the matrix's last row (whose best cell the
+// traceback may start from): the computed rows follow from the column's first matrix row jb.
+struct DpEdge { int jb0, num_rows, bw, L2, i; };
+template <int K>
+__device__ __forceinline__ void dp_edge_column(const DpLane& C, const DpScores& sc, const DpEdge& E, const int (&Hp)[4], int (&Hc)[4],
+                                               const uint32_t (&c)[5], const bool (&h1)[4], const uint32_t (&e)[8], const bool (&h2)[7],
+                                               uint8_t* tr, int& best_row_val, int& best_row_i)
+{
+    const int jb = E.jb0 + K;
+    const int rlo = jb < 1 ? 1 - jb : 0;
+    const int rhi = E.num_rows - jb < E.bw ? E.num_rows - jb : E.bw;
+    const int rlast = rhi - 1 != rlo ? rhi - 1 : -1;
+    tr[K * kDpTraceStride] = (uint8_t)dp_column<true, K>(C, sc, Hp, Hc, c[K], h1[K], e, h2, rlo, rhi, rlast);
+    const int rl = E.L2 - jb;                                   // band row of the matrix's last row
+    if(rl >= 0 && rl < E.bw) {                                  // (wave-uniform: its best cell is tracked in scalar registers)
+        const int ln = rl >> 2, ts = rl & 3;
+        const int h = ts == 0 ? __builtin_amdgcn_readlane(Hc[0], ln) : ts == 1 ? __builtin_amdgcn_readlane(Hc[1], ln)
+                    : ts == 2 ? __builtin_amdgcn_readlane(Hc[2], ln) : __builtin_amdgcn_readlane(Hc[3], ln);
+        const int v = h + sc.g * rl;
+        if(v > best_row_val) { best_row_val = v; best_row_i = E.i + K; }
+    }
+}
+__device__ __forceinline__ void dp_copy(int (&dst)[4], const int (&src)[4])
+{
+#pragma unroll
+    for(int t = 0; t < 4; ++t) dst[t] = src[t];
+}
 } // namespace
 
 template <bool GLOBAL>
 __global__ __launch_bounds__(64) void dp_align_kernel(DpAlignArgs a)
 {
-    extern __shared__ uint8_t lds[];
+    extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     // the two sequences are staged in LDS, or -- for the few alignments beyond it -- in this wavefront's slice of a global workspace
     uint8_t* smem = GLOBAL ? a.seq_ws + (uint64_t)blockIdx.x * a.seq_ws_stride : lds;
     uint8_t* S1 = smem;                                        // s1 codes, S1[L1] = 4 (the string's NUL)
-    // s2 codes at S2[0 .. L2), sentinel 4 in the kS2Pad bytes before and the 16 after: a lane's five characters
-    // s2[j-1 .. j+3] are then two aligned dword reads for any band position
-    uint8_t* S2buf = smem + ((a.max_s1 + 2 + 3) & ~3u);
-    uint8_t* S2 = S2buf + kS2Pad;
-    for(uint32_t i = threadIdx.x; i < kS2Pad; i += 64) S2buf[i] = 4;
-    const uint32_t lane = threadIdx.x;
+    const uint32_t tid = threadIdx.x;
     uint8_t* trace = a.trace + (uint64_t)blockIdx.x * a.trace_stride;
     const int half = (int)a.band_width / 2;
     const int bw = 2 * half + 1;
-    const int g = a.gap_penalty, MS = a.match_score, MX = a.mismatch_penalty;
-    const int r0 = 4 * (int)lane;
+    const DpScores sc = {a.match_score, a.mismatch_penalty, a.gap_penalty, 2 * a.gap_penalty};
+    const int g = sc.g;
+    const int r0 = 4 * (int)tid;
+    DpLane C;
+    C.r0 = r0; C.top1 = r0 + 1 == bw; C.top3 = r0 + 3 == bw;
+#pragma unroll
+    for(int t = 0; t < 4; ++t) {
+        const int r = r0 + t;
+        C.zero[t] = r < bw ? -g * r : kNeg;
+    }
 
     for(uint32_t job = blockIdx.x; job < a.n_jobs; job += gridDim.x) {
-        const DpJob J = a.jobs[job];
+        // (the lane number is made opaque here and before the traceback: addresses derived from it are then formed where they are used and
+        //  do not stay in registers through the fill)
+        uint32_t lane = tid;
+        asm volatile("" : "+v"(lane));
+        DpJob J = a.jobs[job];                                     // the same for every lane: keep it in scalar registers
+        J.s1_off = uni64(J.s1_off); J.s2_off = uni64(J.s2_off); J.ops_off = uni64(J.ops_off);
+        J.s1_len = uni(J.s1_len); J.s2_len = uni(J.s2_len); J.start1 = (int32_t)uni((uint32_t)J.start1); J.start2 = (int32_t)uni((uint32_t)J.start2);
+        J.mode = uni(J.mode); J.req = uni(J.req);
+        {
+            // every launch does the alignments of one staging-size class (by the owning request's capacities where there is one, as
+            // the host sized the launches: a long query with a short retrieved string is still long)
+            const uint32_t sb = a.reqs ? dp_align_stage_bytes(a.reqs[J.req].lq, a.reqs[J.req].str_cap) : dp_align_stage_bytes(J.s1_len, J.s2_len);
+            if(sb <= a.stage_lo || sb > a.stage_hi) continue;
+        }
         DpAlignOut o;
         o.m0s = 0; o.m0e = -1; o.m1s = 0; o.m1e = -1; o.score = -1; o.edit_distance = -1; o.total_columns = -1; o.n_ops = 0;
         o.accept = 0; o.skipped = 1; o.t_fill = 0; o.t_trace = 0;
@@ -74,16 +217,13 @@ __global__ __launch_bounds__(64) void dp_align_kernel(DpAlignArgs a)
             continue;
         }
         const int L1 = (int)J.s1_len, L2 = (int)J.s2_len;
-        {
-            // an alignment beyond the LDS stage belongs to the global-workspace launch (and only those do)
-            // (classified by the owning request's capacities, as the host sized the two launches: a long query with a short retrieved
-            //  string is still long)
-            const bool is_long = a.reqs ? dp_align_stage_bytes(a.reqs[J.req].lq, a.reqs[J.req].str_cap) > a.lds_cap
-                                        : dp_align_stage_bytes(J.s1_len, J.s2_len) > a.lds_cap;
-            if(GLOBAL ? (a.only_long && !is_long) : is_long) continue;
-        }
+        // s2 codes at S2[0 .. L2), sentinel 4 in the kS2Pad bytes before and the 16 after: the twelve aligned bytes that hold a lane's
+        // characters s2[j - 1 .. j + 6] of four columns can then be read for any band position
+        uint8_t* S2buf = smem + (((uint32_t)L1 + 2 + 3) & ~3u);
+        uint8_t* S2 = S2buf + kS2Pad;
         __syncthreads();
         if(GLOBAL) __threadfence_block();
+        for(uint32_t i = lane; i < kS2Pad; i += 64) S2buf[i] = 4;
         for(int i = (int)lane; i <= L1; i += 64) S1[i] = i < L1 ? a.codes[J.s1_off + i] : (uint8_t)4;
         for(int j = (int)lane; j < L2 + 16; j += 64) S2[j] = j < L2 ? a.strings[J.s2_off + j] : (uint8_t)4;
         __syncthreads();
@@ -101,79 +241,75 @@ __global__ __launch_bounds__(64) void dp_align_kernel(DpAlignArgs a)
 
         const int origin = (J.start2 - J.start1 + 1) - (half + 1);
         const int num_rows = L2 + 1;
-        int prev[4] = {0, 0, 0, 0};
         int best_row_val = kIntMin, best_row_i = 0;
+        int H[4], T[4];
+#pragma unroll
+        for(int t = 0; t < 4; ++t) H[t] = C.zero[t];
+        const uint32_t* S1w = reinterpret_cast<const uint32_t*>(S1);
+        const uint32_t s2_shift = (uint32_t)origin & 3u;            // byte offset of a lane's first character in its aligned window: the
+                                                                    // window starts at origin + i - 1 + 4 lane + kS2Pad with i = 1 (mod 4)
+        const int s2_last = (int)kS2Pad + ((L2 + 4) & ~3);          // last window start whose twelve bytes are staged
 
-        for(int i = 1; i <= L1; ++i) {
-            const int jbase = origin + i;
-            const int j_lo = jbase < 1 ? 1 : jbase;
-            const int j_hi = jbase + bw > num_rows ? num_rows : jbase + bw;
-            const bool skipcol = j_hi <= 0 || j_lo >= num_rows || j_lo >= j_hi;
-            int cur[4] = {0, 0, 0, 0};
-            uint32_t flags = 0;
-            const int prev_next = lane_above(0, prev[0]);
-            if(!skipcol) {
-                const uint32_t c1 = S1[i - 1];
-                const bool h1 = c1 == S1[i];
-                uint32_t s2c[5];
-                {
-                    int idx = jbase + r0 - 1;                               // >= -kS2Pad whenever the column is computed
-                    idx = idx > L2 + 8 ? L2 + 8 : idx;                      // rows past the end are out of range anyway
-                    const uint32_t b = (uint32_t)(idx + (int)kS2Pad);
-                    const uint32_t* p32 = reinterpret_cast<const uint32_t*>(S2buf + (b & ~3u));
-                    const unsigned long long v = (((unsigned long long)p32[1] << 32) | p32[0]) >> (8u * (b & 3u));
+        // four columns per turn: i = 1 (mod 4), so their s1 characters are one aligned dword (plus one byte for the last h1) and a
+        // lane's s2 characters one 8-byte window that moves by a byte per column
+        for(int i = 1; i <= L1; i += 4) {
+            const int n = L1 - i + 1 < 4 ? L1 - i + 1 : 4;
+            const int jb0 = origin + i;                             // first matrix row of the band in the first of the columns
+            uint8_t* tr = trace + (uint64_t)i * kDpTraceStride + tid;
+            if(n == 4 && (jb0 + 3 + bw <= 1 || jb0 >= num_rows)) {  // the band lies outside the matrix in all four: cells read as 0
 #pragma unroll
-                    for(int t = 0; t < 5; ++t) s2c[t] = (uint32_t)(v >> (8 * t)) & 0xFFu;
-                }
-                int diag[4], leftg[4], B[4];
-                bool inr[4], left_in[4];
+                for(int k = 0; k < 4; ++k) tr[k * kDpTraceStride] = 0;
 #pragma unroll
-                for(int t = 0; t < 4; ++t) {
-                    const int r = r0 + t, j = jbase + r;
-                    inr[t] = j >= j_lo && j < j_hi;
-                    diag[t] = prev[t] + (c1 == s2c[t] ? MS : MX);
-                    left_in[t] = r + 1 < bw;
-                    leftg[t] = (t < 3 ? prev[t + 1] : prev_next) + g;
-                    int A;
-                    if(j == j_lo) A = imax(left_in[t] ? leftg[t] : kNeg, diag[t]);
-                    else if(j == j_hi - 1) A = diag[t];
-                    else A = imax(diag[t], leftg[t]);
-                    B[t] = inr[t] ? A - g * r : kNeg;
-                }
-                const int p0 = B[0], p1 = imax(p0, B[1]), p2 = imax(p1, B[2]), p3 = imax(p2, B[3]);
-                const int incl = wave_prefix_max(p3);
-                const int excl = lane_below(kNeg, incl);
-                const int P[4] = {imax(p0, excl), imax(p1, excl), imax(p2, excl), imax(p3, excl)};
-#pragma unroll
-                for(int t = 0; t < 4; ++t) cur[t] = inr[t] ? P[t] + g * (r0 + t) : 0;
-                const int below = lane_below(0, cur[3]);            // band row r0 - 1 of this column
-#pragma unroll
-                for(int t = 0; t < 4; ++t) {
-                    const int r = r0 + t;
-                    const int curr = cur[t];
-                    const bool eq_diag = curr == diag[t];
-                    const bool eq_up = r >= 1 && curr == (t > 0 ? cur[t - 1] : below) + g;
-                    const bool eq_left = left_in[t] && curr == leftg[t];
-                    const bool h2 = s2c[t] == s2c[t + 1];
-                    uint32_t dir;                                   // 0 = M, 2 = I, 3 = D
-                    if(h2) dir = eq_up ? 2u : eq_left ? 3u : 0u;
-                    else if(h1) dir = eq_left ? 3u : eq_up ? 2u : 0u;
-                    else dir = eq_diag ? 0u : eq_left ? 3u : 2u;
-                    if(dir == 0u && c1 != s2c[t]) dir = 1u;         // M over a mismatch
-                    flags |= inr[t] ? dir << (2 * t) : 0u;
-                }
+                for(int t = 0; t < 4; ++t) H[t] = C.zero[t];
+                continue;
             }
-            trace[(uint64_t)i * kDpTraceStride + lane] = (uint8_t)flags;
-            // last row (j = L2) of this column, if it is inside the band
+            uint32_t c[5];
+            bool h1[4];
             {
-                const int r = L2 - jbase;
-                if(r >= r0 && r < r0 + 4 && r >= 0 && r < bw) {
-                    const int v = cur[r - r0];
-                    if(v > best_row_val) { best_row_val = v; best_row_i = i; }
+                const uint32_t w0 = uni(S1w[(i - 1) >> 2]);
+                const int nxt = (i + 3) >> 2 < L1 >> 2 ? (i + 3) >> 2 : L1 >> 2;      // only a full turn looks at its byte
+                const uint32_t w1 = uni(S1w[nxt]);
+#pragma unroll
+                for(int k = 0; k < 4; ++k) c[k] = (w0 >> (8 * k)) & 0xFFu;
+                c[4] = w1 & 0xFFu;
+#pragma unroll
+                for(int k = 0; k < 4; ++k) h1[k] = c[k] == c[k + 1];
+            }
+            uint32_t e[8];
+            bool h2[7];
+            {
+                // lanes whose window is clamped have no row inside the matrix in any of the four columns
+                int b = jb0 + r0 - 1 + (int)kS2Pad;
+                b = (b < 0 ? 0 : b) & ~3;
+                b = b > s2_last ? s2_last : b;
+                const uint32_t* p32 = reinterpret_cast<const uint32_t*>(S2buf + b);
+                const uint32_t d0 = p32[0], d1 = p32[1], d2 = p32[2];
+                const uint32_t lo = __builtin_amdgcn_alignbyte(d1, d0, s2_shift), hi = __builtin_amdgcn_alignbyte(d2, d1, s2_shift);
+#pragma unroll
+                for(int m = 0; m < 4; ++m) { e[m] = (lo >> (8 * m)) & 0xFFu; e[4 + m] = (hi >> (8 * m)) & 0xFFu; }
+#pragma unroll
+                for(int m = 0; m < 7; ++m) h2[m] = e[m] == e[m + 1];
+            }
+            if(n == 4 && jb0 >= 1 && jb0 + 3 + bw <= L2) {
+                tr[0 * kDpTraceStride] = (uint8_t)dp_column<false, 0>(C, sc, H, T, c[0], h1[0], e, h2, 0, 0, 0);
+                tr[1 * kDpTraceStride] = (uint8_t)dp_column<false, 1>(C, sc, T, H, c[1], h1[1], e, h2, 0, 0, 0);
+                tr[2 * kDpTraceStride] = (uint8_t)dp_column<false, 2>(C, sc, H, T, c[2], h1[2], e, h2, 0, 0, 0);
+                tr[3 * kDpTraceStride] = (uint8_t)dp_column<false, 3>(C, sc, T, H, c[3], h1[3], e, h2, 0, 0, 0);
+                continue;
+            }
+            // the band is cut by the first or the last matrix row, or the last row of the matrix (whose best cell the traceback may
+            // start from) is inside it
+            const DpEdge E = {jb0, num_rows, bw, L2, i};
+            dp_edge_column<0>(C, sc, E, H, T, c, h1, e, h2, tr, best_row_val, best_row_i);
+            if(n == 1) dp_copy(H, T);
+            else {
+                dp_edge_column<1>(C, sc, E, T, H, c, h1, e, h2, tr, best_row_val, best_row_i);
+                if(n > 2) {
+                    dp_edge_column<2>(C, sc, E, H, T, c, h1, e, h2, tr, best_row_val, best_row_i);
+                    if(n == 3) dp_copy(H, T);
+                    else dp_edge_column<3>(C, sc, E, T, H, c, h1, e, h2, tr, best_row_val, best_row_i);
                 }
             }
-#pragma unroll
-            for(int t = 0; t < 4; ++t) prev[t] = cur[t];
         }
 
         // best of the last column (rows ascending, first maximum wins) and of the last row (columns ascending)
@@ -183,15 +319,14 @@ __global__ __launch_bounds__(64) void dp_align_kernel(DpAlignArgs a)
 #pragma unroll
             for(int t = 0; t < 4; ++t) {
                 const int r = r0 + t, j = jbase + r;
-                if(r < bw && j >= 1 && j <= L2 && prev[t] > best_col_val) { best_col_val = prev[t]; best_col_j = j; }
+                const int v = H[t] + g * r;
+                if(r < bw && j >= 1 && j <= L2 && v > best_col_val) { best_col_val = v; best_col_j = j; }
             }
         }
 #pragma unroll
         for(int d = 32; d >= 1; d >>= 1) {
             const int ov = __shfl_xor(best_col_val, d), oj = __shfl_xor(best_col_j, d);
             if(ov > best_col_val || (ov == best_col_val && ov != kIntMin && oj < best_col_j)) { best_col_val = ov; best_col_j = oj; }
-            const int rv = __shfl_xor(best_row_val, d), ri = __shfl_xor(best_row_i, d);
-            if(rv > best_row_val || (rv == best_row_val && rv != kIntMin && ri < best_row_i)) { best_row_val = rv; best_row_i = ri; }
         }
         int ti, tj;
         if(best_col_val > best_row_val) { ti = L1; tj = best_col_j; o.score = best_col_val; }
@@ -203,6 +338,7 @@ __global__ __launch_bounds__(64) void dp_align_kernel(DpAlignArgs a)
 
         // ---- traceback ----------------------------------------------------------------------------------------
         const uint64_t t_job1 = __builtin_readcyclecounter();
+        asm volatile("" : "+v"(lane));
         __threadfence();
         uint32_t w0 = 0, w1 = 0, w2 = 0, w3 = 0;
         int wb = -1;                                                // first column of the 16-column window held in w0..w3
@@ -251,7 +387,7 @@ hipError_t launch_dp_align(const DpAlignArgs& a, uint32_t n_waves, hipStream_t s
 {
     if(a.n_jobs == 0) return hipSuccess;
     if(a.band_width < 2 || (a.band_width / 2) * 2 + 1 > kDpMaxBand) return hipErrorInvalidValue;
-    const size_t lds = dp_align_stage_bytes(a.max_s1, a.max_s2);
+    const size_t lds = a.stage_max;
     if(n_waves > a.n_jobs) n_waves = a.n_jobs;
     if(a.seq_ws) {
         if(a.seq_ws_stride < lds) return hipErrorInvalidValue;

@@ -86,15 +86,17 @@ struct DpAlignArgs {
     uint8_t* ops;                 // 'M' 'I' 'D'
     DpAlignOut* out;
     uint8_t* trace;               // n_waves x trace_stride
-    uint64_t trace_stride;        // (max s1_len + 1) * kDpTraceStride
-    uint32_t max_s1, max_s2;      // staging sizes
+    uint64_t trace_stride;        // (max s1_len of this launch + 17) * kDpTraceStride
     const DpRequest* reqs;        // optional
-    // staging of the two sequences: LDS (seq_ws == nullptr; jobs that do not fit lds_cap are left to a second launch) or, for the few
-    // alignments beyond it (a raw segment of tens of kb between two seeds), a per-wavefront slice of this global workspace
+    // One launch does the alignments of one staging-size class, stage_lo < dp_align_stage_bytes <= stage_hi (of the owning request's
+    // capacities where reqs is set, else of the job's own lengths), and skips the others: a wavefront reserves the LDS of the largest
+    // alignment of its launch, so a few long queries in the launch of the short ones would cost those their occupancy.
+    uint32_t stage_lo, stage_hi;
+    uint32_t stage_max;           // staging bytes of the largest alignment of this launch: its dynamic LDS
+    // staging of the two sequences: LDS (seq_ws == nullptr, stage_max <= kDpAlignLdsCap) or, for the few alignments beyond it (a raw
+    // segment of tens of kb between two seeds), a per-wavefront slice of this global workspace (seq_ws_stride >= stage_max, 256-aligned)
     uint8_t* seq_ws;
     uint64_t seq_ws_stride;
-    uint32_t lds_cap;
-    uint32_t only_long;           // global variant: do only the jobs the LDS launch skipped
 };
 
 // n_waves = gridDim.x; every wave loops over jobs wave, wave + n_waves, ...
@@ -102,6 +104,15 @@ hipError_t launch_dp_align(const DpAlignArgs& a, uint32_t n_waves, hipStream_t s
 // bytes of sequence staging one alignment needs (LDS or global slice)
 constexpr uint32_t dp_align_stage_bytes(uint32_t s1_len, uint32_t s2_len) { return ((s1_len + 2 + 3) & ~3u) + 264u + ((s2_len + 3) & ~3u) + 16u; }
 constexpr uint32_t kDpAlignLdsCap = 64u * 1024u;
+// upper bounds of the staging-size classes that run from LDS; what is beyond the last one runs from the global workspace
+constexpr uint32_t kDpAlignClasses = 3;
+constexpr uint32_t kDpAlignClassCap[kDpAlignClasses] = {4u * 1024u, 16u * 1024u, kDpAlignLdsCap};
+constexpr uint32_t dp_align_class(uint32_t stage_bytes)
+{
+    uint32_t c = 0;
+    while(c < kDpAlignClasses && stage_bytes > kDpAlignClassCap[c]) ++c;
+    return c;                     // kDpAlignClasses = the global-workspace launch
+}
 // lane per (request, direction): the two seed k-mers' bi-intervals -> row_lo / cnt
 hipError_t launch_dp_seeds(const FmIndexDev& fm, const DpPipeArgs& a, hipStream_t stream);
 // lane per retrieved string: LF-walk (retrieveStr), writes the string in its final orientation and its DpJob
