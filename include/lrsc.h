@@ -339,6 +339,61 @@ int lrsc_dp_consensus(lrsc_ctx* ctx, const char* seq, uint64_t seq_len, const lr
 int lrsc_lf_walk(lrsc_ctx* ctx, const uint64_t* rows, const uint8_t* strand, const uint32_t* max_steps,
                  const uint64_t* out_off, uint64_t n, char* out, uint64_t out_cap, uint32_t* out_len);
 
+/* ---- hash-guided seed-pair merge: SAIPBSelfCorrectTree ------------------------------------------------------ */
+/* One job is one tree object of the reference (PacBio/SAIPBSelfCTree.h:140-287): the constructor's rawSeq, an ordered list of
+ * addHashBySingleSeed calls (.cpp:704-787) and one mergeTwoSeedsUsingHash call (.cpp:91-256).  (The reference never instantiates
+ * the class; its commented-out call site is PacBioHybridCorrectionProcess.cpp:1074-1130.)  Strings are ASCII ACGT spans of seq. */
+typedef struct lrsc_saipb_seed {     /* addHashBySingleSeed(seedStr, largeKmerSize, job.hash_kmer, maxLength, skipRepeat, expectedLength) */
+    uint64_t seq_off;
+    uint32_t len;                /* seedStr length (>= large_kmer, >= the job's hash_kmer)                          */
+    uint32_t large_kmer;         /* largeKmerSize                                                                   */
+    uint32_t max_length;         /* maxLength                                                                       */
+    int32_t  expected_length;    /* expectedLength, -1 = the default (source side)                                  */
+    uint32_t skip_repeat;        /* skipRepeat                                                                      */
+    uint32_t pad;
+} lrsc_saipb_seed;
+typedef struct lrsc_saipb_job {
+    uint64_t raw_off;            /* rawSeq (not empty)                                                              */
+    uint64_t src_off;            /* mergeTwoSeedsUsingHash's src                                                    */
+    uint64_t dest_off;           /* ... and dest                                                                    */
+    uint32_t raw_len, src_len, dest_len;   /* src_len, dest_len >= hash_kmer                                        */
+    uint32_t seed_first, n_seeds;          /* the job's addHashBySingleSeed calls, in call order: seeds[seed_first ..) */
+    uint32_t hash_kmer;          /* every seed's smallKmerSize and the merge's hashKmerSize, 2..31                  */
+    uint32_t max_leaves;         /* maxLeaves, 1..64                                                                */
+    uint32_t min_length, max_length, expected_length;
+    uint32_t min_sa_threshold;   /* the constructor's min_SA_threshold                                              */
+    uint32_t pad;
+} lrsc_saipb_job;
+typedef struct lrsc_saipb_result {
+    int32_t  code;               /* mergeTwoSeedsUsingHash's return value: 1, or -1 .. -5 (0 when status != 0)      */
+    int32_t  status;             /* LRSC_SAIPB_OK, or the per-job capacity this job alone outgrew: no numbers then  */
+    uint32_t steps;              /* iterations of the extension loop                                                */
+    uint32_t max_used_leaves;    /* widest frontier at the start of a step                                          */
+    uint32_t n_results;          /* terminated lineages collected                                                   */
+    uint32_t hash_entries;       /* distinct k-mers collected                                                       */
+    uint64_t out_off;            /* mergedseq at out_arena + out_off (code 1 only)                                  */
+    uint32_t out_len;
+    uint32_t pad;
+} lrsc_saipb_result;
+enum lrsc_saipb_status {
+    LRSC_SAIPB_OK = 0,
+    LRSC_SAIPB_HASH_LIMIT = 1,     /* this job's workspace (mostly its k-mer table) would exceed the per-job limit
+                                    * (LRSC_SAIPB_JOB_KB, in KiB, default 262144 = 256 MiB)                          */
+    LRSC_SAIPB_RESULT_LIMIT = 2,   /* more than 32 terminated lineages                                              */
+    LRSC_SAIPB_PATH_LIMIT = 3,     /* the path store / the child list of one step overflowed                        */
+    LRSC_SAIPB_INTERNAL = 4
+};
+/* n_jobs independent jobs on the device, one wavefront each, in chunks that fit the workspace budget (LRSC_SAIPB_CHUNK_MB,
+ * default 1024); seed_freq[i] (may be NULL) = what addHashBySingleSeed returns for seeds[i].  out_arena receives the merged
+ * sequences back to back (*arena_used bytes); LRSC_ERR_CAPACITY if arena_cap is too small (then *arena_used = bytes needed).
+ * LRSC_ERR_ARG where the reference would throw or divide by zero (a seed shorter than its large_kmer or than hash_kmer, src /
+ * dest shorter than hash_kmer, an empty rawSeq); LRSC_ERR_UNSUPPORTED for hash_kmer outside 2..31, max_leaves outside 1..64, a
+ * string or max_length beyond 32000 bases, or raw_len + max_length + dest_len beyond 65534 (the alignment's column count).
+ * The merge launches are counted under LRSC_K_SAIPB (lrsc_ctx_stats). */
+int lrsc_saipb_merge(lrsc_ctx* ctx, const char* seq, uint64_t seq_len, const lrsc_saipb_seed* seeds, uint32_t n_seeds,
+                     const lrsc_saipb_job* jobs, uint32_t n_jobs, lrsc_saipb_result* results, uint64_t* seed_freq,
+                     char* out_arena, uint64_t arena_cap, uint64_t* arena_used);
+
 /* ---- measurement ------------------------------------------------------------------------- */
 typedef struct lrsc_kernel_stats {
     uint64_t launches;          /* launches since the last reset                        */
@@ -347,9 +402,11 @@ typedef struct lrsc_kernel_stats {
     uint64_t block_loads;       /* rank-block loads (lower-1/upper in one block count 1) */
     uint64_t table_loads;       /* k-mer interval table look-ups (one 64-byte line each)  */
 } lrsc_kernel_stats;
-/* LRSC_K_EXTEND_WIDE: the wide walk launches of max_leaves above 32 (one per round with escalated walks; none at <= 32) */
+/* LRSC_K_EXTEND_WIDE: the wide walk launches of max_leaves above 32 (one per round with escalated walks; none at <= 32)
+ * LRSC_K_SAIPB: lrsc_saipb_merge's merge launches, one per workspace chunk; total_ms spans a call's chunks together, the query
+ *   counters are not kept for it */
 enum { LRSC_K_RANK = 0, LRSC_K_FIND = 1, LRSC_K_GRID = 2, LRSC_K_SEEDS = 3, LRSC_K_EXTEND = 4, LRSC_K_LF = 5, LRSC_K_DP = 6, LRSC_K_MSA = 7,
-       LRSC_K_EXTEND_WIDE = 8, LRSC_K_COUNT = 9 };
+       LRSC_K_EXTEND_WIDE = 8, LRSC_K_SAIPB = 9, LRSC_K_COUNT = 10 };
 int lrsc_ctx_stats(lrsc_ctx* ctx, int kernel, lrsc_kernel_stats* out);
 int lrsc_ctx_stats_reset(lrsc_ctx* ctx);
 /* Block until everything queued on the ctx stream is done. */

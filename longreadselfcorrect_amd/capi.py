@@ -108,6 +108,73 @@ class ReadResult(C.Structure):
                                  "exceed_depth_num", "exceed_leave_num", "fm_num", "dp_num", "seed_dis")] + [("status", C.c_int32), ("pad", C.c_int32)]
 
 
+class SaipbSeed(C.Structure):
+    _fields_ = [("seq_off", C.c_uint64), ("len", C.c_uint32), ("large_kmer", C.c_uint32), ("max_length", C.c_uint32),
+                ("expected_length", C.c_int32), ("skip_repeat", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class SaipbJob(C.Structure):
+    _fields_ = [("raw_off", C.c_uint64), ("src_off", C.c_uint64), ("dest_off", C.c_uint64), ("raw_len", C.c_uint32),
+                ("src_len", C.c_uint32), ("dest_len", C.c_uint32), ("seed_first", C.c_uint32), ("n_seeds", C.c_uint32),
+                ("hash_kmer", C.c_uint32), ("max_leaves", C.c_uint32), ("min_length", C.c_uint32), ("max_length", C.c_uint32),
+                ("expected_length", C.c_uint32), ("min_sa_threshold", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class SaipbResult(C.Structure):
+    _fields_ = [("code", C.c_int32), ("status", C.c_int32), ("steps", C.c_uint32), ("max_used_leaves", C.c_uint32),
+                ("n_results", C.c_uint32), ("hash_entries", C.c_uint32), ("out_off", C.c_uint64), ("out_len", C.c_uint32),
+                ("pad", C.c_uint32)]
+
+
+def saipb_pair_jobs(pairs, max_leaves: int = 32):
+    """(source, between, target, dis) per pair -> (seq, seeds, jobs) the way the reference's commented-out call site drives the
+    tree (PacBioHybridCorrectionProcess.cpp:1083-1122; the C++ twin is stride::saipbPairJob in host/SAIPBSelfCTree.h): three source
+    17-mers at offsets 2x, 3x and 1.5x 17 from the source's end, then the reverse-complemented target with its expectedLength;
+    extension k-mer 15; length window 1.1 / 0.9 of the gap with an offset of 30."""
+    comp = str.maketrans("ACGT", "TGCA")
+    n = len(pairs)
+    seeds, jobs = (SaipbSeed * (4 * n))(), (SaipbJob * n)()
+    parts, off = [], 0
+    for i, (source, between, target, dis) in enumerate(pairs):
+        src_k, ext_k = 17, 15
+        rvc = target[::-1].translate(comp)
+        s_off, b_off = off, off + len(source)
+        t_off = b_off + len(between)
+        r_off = t_off + len(target)
+        parts += [source, between, target, rvc]
+        off = r_off + len(rvc)
+        src_max = int(1.1 * (dis + 30) + src_k + ext_k)
+        for q, back in enumerate((2 * src_k, 3 * src_k, int(src_k * 1.5))):
+            sd = seeds[4 * i + q]
+            sd.seq_off, sd.len, sd.large_kmer, sd.max_length = s_off + len(source) - back, src_k, src_k, src_max
+            sd.expected_length, sd.skip_repeat = -1, 1
+        sd = seeds[4 * i + 3]
+        sd.seq_off, sd.len, sd.large_kmer = r_off, len(rvc), src_k
+        sd.max_length, sd.expected_length, sd.skip_repeat = int(1.1 * (dis + 30) + len(rvc) + src_k), dis + len(rvc), 1
+        j = jobs[i]
+        j.raw_off, j.raw_len = b_off, len(between)
+        j.src_off, j.src_len = s_off + len(source) - src_k, src_k
+        j.dest_off, j.dest_len = t_off, len(target)
+        j.seed_first, j.n_seeds = 4 * i, 4
+        j.hash_kmer, j.max_leaves = ext_k, max_leaves
+        j.min_length = max(int(0.9 * (dis - 30) + src_k + ext_k), 0)
+        j.max_length, j.expected_length, j.min_sa_threshold = src_max, src_k + dis + len(target), 2
+    return "".join(parts).encode(), seeds, jobs
+
+
+def saipb_pair_results(pairs, res, freq, arena: bytes):
+    """What oracle.saipb_merge reports per pair: (code, merged, stats dict) from the results of saipb_pair_jobs' jobs."""
+    out = []
+    for i, (source, _, _, _) in enumerate(pairs):
+        r = res[i]
+        pb = arena[r.out_off: r.out_off + r.out_len].decode() if r.code == 1 else ""
+        merged = source + pb[17:] if pb else ""
+        out.append((r.code, merged, {"steps": r.steps, "max_leaves": r.max_used_leaves, "results": r.n_results,
+                                     "hash_entries": r.hash_entries, "source_freq": int(freq[4 * i + 2]),
+                                     "target_freq": int(freq[4 * i + 3])}, r.status))
+    return out
+
+
 class KernelStats(C.Structure):
     _fields_ = [
         ("launches", C.c_uint64),
@@ -118,7 +185,7 @@ class KernelStats(C.Structure):
     ]
 
 
-K_RANK, K_FIND, K_GRID, K_SEEDS, K_EXTEND, K_LF, K_DP, K_MSA, K_EXTEND_WIDE = range(9)
+K_RANK, K_FIND, K_GRID, K_SEEDS, K_EXTEND, K_LF, K_DP, K_MSA, K_EXTEND_WIDE, K_SAIPB = range(10)
 SEED_DTYPE = np.dtype([("start", "<i4"), ("len", "<i4"), ("max_freq", "<i4"), ("repeat", "<i4"), ("start_k", "<i4"),
                        ("end_k", "<i4"), ("start_freq", "<i4"), ("end_freq", "<i4")])
 BWT, RBWT = 0, 1
@@ -203,6 +270,8 @@ class Lrsc:
                                         C.c_uint64, C.POINTER(C.c_uint64)]
         L.lrsc_correct_reads.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64,
                                          C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.lrsc_saipb_merge.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         L.lrsc_ctx_get_params.argtypes = [C.c_void_p, C.POINTER(Params)]
         L.lrsc_lf_walk.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                    C.c_void_p]
@@ -460,6 +529,30 @@ class Ctx:
             break
         raw = arena.raw
         return [(r.code, raw[r.out_off: r.out_off + r.out_len].decode() if r.code > 0 else "", r.steps) for r in res]
+
+    def saipb_merge(self, seq: bytes, seeds, jobs, arena_cap: int | None = None):
+        """lrsc_saipb_merge -> (results, seed_freq uint64[n_seeds], arena bytes)."""
+        n_seeds, n_jobs = len(seeds), len(jobs)
+        res = (SaipbResult * max(n_jobs, 1))()
+        freq = np.zeros(max(n_seeds, 1), dtype=np.uint64)
+        cap = arena_cap if arena_cap is not None else max(1 << 16, 2 * len(seq) + 4096)
+        used = C.c_uint64()
+        while True:
+            arena = C.create_string_buffer(max(cap, 1))
+            st = self.api.lib.lrsc_saipb_merge(self.h, seq, len(seq), seeds, n_seeds, jobs, n_jobs, res, _ptr(freq), arena, cap, C.byref(used))
+            if st == -6 and used.value > cap and arena_cap is None:
+                cap = int(used.value)
+                continue
+            self.last_arena_used = int(used.value)
+            self.api.check(st, "lrsc_saipb_merge")
+            break
+        return res, freq, arena.raw[: used.value]
+
+    def saipb_merge_pairs(self, pairs, max_leaves: int = 32):
+        """pairs of (source, between, target, dis) by the call-site recipe -> [(code, merged, stats, status)] (saipb_pair_results)."""
+        seq, seeds, jobs = saipb_pair_jobs(pairs, max_leaves)
+        res, freq, arena = self.saipb_merge(seq, seeds, jobs)
+        return saipb_pair_results(pairs, res, freq, arena)
 
     def correct_reads(self, bases: np.ndarray, off: np.ndarray):
         """The whole per-read path.  -> (results: list[ReadResult], pieces: list[list[str]])."""

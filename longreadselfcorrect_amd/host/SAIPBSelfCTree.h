@@ -88,4 +88,42 @@ private:
     size_t m_hashKmerSize = 0;            // the small k-mer size of the collected k-mers (keys carry no length)
 };
 
+// The reference's (commented-out) call site as records of the batched device entry lrsc_saipb_merge: fills seeds[0..4) and job for one
+// (source, between, target, dis), exactly as tests/host_tools/saipb_driver.cpp drives the class above -- three source 17-mers at
+// 2x, 3x and 1.5x 17 from the source's end, then the reverse-complemented target with its expectedLength; extension k-mer 15; length
+// window 1.1 / 0.9 of the gap with an offset of 30.  The four strings are appended to `seq` (source, between, target, revcomp target);
+// seed_first = the index of seeds[0] in the caller's seed list.  source needs >= 51 bases, target >= 17.
+inline void saipbPairJob(const std::string& source, const std::string& between, const std::string& target, int dis, uint32_t maxLeaves,
+                         uint32_t seed_first, std::string& seq, lrsc_saipb_seed seeds[4], lrsc_saipb_job& job)
+{
+    const double maxRatio = 1.1, minRatio = 0.9;
+    const int minOffSet = 30;
+    const size_t extendKmerSize = 15, srcKmerSize = 17;
+    std::string rvcTarget(target.rbegin(), target.rend());
+    for(char& c : rvcTarget) c = c == 'A' ? 'T' : c == 'C' ? 'G' : c == 'G' ? 'C' : 'A';
+    const uint64_t sOff = seq.size(), bOff = sOff + source.size(), tOff = bOff + between.size(), rOff = tOff + target.size();
+    seq += source; seq += between; seq += target; seq += rvcTarget;
+    const size_t srcMaxLength = (size_t)(maxRatio * (dis + minOffSet) + srcKmerSize + extendKmerSize);
+    const size_t back[3] = {srcKmerSize * 2, srcKmerSize * 3, (size_t)(srcKmerSize * 1.5)};
+    for(int q = 0; q < 3; ++q) {
+        lrsc_saipb_seed& sd = seeds[q];
+        sd.seq_off = sOff + source.size() - back[q]; sd.len = (uint32_t)srcKmerSize; sd.large_kmer = (uint32_t)srcKmerSize;
+        sd.max_length = (uint32_t)srcMaxLength; sd.expected_length = -1; sd.skip_repeat = 1; sd.pad = 0;
+    }
+    lrsc_saipb_seed& td = seeds[3];
+    td.seq_off = rOff; td.len = (uint32_t)rvcTarget.size(); td.large_kmer = (uint32_t)srcKmerSize;
+    td.max_length = (uint32_t)(int)(maxRatio * (dis + minOffSet) + rvcTarget.length() + srcKmerSize);
+    td.expected_length = (int32_t)((size_t)dis + rvcTarget.length()); td.skip_repeat = 1; td.pad = 0;
+    int srcMinLength = (int)(minRatio * (dis - minOffSet) + srcKmerSize + extendKmerSize);
+    if(srcMinLength < 0) srcMinLength = 0;
+    job.raw_off = bOff; job.raw_len = (uint32_t)between.size();
+    job.src_off = sOff + source.size() - srcKmerSize; job.src_len = (uint32_t)srcKmerSize;
+    job.dest_off = tOff; job.dest_len = (uint32_t)target.size();
+    job.seed_first = seed_first; job.n_seeds = 4;
+    job.hash_kmer = (uint32_t)extendKmerSize; job.max_leaves = maxLeaves;
+    job.min_length = (uint32_t)srcMinLength; job.max_length = (uint32_t)srcMaxLength;
+    job.expected_length = (uint32_t)(srcKmerSize + (size_t)dis + target.length());
+    job.min_sa_threshold = 2; job.pad = 0;
+}
+
 } // namespace stride
