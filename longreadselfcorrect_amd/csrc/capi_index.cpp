@@ -1,0 +1,222 @@
+// capi_index.cpp -- the index object (open / from units / upload with its k-mer tables / close) and the device BWT build and
+// its file writer.
+#include <thread>
+
+#include "capi_internal.h"
+
+using namespace lrsc;
+
+static int index_from_units_impl(const uint8_t* u0, uint64_t n0, const uint8_t* u1, uint64_t n1,
+                                 uint64_t num_strings, uint64_t num_symbols, lrsc_index** out)
+{
+    lrsc_index* idx = new(std::nothrow) lrsc_index();
+    if(!idx) return fail(LRSC_ERR_NOMEM, "lrsc_index");
+    idx->num_strings = num_strings;
+    idx->num_symbols = num_symbols;
+    // Block64 (64-bit counters, 128 symbols per block) from 2^31 symbols per strand; LRSC_FORCE_WIDE=1 selects it for any
+    // index so that the wide code path can be tested on small data
+    idx->wide = num_symbols >= (1ull << 31) || std::getenv("LRSC_FORCE_WIDE") != nullptr;
+    int st[2] = {LRSC_OK, LRSC_OK};
+    std::string err[2];
+    const uint8_t* us[2] = {u0, u1};
+    const uint64_t ns[2] = {n0, n1};
+    // the two strands are independent: build them on two host threads
+    std::thread t([&]() { st[1] = build_strand_image(us[1], ns[1], num_symbols, idx->wide, idx->image[1], err[1]); });
+    st[0] = build_strand_image(us[0], ns[0], num_symbols, idx->wide, idx->image[0], err[0]);
+    t.join();
+    for(int s = 0; s < 2; ++s)
+        if(st[s] != LRSC_OK) { const int r = fail(st[s], err[s]); delete idx; return r; }
+    if(idx->image[0].dollars.size() != num_strings || idx->image[1].dollars.size() != num_strings) {
+        delete idx;
+        return fail(LRSC_ERR_FORMAT, "number of '$' rows differs from the number of strings in the header");
+    }
+    *out = idx;
+    return LRSC_OK;
+}
+
+extern "C" int lrsc_index_from_units(const uint8_t* bwt_units, uint64_t n_bwt_units, const uint8_t* rbwt_units,
+                                     uint64_t n_rbwt_units, uint64_t num_strings, uint64_t num_symbols,
+                                     lrsc_index** out)
+{
+    if(!bwt_units || !rbwt_units || !out || num_symbols == 0) return fail(LRSC_ERR_ARG, "null/empty index input");
+    return index_from_units_impl(bwt_units, n_bwt_units, rbwt_units, n_rbwt_units, num_strings, num_symbols, out);
+}
+
+extern "C" int lrsc_index_open(const char* bwt_path, const char* rbwt_path, lrsc_index** out)
+{
+    if(!bwt_path || !rbwt_path || !out) return fail(LRSC_ERR_ARG, "null path");
+    std::vector<uint8_t> u[2];
+    uint64_t nstr[2] = {0, 0}, nsym[2] = {0, 0};
+    std::string err;
+    int st = read_bwt_file(bwt_path, u[0], nstr[0], nsym[0], err);
+    if(st != LRSC_OK) return fail(st, err);
+    st = read_bwt_file(rbwt_path, u[1], nstr[1], nsym[1], err);
+    if(st != LRSC_OK) return fail(st, err);
+    if(nstr[0] != nstr[1] || nsym[0] != nsym[1]) return fail(LRSC_ERR_FORMAT, ".bwt and .rbwt disagree on strings/symbols");
+    return index_from_units_impl(u[0].data(), u[0].size(), u[1].data(), u[1].size(), nstr[0], nsym[0], out);
+}
+
+extern "C" int lrsc_index_info_get(const lrsc_index* idx, lrsc_index_info* out)
+{
+    if(!idx || !out) return fail(LRSC_ERR_ARG, "null");
+    std::memset(out, 0, sizeof(*out));
+    out->num_strings = idx->num_strings;
+    out->num_symbols = idx->num_symbols;
+    for(int s = 0; s < 2; ++s) {
+        out->num_runs[s] = idx->image[s].n_runs;
+        for(int c = 0; c < 5; ++c) out->pred_count[s][c] = idx->image[s].pred[c];
+        out->device_bytes += idx->image[s].blocks.size() + idx->image[s].dollars.size() * 8 + idx->image[s].dollar_dir.size() * 4;
+    }
+    out->block_bytes = 64;
+    out->block_symbols = idx->wide ? Block64::kSyms : Block32::kSyms;
+    return LRSC_OK;
+}
+
+extern "C" int lrsc_index_upload(lrsc_index* idx, int device)
+{
+    if(!idx) return fail(LRSC_ERR_ARG, "null index");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    if(idx->copies.count(device)) return LRSC_OK;
+    HIP_TRY(hipSetDevice(device));
+    DeviceCopy dc;
+    dc.dev.wide = idx->wide ? 1u : 0u;
+    for(int s = 0; s < 2; ++s) {
+        const StrandImage& im = idx->image[s];
+        HIP_TRY(hipMalloc(&dc.blocks[s], im.blocks.size()));
+        HIP_TRY(hipMemcpy(dc.blocks[s], im.blocks.data(), im.blocks.size(), hipMemcpyHostToDevice));
+        const size_t db = std::max<size_t>(im.dollars.size(), 1) * sizeof(uint64_t);
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&dc.dollars[s]), db));
+        if(!im.dollars.empty())
+            HIP_TRY(hipMemcpy(dc.dollars[s], im.dollars.data(), im.dollars.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&dc.dollar_dir[s]), im.dollar_dir.size() * sizeof(uint32_t)));
+        HIP_TRY(hipMemcpy(dc.dollar_dir[s], im.dollar_dir.data(), im.dollar_dir.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        FmStrand& fs = dc.dev.strand[s];
+        fs.blocks = dc.blocks[s];
+        fs.dollars = dc.dollars[s];
+        fs.dollar_dir = dc.dollar_dir[s];
+        fs.dollar_group_syms = (uint64_t)(idx->wide ? Block64::kSyms : Block32::kSyms) << kDollarDirShift;
+        fs.n_dollars = im.dollars.size();
+        fs.n_symbols = im.n_symbols;
+        fs.n_blocks = im.n_blocks;
+        for(int c = 0; c < 5; ++c) fs.pred[c] = im.pred[c];
+    }
+    // k-mer interval tables (narrow indexes): sizes 5 and 9 (the walk's 5-mer / idmer look-ups), T = floor(log4 N) clamped
+    // to [9, 13] -- up to there practically every k-mer occurs in the index -- and T + 2, where most chance matches have
+    // died (16 bytes x 4^k: 1.07 GB at 13, 17.2 GB at 15, taken only if it fits a quarter of the free HBM).
+    // LRSC_KTAB_K overrides T (0 disables all tables), LRSC_KTAB_K2 the fourth size (0 disables it).
+    {
+        const size_t entry_bytes = idx->wide ? 32 : 16;          // 4 x u64 for Block64 indexes
+        int T = 0;
+        for(uint64_t n = idx->num_symbols; n >= 4; n >>= 2) ++T;
+        T = std::max(9, std::min(13, T));
+        if(const char* e = std::getenv("LRSC_KTAB_K")) T = std::atoi(e);
+        int T2 = T > 0 ? std::min(15, T + 2) : 0;
+        if(const char* e = std::getenv("LRSC_KTAB_K2")) T2 = std::atoi(e);
+        // LRSC_KTAB_K3 (experimental, default off): a fifth table of T + 3 (16-mers: 69 GB)
+        int T3 = 0;
+        if(const char* e = std::getenv("LRSC_KTAB_K3")) T3 = std::atoi(e);
+        uint32_t want[5] = {5, 9, (uint32_t)T, (uint32_t)T2, (uint32_t)T3};
+        uint32_t ks[5] = {0, 0, 0, 0, 0};
+        uint32_t n_t = 0;
+        for(int i = 0; i < 5 && T > 0; ++i) {
+            if(want[i] == 0 || want[i] > 16 || (n_t > 0 && want[i] <= ks[n_t - 1])) continue;
+            const size_t bytes = entry_bytes << (2 * want[i]);
+            if(i >= 3) {
+                size_t free_b = 0, total_b = 0;
+                HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+                if(bytes > free_b / (i == 3 ? 4 : 3)) continue;
+            }
+            HIP_TRY(hipMalloc(&dc.ktab[n_t], bytes));
+            // each table starts from the previous (smaller) one; dc.dev.ktab[].k stays 0 until all are built so that the
+            // builder's own walk_step never consults a table
+            hipError_t e2 = launch_ktab_build(dc.dev, want[i], dc.ktab[n_t], n_t ? ks[n_t - 1] : 0, n_t ? dc.ktab[n_t - 1] : nullptr, nullptr);
+            if(e2 != hipSuccess) return hip_fail(e2, "ktab build");
+            dc.dev.ktab[n_t].entries = dc.ktab[n_t];
+            dc.dev.ktab[n_t].k = 0;
+            ks[n_t] = want[i];
+            ++n_t;
+        }
+        HIP_TRY(hipDeviceSynchronize());
+        for(uint32_t i = 0; i < n_t; ++i) dc.dev.ktab[i].k = ks[i];
+    }
+    idx->copies[device] = dc;
+    return LRSC_OK;
+}
+
+extern "C" void lrsc_index_close(lrsc_index* idx)
+{
+    if(!idx) return;
+    for(auto& kv : idx->copies) {
+        if(hipSetDevice(kv.first) != hipSuccess) continue;
+        for(int s = 0; s < 2; ++s) {
+            if(kv.second.blocks[s]) (void)hipFree(kv.second.blocks[s]);
+            if(kv.second.dollars[s]) (void)hipFree(kv.second.dollars[s]);
+            if(kv.second.dollar_dir[s]) (void)hipFree(kv.second.dollar_dir[s]);
+        }
+        for(int t = 0; t < 5; ++t) if(kv.second.ktab[t]) (void)hipFree(kv.second.ktab[t]);
+    }
+    delete idx;
+}
+
+// ---------------------------------------------------------------------------------------
+// index construction
+// ---------------------------------------------------------------------------------------
+namespace lrsc {
+int build_bwt_device(const char* reads, const uint64_t* off, uint32_t n_reads, int reverse_reads, int device,
+                     std::vector<uint8_t>& bwt_out, uint32_t* rounds_out, std::string& err);
+}
+
+extern "C" int lrsc_build_bwt(const char* reads, const uint64_t* read_off, uint32_t n_reads, int reverse_reads,
+                              int device, uint8_t** units_out, uint64_t* n_units_out)
+{
+    if(!reads || !units_out || !n_units_out || n_reads == 0) return fail(LRSC_ERR_ARG, "null / empty read set");
+    int st = check_offsets(read_off, n_reads);
+    if(st != LRSC_OK) return st;
+    std::vector<uint8_t> bwt;
+    std::string err;
+    st = build_bwt_device(reads, read_off, n_reads, reverse_reads, device, bwt, nullptr, err);
+    if(st != LRSC_OK) return fail(st, err);
+    // RL-encode as BWTWriterBinary::writeBWChar does: same symbol and run < 31 extends the run
+    uint64_t n_units = 0;
+    {
+        uint8_t prev = 0xFF; unsigned run = 0;
+        for(uint8_t c : bwt) {
+            if(c == prev && run < 31) ++run;
+            else { ++n_units; prev = c; run = 1; }
+        }
+    }
+    uint8_t* units = static_cast<uint8_t*>(std::malloc(n_units ? n_units : 1));
+    if(!units) return fail(LRSC_ERR_NOMEM, "RL units");
+    {
+        uint64_t u = 0; uint8_t prev = 0xFF; unsigned run = 0;
+        for(uint8_t c : bwt) {
+            if(c == prev && run < 31) { ++run; units[u - 1] = (uint8_t)((c << 5) | run); }
+            else { prev = c; run = 1; units[u++] = (uint8_t)((c << 5) | 1); }
+        }
+    }
+    *units_out = units;
+    *n_units_out = n_units;
+    return LRSC_OK;
+}
+
+extern "C" void lrsc_buffer_free(void* p) { std::free(p); }
+
+extern "C" int lrsc_write_bwt_file(const char* path, const uint8_t* units, uint64_t n_units, uint64_t num_strings,
+                                   uint64_t num_symbols)
+{
+    if(!path || (!units && n_units)) return fail(LRSC_ERR_ARG, "null");
+    std::FILE* f = std::fopen(path, "wb");
+    if(!f) return fail(LRSC_ERR_IO, std::string("cannot open ") + path);
+    uint8_t hdr[30];
+    const uint16_t magic = 0xCACA;
+    const int32_t flag = 0;   // BWF_NOFMI
+    std::memcpy(hdr, &magic, 2);
+    std::memcpy(hdr + 2, &num_strings, 8);
+    std::memcpy(hdr + 10, &num_symbols, 8);
+    std::memcpy(hdr + 18, &n_units, 8);
+    std::memcpy(hdr + 26, &flag, 4);
+    bool ok = std::fwrite(hdr, 1, 30, f) == 30;
+    ok = ok && std::fwrite(units, 1, n_units, f) == n_units;
+    ok = (std::fclose(f) == 0) && ok;
+    return ok ? LRSC_OK : fail(LRSC_ERR_IO, std::string("short write to ") + path);
+}

@@ -1,4 +1,4 @@
-// saipb.h -- what the host side (capi.cpp) and the kernels (saipb.hip, saipb_device.h) share about the hash-guided seed-pair merge:
+// saipb.h -- what the host side (capi_saipb.cpp) and the kernels (saipb.hip, saipb_device.h) share about the hash-guided seed-pair merge:
 // the job / seed records, the per-job workspace layout and the planner that sizes it from the seeds' intervals.
 #pragma once
 #include <stdint.h>

@@ -196,6 +196,21 @@ struct WpArgs {
 
 constexpr uint32_t kWpPathwSmall = 64, kWpPathwMid = 256;
 
+// Host side: word indices of the flow's small device scratch, the counters and queue heads the WpArgs pointers above name.  All
+// kWpSmallWords are zeroed at the start of every round.
+enum WpSmall : uint32_t {
+    kWpSmallPlanStats = 0,        // [0, 4): WpArgs::plan_stats
+    kWpSmallQueue = 4,            // WpArgs::queue outside the extension launches
+    kWpSmallDpItems = 5,          // WpArgs::n_dp_items
+    kWpSmallReqOut = 6,           // WpArgs::n_req_out
+    kWpSmallExtQueue = 8,         // queue of an extension launch on the ctx stream ...
+    kWpSmallSideQueue = 9,        // ... and of the long-gap walks' side launch
+    kWpSmallSideDpItems = 12,     // n_dp_items of the side launch
+    kWpSmallWideQueue = 13,       // queue of the wide (escalated) launch
+    kWpSmallWideCount = 14,       // walks collected for it
+    kWpSmallWords = 16
+};
+
 // bounds of every walk a read can be asked for (initCorrect's two loops, PacBioSelfCorrectionProcess.cpp:78-157): the source always
 // ends where seed it-1 ends and the target is seed it + next, next < nextTarget
 hipError_t launch_wp_bounds(const WpArgs& a, ReadPlan* plan, hipStream_t stream);

@@ -31,7 +31,7 @@
 namespace lrsc {
 
 #ifndef LRSC_WP_EXTEND_OCC
-#define LRSC_WP_EXTEND_OCC 2          // wavefronts per SIMD the extension kernel is compiled for (capi.cpp sizes its lanes to match)
+#define LRSC_WP_EXTEND_OCC 2          // wavefronts per SIMD the extension kernel is compiled for (capi_core.cpp sizes LRSC_WP_LANES to match)
 #endif
 
 // ---------------------------------------------------------------------------------------

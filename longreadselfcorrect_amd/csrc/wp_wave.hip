@@ -24,7 +24,7 @@
 namespace lrsc {
 
 #ifndef LRSC_WP_EXTEND_OCC
-#define LRSC_WP_EXTEND_OCC 2          // wavefronts per SIMD, as wp_extend_kernel (capi.cpp sizes the launches for that)
+#define LRSC_WP_EXTEND_OCC 2          // wavefronts per SIMD, as wp_extend_kernel (capi_core.cpp sizes the launches for that)
 #endif
 
 namespace {
