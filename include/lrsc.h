@@ -69,7 +69,7 @@ typedef struct lrsc_rank_query {
 typedef struct lrsc_index_info {
     uint64_t num_strings;        /* reads in the index                        */
     uint64_t num_symbols;        /* BWT length per strand (bases + num_strings) */
-    uint64_t num_runs[2];        /* RL units on disk (.bwt, .rbwt)              */
+    uint64_t num_runs[2];        /* RL units on disk (.bwt, .rbwt); 0 for an index made by lrsc_index_build */
     uint64_t pred_count[2][5];   /* C[$ACGT] per strand                         */
     uint32_t block_bytes;        /* bytes of one device rank block              */
     uint32_t block_symbols;      /* BWT symbols covered by one rank block       */
@@ -127,6 +127,10 @@ void lrsc_index_close(lrsc_index* idx);
 int lrsc_build_bwt(const char* reads, const uint64_t* read_off, uint32_t n_reads, int reverse_reads, int device,
                    uint8_t** units_out, uint64_t* n_units_out);
 void lrsc_buffer_free(void* p);
+/* Both strands' FM-index of the reads, built and packed on `device`; no files.  On return the index is resident on
+ * `device` (lrsc_index_upload(idx, device) is a no-op) with its k-mer tables, and carries a host image, so
+ * lrsc_index_upload to any other device works as for an opened index.  Same read checks and messages as lrsc_build_bwt. */
+int lrsc_index_build(const char* reads, const uint64_t* read_off, uint32_t n_reads, int device, lrsc_index** out);
 /* 30-byte header + units, the reference's binary .bwt/.rbwt format (BWTWriterBinary.cpp:28-46,82-93). */
 int lrsc_write_bwt_file(const char* path, const uint8_t* units, uint64_t n_units, uint64_t num_strings,
                         uint64_t num_symbols);

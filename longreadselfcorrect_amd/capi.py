@@ -233,6 +233,7 @@ class Lrsc:
         L.lrsc_build_bwt.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_void_p),
                                      C.POINTER(C.c_uint64)]
         L.lrsc_buffer_free.argtypes = [C.c_void_p]
+        L.lrsc_index_build.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
         L.lrsc_buffer_free.restype = None
         L.lrsc_write_bwt_file.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64]
         L.lrsc_params_default.argtypes = [C.c_int, C.c_int, C.POINTER(Params)]
@@ -349,6 +350,14 @@ class Lrsc:
         units = np.ascontiguousarray(units, dtype=np.uint8)
         self.check(self.lib.lrsc_write_bwt_file(str(path).encode(), _ptr(units), units.size, num_strings, num_symbols),
                    "lrsc_write_bwt_file")
+
+    def index_build(self, bases: np.ndarray, off: np.ndarray, device: int = 0) -> "Index":
+        """Both strands' index of the reads, sorted and packed on `device` and resident there; no files."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        h = C.c_void_p()
+        self.check(self.lib.lrsc_index_build(_ptr(bases), _ptr(off), off.size - 1, device, C.byref(h)), "lrsc_index_build")
+        return Index(self, h)
 
     # ---- index / ctx ------------------------------------------------------------------------
     def index_open(self, bwt_path: str, rbwt_path: str) -> "Index":

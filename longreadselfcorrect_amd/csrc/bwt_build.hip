@@ -228,6 +228,11 @@ struct Dev {
     {
         for(size_t i = 0; i < ptrs.size(); ++i) if(ptrs[i] == p) { (void)hipFree(p); ptrs.erase(ptrs.begin() + (long)i); return; }
     }
+    // hand p over to the caller: it outlives this object
+    void keep(void* p)
+    {
+        for(size_t i = 0; i < ptrs.size(); ++i) if(ptrs[i] == p) { ptrs.erase(ptrs.begin() + (long)i); return; }
+    }
 };
 
 static inline unsigned nblk(uint64_t n) { return (unsigned)((n + 255) / 256); }
@@ -422,12 +427,13 @@ static int build_grouped(Dev& d, const uint8_t* d_T, uint64_t N, uint64_t limit,
     return LRSC_OK;
 }
 
-// Builds the BWT of the read set (or of the reversed reads) on `device`; bwt_out receives N codes 0..4 ($ACGT),
-// N = total bases + n_reads.  Up to LRSC_BWT_JOB suffixes (default 2^30) are sorted per job: a read set below that is one job over
+// Builds the BWT of the read set (or of the reversed reads) on `device` and leaves it there: *d_bwt_out receives N codes 0..4
+// ($ACGT), N = total bases + n_reads, in memory that is the caller's to hipFree; the text and the sort workspace are released
+// on return.  Up to LRSC_BWT_JOB suffixes (default 2^30) are sorted per job: a read set below that is one job over
 // all positions; a larger one is cut into groups of leading-symbol classes that are sorted one after the other (positions
 // become 64-bit from 2^32 symbols on).  LRSC_BWT_WIDE_POS=1 forces 64-bit positions (tests).
-int build_bwt_device(const char* reads, const uint64_t* off, uint32_t n_reads, int reverse_reads, int device,
-                     std::vector<uint8_t>& bwt_out, uint32_t* rounds_out, std::string& err)
+int build_bwt_resident(const char* reads, const uint64_t* off, uint32_t n_reads, int reverse_reads, int device,
+                       uint8_t** d_bwt_out, uint32_t* rounds_out, std::string& err)
 {
     const uint64_t total = off[n_reads];
     const uint64_t N = total + n_reads;
@@ -479,9 +485,25 @@ int build_bwt_device(const char* reads, const uint64_t* off, uint32_t n_reads, i
     if(std::getenv("LRSC_BWT_PROFILE"))
         std::fprintf(stderr, "[lrsc] BWT of %llu symbols: %u job(s), %u refinement rounds, %d-bit positions\n", (unsigned long long)N, n_groups,
                      rounds, wide_pos ? 64 : 32);
-    bwt_out.resize(N);
-    BB_TRY(hipMemcpy(bwt_out.data(), d_bwt, N, hipMemcpyDeviceToHost));
+    BB_TRY(hipDeviceSynchronize());
+    d.keep(d_bwt);
+    *d_bwt_out = d_bwt;
     if(rounds_out) *rounds_out = rounds;
+    return LRSC_OK;
+}
+
+// The same, copied to the host at one byte per symbol.
+int build_bwt_device(const char* reads, const uint64_t* off, uint32_t n_reads, int reverse_reads, int device,
+                     std::vector<uint8_t>& bwt_out, uint32_t* rounds_out, std::string& err)
+{
+    uint8_t* d_bwt = nullptr;
+    const int rc = build_bwt_resident(reads, off, n_reads, reverse_reads, device, &d_bwt, rounds_out, err);
+    if(rc != LRSC_OK) return rc;
+    const uint64_t N = off[n_reads] + n_reads;
+    bwt_out.resize(N);
+    const hipError_t e = hipMemcpy(bwt_out.data(), d_bwt, N, hipMemcpyDeviceToHost);
+    (void)hipFree(d_bwt);
+    if(e != hipSuccess) { err = std::string("copy of the BWT to the host: ") + hipGetErrorString(e); return LRSC_ERR_DEVICE; }
     return LRSC_OK;
 }
 

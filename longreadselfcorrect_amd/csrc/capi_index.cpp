@@ -1,8 +1,10 @@
-// capi_index.cpp -- the index object (open / from units / upload with its k-mer tables / close) and the device BWT build and
-// its file writer.
+// capi_index.cpp -- the index object (open / from units / build from reads / upload with its k-mer tables / close) and the
+// device BWT build and its file writer.
+#include <chrono>
 #include <thread>
 
 #include "capi_internal.h"
+#include "fm_pack.h"
 
 using namespace lrsc;
 
@@ -72,14 +74,20 @@ extern "C" int lrsc_index_info_get(const lrsc_index* idx, lrsc_index_info* out)
     return LRSC_OK;
 }
 
-extern "C" int lrsc_index_upload(lrsc_index* idx, int device)
+static void free_device_copy(DeviceCopy& dc)
 {
-    if(!idx) return fail(LRSC_ERR_ARG, "null index");
-    std::lock_guard<std::mutex> lock(idx->mu);
-    if(idx->copies.count(device)) return LRSC_OK;
-    HIP_TRY(hipSetDevice(device));
-    DeviceCopy dc;
-    dc.dev.wide = idx->wide ? 1u : 0u;
+    for(int s = 0; s < 2; ++s) {
+        if(dc.blocks[s]) (void)hipFree(dc.blocks[s]);
+        if(dc.dollars[s]) (void)hipFree(dc.dollars[s]);
+        if(dc.dollar_dir[s]) (void)hipFree(dc.dollar_dir[s]);
+        dc.blocks[s] = nullptr; dc.dollars[s] = nullptr; dc.dollar_dir[s] = nullptr;
+    }
+    for(int t = 0; t < 5; ++t) { if(dc.ktab[t]) (void)hipFree(dc.ktab[t]); dc.ktab[t] = nullptr; }
+}
+
+// first half of an upload: the host image of both strands -> the current device
+static int copy_image(const lrsc_index* idx, DeviceCopy& dc)
+{
     for(int s = 0; s < 2; ++s) {
         const StrandImage& im = idx->image[s];
         HIP_TRY(hipMalloc(&dc.blocks[s], im.blocks.size()));
@@ -90,6 +98,17 @@ extern "C" int lrsc_index_upload(lrsc_index* idx, int device)
             HIP_TRY(hipMemcpy(dc.dollars[s], im.dollars.data(), im.dollars.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
         HIP_TRY(hipMalloc(reinterpret_cast<void**>(&dc.dollar_dir[s]), im.dollar_dir.size() * sizeof(uint32_t)));
         HIP_TRY(hipMemcpy(dc.dollar_dir[s], im.dollar_dir.data(), im.dollar_dir.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    return LRSC_OK;
+}
+
+// second half: describe the image that dc holds on the current device (copied there, or packed there by lrsc_index_build),
+// build its k-mer tables and enter it as `device`'s copy.  The caller holds idx->mu and frees dc on failure.
+static int register_copy(lrsc_index* idx, int device, DeviceCopy& dc)
+{
+    dc.dev.wide = idx->wide ? 1u : 0u;
+    for(int s = 0; s < 2; ++s) {
+        const StrandImage& im = idx->image[s];
         FmStrand& fs = dc.dev.strand[s];
         fs.blocks = dc.blocks[s];
         fs.dollars = dc.dollars[s];
@@ -143,17 +162,25 @@ extern "C" int lrsc_index_upload(lrsc_index* idx, int device)
     return LRSC_OK;
 }
 
+extern "C" int lrsc_index_upload(lrsc_index* idx, int device)
+{
+    if(!idx) return fail(LRSC_ERR_ARG, "null index");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    if(idx->copies.count(device)) return LRSC_OK;
+    HIP_TRY(hipSetDevice(device));
+    DeviceCopy dc;
+    int st = copy_image(idx, dc);
+    if(st == LRSC_OK) st = register_copy(idx, device, dc);
+    if(st != LRSC_OK) free_device_copy(dc);
+    return st;
+}
+
 extern "C" void lrsc_index_close(lrsc_index* idx)
 {
     if(!idx) return;
     for(auto& kv : idx->copies) {
         if(hipSetDevice(kv.first) != hipSuccess) continue;
-        for(int s = 0; s < 2; ++s) {
-            if(kv.second.blocks[s]) (void)hipFree(kv.second.blocks[s]);
-            if(kv.second.dollars[s]) (void)hipFree(kv.second.dollars[s]);
-            if(kv.second.dollar_dir[s]) (void)hipFree(kv.second.dollar_dir[s]);
-        }
-        for(int t = 0; t < 5; ++t) if(kv.second.ktab[t]) (void)hipFree(kv.second.ktab[t]);
+        free_device_copy(kv.second);
     }
     delete idx;
 }
@@ -164,6 +191,8 @@ extern "C" void lrsc_index_close(lrsc_index* idx)
 namespace lrsc {
 int build_bwt_device(const char* reads, const uint64_t* off, uint32_t n_reads, int reverse_reads, int device,
                      std::vector<uint8_t>& bwt_out, uint32_t* rounds_out, std::string& err);
+int build_bwt_resident(const char* reads, const uint64_t* off, uint32_t n_reads, int reverse_reads, int device,
+                       uint8_t** d_bwt_out, uint32_t* rounds_out, std::string& err);
 }
 
 extern "C" int lrsc_build_bwt(const char* reads, const uint64_t* read_off, uint32_t n_reads, int reverse_reads,
@@ -200,6 +229,71 @@ extern "C" int lrsc_build_bwt(const char* reads, const uint64_t* read_off, uint3
 }
 
 extern "C" void lrsc_buffer_free(void* p) { std::free(p); }
+
+// One strand of lrsc_index_build: BWT on the device -> packed image on the device (dc.*[s]) -> host image by a copy of the
+// packed arrays (a third of a byte per symbol).  d_bwt is gone before the next strand starts.
+static int build_strand(const char* reads, const uint64_t* off, uint32_t n_reads, int s, int device, bool wide, StrandImage& im,
+                        DeviceCopy& dc, double ms[2], std::string& err)
+{
+    using clk = std::chrono::steady_clock;
+    const auto t0 = clk::now();
+    uint8_t* d_bwt = nullptr;
+    int st = build_bwt_resident(reads, off, n_reads, s, device, &d_bwt, nullptr, err);
+    if(st != LRSC_OK) return st;
+    const auto t1 = clk::now();
+    const uint64_t N = off[n_reads] + n_reads;
+    PackedStrand ps;
+    st = pack_strand_device(d_bwt, N, wide, ps, err);
+    (void)hipFree(d_bwt);
+    if(st != LRSC_OK) return st;
+    dc.blocks[s] = ps.blocks;
+    dc.dollars[s] = ps.dollars;
+    dc.dollar_dir[s] = ps.dollar_dir;
+    ms[0] += std::chrono::duration<double, std::milli>(t1 - t0).count();
+    ms[1] += std::chrono::duration<double, std::milli>(clk::now() - t1).count();
+    im.n_blocks = ps.n_blocks;
+    im.n_symbols = N;
+    im.n_runs = 0;
+    for(int c = 0; c < 5; ++c) im.pred[c] = ps.pred[c];
+    im.blocks.resize(ps.n_blocks * 64);
+    im.dollars.resize(ps.n_dollars);
+    im.dollar_dir.resize(ps.n_dir);
+    hipError_t e = hipMemcpy(im.blocks.data(), ps.blocks, im.blocks.size(), hipMemcpyDeviceToHost);
+    if(e == hipSuccess && ps.n_dollars) e = hipMemcpy(im.dollars.data(), ps.dollars, ps.n_dollars * sizeof(uint64_t), hipMemcpyDeviceToHost);
+    if(e == hipSuccess) e = hipMemcpy(im.dollar_dir.data(), ps.dollar_dir, ps.n_dir * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if(e != hipSuccess) { err = std::string("copy of the packed index to the host: ") + hipGetErrorString(e); return LRSC_ERR_DEVICE; }
+    return LRSC_OK;
+}
+
+extern "C" int lrsc_index_build(const char* reads, const uint64_t* read_off, uint32_t n_reads, int device, lrsc_index** out)
+{
+    if(!reads || !out || n_reads == 0) return fail(LRSC_ERR_ARG, "null / empty read set");
+    int st = check_offsets(read_off, n_reads);
+    if(st != LRSC_OK) return st;
+    lrsc_index* idx = new(std::nothrow) lrsc_index();
+    if(!idx) return fail(LRSC_ERR_NOMEM, "lrsc_index");
+    idx->num_strings = n_reads;
+    idx->num_symbols = read_off[n_reads] + n_reads;
+    idx->wide = idx->num_symbols >= (1ull << 31) || std::getenv("LRSC_FORCE_WIDE") != nullptr;   // as index_from_units_impl
+    DeviceCopy dc;
+    double ms[3] = {0., 0., 0.};
+    std::string err;
+    for(int s = 0; s < 2 && st == LRSC_OK; ++s) {
+        st = build_strand(reads, read_off, n_reads, s, device, idx->wide, idx->image[s], dc, ms, err);
+        if(st != LRSC_OK) st = fail(st, err);
+    }
+    if(st == LRSC_OK) {
+        const auto t0 = std::chrono::steady_clock::now();
+        std::lock_guard<std::mutex> lock(idx->mu);
+        st = register_copy(idx, device, dc);
+        ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    if(st != LRSC_OK) { free_device_copy(dc); delete idx; return st; }
+    if(std::getenv("LRSC_BWT_PROFILE"))
+        std::fprintf(stderr, "[lrsc] index build: bwt %.3f ms, pack %.3f ms, tables %.3f ms\n", ms[0], ms[1], ms[2]);
+    *out = idx;
+    return LRSC_OK;
+}
 
 extern "C" int lrsc_write_bwt_file(const char* path, const uint8_t* units, uint64_t n_units, uint64_t num_strings,
                                    uint64_t num_symbols)

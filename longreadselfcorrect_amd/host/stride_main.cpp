@@ -39,6 +39,7 @@ static const char* CORRECT_USAGE_MESSAGE =
     "\n"
     "      -t, --thread=NUM                 Use NUM threads for the computation (default: 1)\n"
     "      -p, --prefix=PREFIX              Use PREFIX for the names of the index files\n"
+    "      --build-index                    Index READSFILE in memory on the first device instead of loading PREFIX.bwt/.rbwt\n"
     "      -o, --output=DIR                 Output results in the directory\n"
     "      -b, --barcode=FILE               Barcode of raw reads\n"
     "\nPacBio correction parameters:\n"
@@ -75,10 +76,11 @@ static std::array<int, 3> offset = {{0, 0, 0}};
 static std::vector<int> devices(1, 0);
 static int workersPerDevice = 2;
 static size_t batch = 100000;
+static bool buildIndex = false;
 }
 
 static const char* shortopts = "t:p:o:b:c:e:k:u:r:n:l:i:s:g:m:v";
-enum { OPT_HELP = 1, OPT_VERSION, OPT_SPLIT, OPT_FIRST, OPT_DEBUGEXTEND, OPT_DEBUGSEED, OPT_ONLYSEED, OPT_NODP, OPT_DEVICES, OPT_BATCH, OPT_WORKERS };
+enum { OPT_HELP = 1, OPT_VERSION, OPT_SPLIT, OPT_FIRST, OPT_DEBUGEXTEND, OPT_DEBUGSEED, OPT_ONLYSEED, OPT_NODP, OPT_DEVICES, OPT_BATCH, OPT_WORKERS, OPT_BUILDINDEX };
 static const struct option longopts[] = {
     {"thread", required_argument, nullptr, 't'},       {"prefix", required_argument, nullptr, 'p'},
     {"output", required_argument, nullptr, 'o'},       {"barcode", required_argument, nullptr, 'b'},
@@ -93,6 +95,7 @@ static const struct option longopts[] = {
     {"debugseed", no_argument, nullptr, OPT_DEBUGSEED}, {"onlyseed", no_argument, nullptr, OPT_ONLYSEED},
     {"nodp", no_argument, nullptr, OPT_NODP},          {"devices", required_argument, nullptr, OPT_DEVICES},
     {"batch", required_argument, nullptr, OPT_BATCH},  {"workers-per-device", required_argument, nullptr, OPT_WORKERS},
+    {"build-index", no_argument, nullptr, OPT_BUILDINDEX},
     {nullptr, 0, nullptr, 0}};
 
 static void lrscOrDie(int st, const char* what)
@@ -141,13 +144,15 @@ static void parsePacBioSelfCorrectionOptions(int argc, char** argv)
             }
             case OPT_BATCH: arg >> opt::batch; break;
             case OPT_WORKERS: arg >> opt::workersPerDevice; break;
+            case OPT_BUILDINDEX: opt::buildIndex = true; break;
             default: die = true; break;
         }
     }
     if(argc - optind < 1) { std::cerr << SUBPROGRAM ": missing arguments\n"; die = true; }
     else if(argc - optind > 1) { std::cerr << SUBPROGRAM ": too many arguments\n"; die = true; }
     if(opt::thread <= 0) { std::cerr << SUBPROGRAM ": invalid number of threads: " << opt::thread << "\n"; die = true; }
-    if(opt::prefix.empty()) { std::cerr << SUBPROGRAM << ": no prefix\n"; die = true; }
+    if(opt::buildIndex && !opt::prefix.empty()) { std::cerr << SUBPROGRAM << ": --build-index reads no index files: give either it or -p\n"; die = true; }
+    if(opt::prefix.empty() && !opt::buildIndex) { std::cerr << SUBPROGRAM << ": no prefix\n"; die = true; }
     if(opt::directory.empty()) { std::cerr << SUBPROGRAM << ": no directory\n"; die = true; }
     else {
         opt::directory += "/";
@@ -175,15 +180,32 @@ static void parsePacBioSelfCorrectionOptions(int argc, char** argv)
     opt::readsFile = argv[optind++];
 }
 
+// every read of the file, concatenated: read i is bases[off[i], off[i + 1])
+static void loadReads(const std::string& path, std::string& bases, std::vector<uint64_t>& off)
+{
+    SeqReader reader(path);
+    SeqRecord r;
+    off.assign(1, 0);
+    while(reader.get(r)) { bases += r.seq; off.push_back(bases.size()); }
+}
+
 static int PacBioSelfCorrectionMain(int argc, char** argv)
 {
     parsePacBioSelfCorrectionOptions(argc, argv);
     // --debugextend is accepted and inert: in the reference its only consumer (the debugExtInfo FASTA dump) is commented out
     // (PacBioSelfCorrectionProcess.cpp:87-98).
     PacBioSelfCorrectionParameters ecParams;
-    std::cerr << "Loading BWT: " << opt::prefix + BWT_EXT << "\n" << "Loading RBWT: " << opt::prefix + RBWT_EXT << "\n";
     lrsc_index* idx = nullptr;
-    lrscOrDie(lrsc_index_open((opt::prefix + BWT_EXT).c_str(), (opt::prefix + RBWT_EXT).c_str(), &idx), "lrsc_index_open");
+    if(opt::buildIndex) {
+        std::cerr << "Building the index of " << opt::readsFile << " on device " << opt::devices[0] << "\n";
+        std::string bases;
+        std::vector<uint64_t> off;
+        loadReads(opt::readsFile, bases, off);
+        lrscOrDie(lrsc_index_build(bases.data(), off.data(), (uint32_t)(off.size() - 1), opt::devices[0], &idx), "lrsc_index_build");
+    } else {
+        std::cerr << "Loading BWT: " << opt::prefix + BWT_EXT << "\n" << "Loading RBWT: " << opt::prefix + RBWT_EXT << "\n";
+        lrscOrDie(lrsc_index_open((opt::prefix + BWT_EXT).c_str(), (opt::prefix + RBWT_EXT).c_str(), &idx), "lrsc_index_open");
+    }
     for(int d : opt::devices) lrscOrDie(lrsc_index_upload(idx, d), "lrsc_index_upload");
 
     lrsc_params p;
@@ -245,11 +267,9 @@ static int indexMain(int argc, char** argv)
     }
     if(reads.empty()) { std::cerr << "index: missing arguments\n"; return EXIT_FAILURE; }
     if(prefix.empty()) { prefix = reads.substr(reads.find_last_of('/') + 1); prefix = prefix.substr(0, prefix.find_last_of('.')); }
-    SeqReader reader(reads);
-    SeqRecord r;
     std::string bases;
-    std::vector<uint64_t> off(1, 0);
-    while(reader.get(r)) { bases += r.seq; off.push_back(bases.size()); }
+    std::vector<uint64_t> off;
+    loadReads(reads, bases, off);
     const uint32_t n = (uint32_t)(off.size() - 1);
     std::cout << "Building index for " << reads << " on the GPU\n";
     for(int rev = 0; rev < 2; ++rev) {
