@@ -134,6 +134,12 @@ int lrsc_index_build(const char* reads, const uint64_t* read_off, uint32_t n_rea
 /* 30-byte header + units, the reference's binary .bwt/.rbwt format (BWTWriterBinary.cpp:28-46,82-93). */
 int lrsc_write_bwt_file(const char* path, const uint8_t* units, uint64_t n_units, uint64_t num_strings,
                         uint64_t num_symbols);
+/* RL units of one strand's BWT (BWTWriterBinary::writeBWChar's rule), encoded on `device` from the index's resident copy there.
+ * *units_out is malloc'ed (lrsc_buffer_free).  Works on any index, built or opened, that has a copy on `device`
+ * (LRSC_ERR_DEVICE otherwise); the index itself is not modified. */
+int lrsc_index_units(lrsc_index* idx, int strand, int device, uint8_t** units_out, uint64_t* n_units_out);
+/* Both strands through lrsc_index_units and lrsc_write_bwt_file's header and layout. */
+int lrsc_index_write(lrsc_index* idx, int device, const char* bwt_path, const char* rbwt_path);
 
 /* ---- context ------------------------------------------------------------------------ */
 int lrsc_ctx_create(const lrsc_index* idx, const lrsc_params* params, int device, lrsc_ctx** out);

@@ -236,6 +236,8 @@ class Lrsc:
         L.lrsc_index_build.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
         L.lrsc_buffer_free.restype = None
         L.lrsc_write_bwt_file.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64]
+        L.lrsc_index_units.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        L.lrsc_index_write.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p]
         L.lrsc_params_default.argtypes = [C.c_int, C.c_int, C.POINTER(Params)]
         L.lrsc_ctx_create.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int, C.POINTER(C.c_void_p)]
         L.lrsc_ctx_destroy.argtypes = [C.c_void_p]
@@ -385,6 +387,20 @@ class Index:
 
     def upload(self, device: int = 0):
         self.api.check(self.api.lib.lrsc_index_upload(self.h, device), "lrsc_index_upload")
+
+    def units(self, strand: int, device: int = 0) -> np.ndarray:
+        """RL units (uint8) of one strand's BWT, encoded on `device` from the copy there: the .bwt (strand 0) or .rbwt payload."""
+        p = C.c_void_p()
+        n = C.c_uint64()
+        self.api.check(self.api.lib.lrsc_index_units(self.h, strand, device, C.byref(p), C.byref(n)), "lrsc_index_units")
+        try:
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(n.value,)).copy()
+        finally:
+            self.api.lib.lrsc_buffer_free(p)
+
+    def write(self, bwt_path, rbwt_path, device: int = 0):
+        """Both strands as the reference's .bwt/.rbwt files, from the copy on `device`."""
+        self.api.check(self.api.lib.lrsc_index_write(self.h, device, str(bwt_path).encode(), str(rbwt_path).encode()), "lrsc_index_write")
 
     def ctx(self, params: Params | None = None, device: int = 0) -> "Ctx":
         h = C.c_void_p()

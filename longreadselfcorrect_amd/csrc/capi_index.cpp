@@ -1,10 +1,11 @@
-// capi_index.cpp -- the index object (open / from units / build from reads / upload with its k-mer tables / close) and the
-// device BWT build and its file writer.
+// capi_index.cpp -- the index object (open / from units / build from reads / upload with its k-mer tables / close), the
+// device BWT build, the RL units of a resident copy and the file writer.
 #include <chrono>
 #include <thread>
 
 #include "capi_internal.h"
 #include "fm_pack.h"
+#include "fm_rle.h"
 
 using namespace lrsc;
 
@@ -195,14 +196,46 @@ int build_bwt_resident(const char* reads, const uint64_t* off, uint32_t n_reads,
                        uint8_t** d_bwt_out, uint32_t* rounds_out, std::string& err);
 }
 
+// device units -> a malloc'ed host copy; d_units is released either way
+static int units_to_host(uint8_t* d_units, uint64_t n_units, uint8_t** units_out, uint64_t* n_units_out)
+{
+    uint8_t* units = static_cast<uint8_t*>(std::malloc(n_units ? n_units : 1));
+    hipError_t e = hipSuccess;
+    if(units && n_units) e = hipMemcpy(units, d_units, n_units, hipMemcpyDeviceToHost);
+    if(d_units) (void)hipFree(d_units);
+    if(!units) return fail(LRSC_ERR_NOMEM, "RL units");
+    if(e != hipSuccess) { std::free(units); return hip_fail(e, "copy of the RL units to the host"); }
+    *units_out = units;
+    *n_units_out = n_units;
+    return LRSC_OK;
+}
+
 extern "C" int lrsc_build_bwt(const char* reads, const uint64_t* read_off, uint32_t n_reads, int reverse_reads,
                               int device, uint8_t** units_out, uint64_t* n_units_out)
 {
     if(!reads || !units_out || !n_units_out || n_reads == 0) return fail(LRSC_ERR_ARG, "null / empty read set");
     int st = check_offsets(read_off, n_reads);
     if(st != LRSC_OK) return st;
-    std::vector<uint8_t> bwt;
     std::string err;
+    const char* host_rle = std::getenv("LRSC_BWT_HOST_RLE");
+    if(!host_rle || std::atoi(host_rle) == 0) {
+        // RL-encode where the BWT lies (fm_rle.hip); only the units cross to the host
+        uint8_t* d_bwt = nullptr;
+        st = build_bwt_resident(reads, read_off, n_reads, reverse_reads, device, &d_bwt, nullptr, err);
+        if(st != LRSC_OK) return fail(st, err);
+        const auto t0 = std::chrono::steady_clock::now();
+        uint8_t* d_units = nullptr;
+        uint64_t n_units = 0;
+        st = rle_bwt_device(d_bwt, read_off[n_reads] + n_reads, &d_units, &n_units, err);
+        (void)hipFree(d_bwt);
+        if(st != LRSC_OK) return fail(st, err);
+        if(std::getenv("LRSC_BWT_PROFILE"))
+            std::fprintf(stderr, "[lrsc] RL encode on the device: %.3f ms, %llu units\n",
+                         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), (unsigned long long)n_units);
+        return units_to_host(d_units, n_units, units_out, n_units_out);
+    }
+    // LRSC_BWT_HOST_RLE=1: the BWT comes to the host at a byte per symbol and one thread encodes it (the encoder's A/B)
+    std::vector<uint8_t> bwt;
     st = build_bwt_device(reads, read_off, n_reads, reverse_reads, device, bwt, nullptr, err);
     if(st != LRSC_OK) return fail(st, err);
     // RL-encode as BWTWriterBinary::writeBWChar does: same symbol and run < 31 extends the run
@@ -292,6 +325,44 @@ extern "C" int lrsc_index_build(const char* reads, const uint64_t* read_off, uin
     if(std::getenv("LRSC_BWT_PROFILE"))
         std::fprintf(stderr, "[lrsc] index build: bwt %.3f ms, pack %.3f ms, tables %.3f ms\n", ms[0], ms[1], ms[2]);
     *out = idx;
+    return LRSC_OK;
+}
+
+extern "C" int lrsc_index_units(lrsc_index* idx, int strand, int device, uint8_t** units_out, uint64_t* n_units_out)
+{
+    if(!idx || !units_out || !n_units_out) return fail(LRSC_ERR_ARG, "null");
+    if(strand != LRSC_BWT && strand != LRSC_RBWT) return fail(LRSC_ERR_ARG, "strand must be LRSC_BWT or LRSC_RBWT");
+    FmStrand fs;
+    bool wide;
+    {
+        std::lock_guard<std::mutex> lock(idx->mu);
+        auto it = idx->copies.find(device);
+        if(it == idx->copies.end()) return fail(LRSC_ERR_DEVICE, "index not uploaded to this device (call lrsc_index_upload)");
+        fs = it->second.dev.strand[strand];
+        wide = idx->wide;
+    }
+    HIP_TRY(hipSetDevice(device));
+    uint8_t* d_units = nullptr;
+    uint64_t n_units = 0;
+    std::string err;
+    const int st = rle_strand_device(fs, wide, &d_units, &n_units, err);
+    if(st != LRSC_OK) return fail(st, err);
+    return units_to_host(d_units, n_units, units_out, n_units_out);
+}
+
+extern "C" int lrsc_index_write(lrsc_index* idx, int device, const char* bwt_path, const char* rbwt_path)
+{
+    if(!idx || !bwt_path || !rbwt_path) return fail(LRSC_ERR_ARG, "null");
+    const char* paths[2] = {bwt_path, rbwt_path};
+    for(int s = 0; s < 2; ++s) {
+        uint8_t* units = nullptr;
+        uint64_t n_units = 0;
+        int st = lrsc_index_units(idx, s, device, &units, &n_units);
+        if(st != LRSC_OK) return st;
+        st = lrsc_write_bwt_file(paths[s], units, n_units, idx->num_strings, idx->num_symbols);
+        std::free(units);
+        if(st != LRSC_OK) return st;
+    }
     return LRSC_OK;
 }
 

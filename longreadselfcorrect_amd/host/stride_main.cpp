@@ -40,6 +40,7 @@ static const char* CORRECT_USAGE_MESSAGE =
     "      -t, --thread=NUM                 Use NUM threads for the computation (default: 1)\n"
     "      -p, --prefix=PREFIX              Use PREFIX for the names of the index files\n"
     "      --build-index                    Index READSFILE in memory on the first device instead of loading PREFIX.bwt/.rbwt\n"
+    "      --save-index=PREFIX              With --build-index: write the built index to PREFIX.bwt/.rbwt/.sai/.rsai\n"
     "      -o, --output=DIR                 Output results in the directory\n"
     "      -b, --barcode=FILE               Barcode of raw reads\n"
     "\nPacBio correction parameters:\n"
@@ -67,7 +68,7 @@ static const char* CORRECT_USAGE_MESSAGE =
 
 namespace opt {
 static int thread = 1;
-static std::string prefix, directory, barcode, readsFile;
+static std::string prefix, directory, barcode, readsFile, saveIndex;
 static size_t PBcoverage = 90;
 static double ErrorRate = 0.15;
 static int startKmerLen = 19, nextTarget = 1, maxLeaves = 32, idmerLen = 9, minKmerLen = 13, genome = 10, mode = 1, verbose = 0;
@@ -80,7 +81,7 @@ static bool buildIndex = false;
 }
 
 static const char* shortopts = "t:p:o:b:c:e:k:u:r:n:l:i:s:g:m:v";
-enum { OPT_HELP = 1, OPT_VERSION, OPT_SPLIT, OPT_FIRST, OPT_DEBUGEXTEND, OPT_DEBUGSEED, OPT_ONLYSEED, OPT_NODP, OPT_DEVICES, OPT_BATCH, OPT_WORKERS, OPT_BUILDINDEX };
+enum { OPT_HELP = 1, OPT_VERSION, OPT_SPLIT, OPT_FIRST, OPT_DEBUGEXTEND, OPT_DEBUGSEED, OPT_ONLYSEED, OPT_NODP, OPT_DEVICES, OPT_BATCH, OPT_WORKERS, OPT_BUILDINDEX, OPT_SAVEINDEX };
 static const struct option longopts[] = {
     {"thread", required_argument, nullptr, 't'},       {"prefix", required_argument, nullptr, 'p'},
     {"output", required_argument, nullptr, 'o'},       {"barcode", required_argument, nullptr, 'b'},
@@ -95,7 +96,7 @@ static const struct option longopts[] = {
     {"debugseed", no_argument, nullptr, OPT_DEBUGSEED}, {"onlyseed", no_argument, nullptr, OPT_ONLYSEED},
     {"nodp", no_argument, nullptr, OPT_NODP},          {"devices", required_argument, nullptr, OPT_DEVICES},
     {"batch", required_argument, nullptr, OPT_BATCH},  {"workers-per-device", required_argument, nullptr, OPT_WORKERS},
-    {"build-index", no_argument, nullptr, OPT_BUILDINDEX},
+    {"build-index", no_argument, nullptr, OPT_BUILDINDEX}, {"save-index", required_argument, nullptr, OPT_SAVEINDEX},
     {nullptr, 0, nullptr, 0}};
 
 static void lrscOrDie(int st, const char* what)
@@ -145,6 +146,7 @@ static void parsePacBioSelfCorrectionOptions(int argc, char** argv)
             case OPT_BATCH: arg >> opt::batch; break;
             case OPT_WORKERS: arg >> opt::workersPerDevice; break;
             case OPT_BUILDINDEX: opt::buildIndex = true; break;
+            case OPT_SAVEINDEX: arg >> opt::saveIndex; break;
             default: die = true; break;
         }
     }
@@ -152,6 +154,7 @@ static void parsePacBioSelfCorrectionOptions(int argc, char** argv)
     else if(argc - optind > 1) { std::cerr << SUBPROGRAM ": too many arguments\n"; die = true; }
     if(opt::thread <= 0) { std::cerr << SUBPROGRAM ": invalid number of threads: " << opt::thread << "\n"; die = true; }
     if(opt::buildIndex && !opt::prefix.empty()) { std::cerr << SUBPROGRAM << ": --build-index reads no index files: give either it or -p\n"; die = true; }
+    if(!opt::saveIndex.empty() && !opt::buildIndex) { std::cerr << SUBPROGRAM << ": --save-index writes the index that --build-index builds: give both\n"; die = true; }
     if(opt::prefix.empty() && !opt::buildIndex) { std::cerr << SUBPROGRAM << ": no prefix\n"; die = true; }
     if(opt::directory.empty()) { std::cerr << SUBPROGRAM << ": no directory\n"; die = true; }
     else {
@@ -189,6 +192,34 @@ static void loadReads(const std::string& path, std::string& bases, std::vector<u
     while(reader.get(r)) { bases += r.seq; off.push_back(bases.size()); }
 }
 
+// .sai / .rsai: lexicographic rank -> read index (SampledSuffixArray::buildLexicoIndex + writeLexicoIndex,
+// SuffixTools/SampledSuffixArray.cpp:158-190,248-258; text format of SAWriter.cpp:32-54).  The reference LF-walks each
+// read back to its '$' row; that row's rank among the '$' rows is the rank of the read among all reads compared as
+// strings ('$' < A < C < G < T, so a proper prefix sorts first) with equal reads in input order (sentinel order
+// MR_SO_IO) -- computed directly here.  `pbcorrect` only needs the file to exist.
+static bool writeLexicoIndex(const std::string& path, const std::string& bases, const std::vector<uint64_t>& off, bool rev)
+{
+    const uint32_t n = (uint32_t)(off.size() - 1);
+    std::vector<uint32_t> order(n);
+    for(uint32_t i = 0; i < n; ++i) order[i] = i;
+    const char* B = bases.data();
+    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+        const uint64_t lx = off[x + 1] - off[x], ly = off[y + 1] - off[y];
+        const uint64_t m = lx < ly ? lx : ly;
+        for(uint64_t t = 0; t < m; ++t) {
+            const char cx = rev ? B[off[x + 1] - 1 - t] : B[off[x] + t], cy = rev ? B[off[y + 1] - 1 - t] : B[off[y] + t];
+            if(cx != cy) return cx < cy;
+        }
+        if(lx != ly) return lx < ly;
+        return x < y;
+    });
+    std::ofstream sai(path.c_str());
+    sai << 51914 << "\n" << n << "\n" << n << "\n";
+    for(uint32_t i = 0; i < n; ++i) sai << order[i] << " 0\n";
+    if(!sai) { std::cerr << "index: cannot write " << path << "\n"; return false; }
+    return true;
+}
+
 static int PacBioSelfCorrectionMain(int argc, char** argv)
 {
     parsePacBioSelfCorrectionOptions(argc, argv);
@@ -202,6 +233,11 @@ static int PacBioSelfCorrectionMain(int argc, char** argv)
         std::vector<uint64_t> off;
         loadReads(opt::readsFile, bases, off);
         lrscOrDie(lrsc_index_build(bases.data(), off.data(), (uint32_t)(off.size() - 1), opt::devices[0], &idx), "lrsc_index_build");
+        if(!opt::saveIndex.empty()) {
+            lrscOrDie(lrsc_index_write(idx, opt::devices[0], (opt::saveIndex + BWT_EXT).c_str(), (opt::saveIndex + RBWT_EXT).c_str()), "lrsc_index_write");
+            for(int rev = 0; rev < 2; ++rev)
+                if(!writeLexicoIndex(opt::saveIndex + (rev ? ".rsai" : ".sai"), bases, off, rev != 0)) exit(EXIT_FAILURE);
+        }
     } else {
         std::cerr << "Loading BWT: " << opt::prefix + BWT_EXT << "\n" << "Loading RBWT: " << opt::prefix + RBWT_EXT << "\n";
         lrscOrDie(lrsc_index_open((opt::prefix + BWT_EXT).c_str(), (opt::prefix + RBWT_EXT).c_str(), &idx), "lrsc_index_open");
@@ -277,28 +313,7 @@ static int indexMain(int argc, char** argv)
         lrscOrDie(lrsc_build_bwt(bases.data(), off.data(), n, rev, device, &units, &nu), "lrsc_build_bwt");
         lrscOrDie(lrsc_write_bwt_file((prefix + (rev ? RBWT_EXT : BWT_EXT)).c_str(), units, nu, n, bases.size() + n), "lrsc_write_bwt_file");
         lrsc_buffer_free(units);
-        // .sai / .rsai: lexicographic rank -> read index (SampledSuffixArray::buildLexicoIndex + writeLexicoIndex,
-        // SuffixTools/SampledSuffixArray.cpp:158-190,248-258; text format of SAWriter.cpp:32-54).  The reference LF-walks each
-        // read back to its '$' row; that row's rank among the '$' rows is the rank of the read among all reads compared as
-        // strings ('$' < A < C < G < T, so a proper prefix sorts first) with equal reads in input order (sentinel order
-        // MR_SO_IO) -- computed directly here.  `pbcorrect` only needs the file to exist.
-        std::vector<uint32_t> order(n);
-        for(uint32_t i = 0; i < n; ++i) order[i] = i;
-        const char* B = bases.data();
-        std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
-            const uint64_t lx = off[x + 1] - off[x], ly = off[y + 1] - off[y];
-            const uint64_t m = lx < ly ? lx : ly;
-            for(uint64_t t = 0; t < m; ++t) {
-                const char cx = rev ? B[off[x + 1] - 1 - t] : B[off[x] + t], cy = rev ? B[off[y + 1] - 1 - t] : B[off[y] + t];
-                if(cx != cy) return cx < cy;
-            }
-            if(lx != ly) return lx < ly;
-            return x < y;
-        });
-        std::ofstream sai((prefix + (rev ? ".rsai" : ".sai")).c_str());
-        sai << 51914 << "\n" << n << "\n" << n << "\n";
-        for(uint32_t i = 0; i < n; ++i) sai << order[i] << " 0\n";
-        if(!sai) { std::cerr << "index: cannot write " << prefix << (rev ? ".rsai" : ".sai") << "\n"; return EXIT_FAILURE; }
+        if(!writeLexicoIndex(prefix + (rev ? ".rsai" : ".sai"), bases, off, rev != 0)) return EXIT_FAILURE;
     }
     return 0;
 }

@@ -13,7 +13,14 @@ memory peak of each route (the free memory of the whole device: only meaningful 
 kernel times come from one child run of lrsc_index_build under `rocprofv3 --kernel-trace --stats`, and are turned into bytes/s
 counting N bytes read and N/3 written per strand.
 
-Writes profiles/index_in_memory.json (or --out)."""
+Writes profiles/index_in_memory.json (or --out).
+
+--rle measures the device RL encoder (csrc/fm_rle.hip) on the same reads instead: lrsc_build_bwt for both strands with the encoder
+and with LRSC_BWT_HOST_RLE=1 (BWT to the host at a byte per symbol, one host thread encodes), alternating, --runs of each after a
+warm-up of each, and one lrsc_index_write from a built index.  The encoder's kernel times come from a child run under
+`rocprofv3 --kernel-trace --stats` (both strands through lrsc_build_bwt: the byte BWT as the source; one lrsc_index_build +
+lrsc_index_write: the rank blocks as the source), as bytes/s counting the source bytes each kernel reads plus the units the emit
+kernel writes.  Writes profiles/index_rle.json (or --out)."""
 from __future__ import annotations
 
 import argparse
@@ -36,6 +43,7 @@ sys.path.insert(0, str(REPO))
 from longreadselfcorrect_amd import Lrsc  # noqa: E402
 
 PACK_KERNELS = ("pack_hist_kernel", "pack_blocks_kernel", "dollar_dir_kernel", "IsDollar")
+RLE_KERNELS = ("rle_summary_kernel", "rle_count_kernel", "rle_emit_kernel")
 
 
 def say(*a):
@@ -154,12 +162,108 @@ def kernel_times(args, n_sym) -> dict:
         return out
 
 
+def build_both(api, bases, off, host_rle: bool):
+    """lrsc_build_bwt for both strands on one route; (wall seconds, units per strand, a digest of the units)"""
+    if host_rle:
+        os.environ["LRSC_BWT_HOST_RLE"] = "1"
+    else:
+        os.environ.pop("LRSC_BWT_HOST_RLE", None)
+    try:
+        t = time.perf_counter()
+        units = [api.build_bwt(bases, off, rev, 0) for rev in (False, True)]
+        wall = time.perf_counter() - t
+    finally:
+        os.environ.pop("LRSC_BWT_HOST_RLE", None)
+    return wall, [int(u.size) for u in units], [hash(u.tobytes()) for u in units]
+
+
+def rle_kernel_times(args, n_sym, n_units) -> dict:
+    with tempfile.TemporaryDirectory() as d:
+        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--", sys.executable, __file__, "--rle-call-only",
+               "--genome-mb", str(args.genome_mb), "--reads", str(args.reads)]
+        try:
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=PROFILE_TIMEOUT_S)
+        except subprocess.TimeoutExpired:
+            return {"error": f"the profiled run passed its limit of {PROFILE_TIMEOUT_S} s"}
+        if r.returncode != 0:
+            return {"error": (r.stderr or r.stdout)[-400:]}
+        out = {}
+        for f in Path(d).rglob("*kernel_stats.csv"):
+            for row in csv.DictReader(open(f)):
+                name = row.get("Name", "")
+                for k in RLE_KERNELS:
+                    if k in name:
+                        src = "byte_bwt" if "SrcBytes" in name else "rank_blocks"
+                        e = out.setdefault(src, {}).setdefault(k, {"calls": 0, "total_ms": 0.0})
+                        e["calls"] += int(row["Calls"])
+                        e["total_ms"] += float(row["TotalDurationNs"]) / 1e6
+        # per source, both strands: every kernel reads the source once (N bytes, or the rank blocks: 64 bytes per block) and the
+        # emit kernel writes the units (the scans over the per-tile entries are not among these kernels)
+        ksyms = 128 if n_sym >= 2**31 or os.environ.get("LRSC_FORCE_WIDE") else 192
+        source_bytes = {"byte_bwt": 2 * n_sym, "rank_blocks": 2 * 64 * (n_sym // ksyms + 1)}
+        for src, kernels in out.items():
+            total_ms = sum(e["total_ms"] for e in kernels.values())
+            counted = 0
+            for k, e in kernels.items():
+                e["counted_bytes"] = source_bytes[src] + (sum(n_units) if k == "rle_emit_kernel" else 0)
+                e["achieved_bytes_per_s"] = e["counted_bytes"] / (e["total_ms"] / 1e3) if e["total_ms"] else None
+                counted += e["counted_bytes"]
+            kernels["all"] = {"total_ms": total_ms, "counted_bytes": counted,
+                              "achieved_bytes_per_s": counted / (total_ms / 1e3) if total_ms else None}
+        return out
+
+
+def rle_main(args, api, bases, off, n_sym):
+    if args.rle_call_only:
+        for rev in (False, True):
+            api.build_bwt(bases, off, rev, 0)
+        with tempfile.TemporaryDirectory() as d:
+            idx = api.index_build(bases, off, 0)
+            idx.write(Path(d) / "x.bwt", Path(d) / "x.rbwt", 0)
+            idx.close()
+        return
+    routes = {"device_rle": False, "host_rle": True}
+    digests = {}
+    for name, host in routes.items():
+        wall, n_units, digests[name] = build_both(api, bases, off, host)
+        say(f"warm-up {name}: {wall:.2f} s, {n_units} units")
+    assert digests["device_rle"] == digests["host_rle"], "the two routes' units differ"
+    walls = {k: [] for k in routes}
+    for i in range(args.runs):
+        for name, host in routes.items():
+            wall, _, dg = build_both(api, bases, off, host)
+            assert dg == digests[name]
+            walls[name].append(wall)
+            say(f"run {i} {name}: {wall:.2f} s")
+    stages = {}
+    with tempfile.TemporaryDirectory() as d:
+        idx = clock(stages, "index_build", lambda: api.index_build(bases, off, 0))
+        clock(stages, "index_units_both_strands", lambda: [idx.units(s, 0) for s in (0, 1)])
+        clock(stages, "index_write", lambda: idx.write(Path(d) / "x.bwt", Path(d) / "x.rbwt", 0))
+        idx.close()
+    result = {
+        "workload": {"genome_mb": args.genome_mb, "reads": off.size - 1, "symbols_per_strand": n_sym, "units_per_strand": n_units},
+        "build_bwt_both_strands_wall_s": {k: {"all": v, "min": min(v), "max": max(v)} for k, v in walls.items()},
+        "device_below_host_in_every_pairing": max(walls["device_rle"]) < min(walls["host_rle"]),
+        "built_index_stages_s": stages,
+    }
+    if not args.no_profile:
+        say("profiled child run")
+        result["encoder_kernels"] = rle_kernel_times(args, n_sym, n_units)
+    out = args.out or str(REPO / "profiles" / "index_rle.json")
+    Path(out).parent.mkdir(parents=True, exist_ok=True)
+    Path(out).write_text(json.dumps(result, indent=1) + "\n")
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--genome-mb", type=float, default=11.1)
     ap.add_argument("--reads", type=int, default=100000)
     ap.add_argument("--runs", type=int, default=2)
-    ap.add_argument("--out", default=str(REPO / "profiles" / "index_in_memory.json"))
+    ap.add_argument("--out", default=None, help="default: profiles/index_in_memory.json, or profiles/index_rle.json with --rle")
+    ap.add_argument("--rle", action="store_true", help="measure the device RL encoder instead (see the module text)")
+    ap.add_argument("--rle-call-only", action="store_true", help="the encoder's calls once (the child run under the profiler)")
     ap.add_argument("--call-only", action="store_true", help="one lrsc_index_build (the child run under the profiler)")
     ap.add_argument("--no-profile", action="store_true")
     args = ap.parse_args()
@@ -170,6 +274,8 @@ def main():
     bases, off = api.synth_reads(0x5EED0002, genome, n_reads, 10000)
     n_sym = int(off[-1]) + n_reads
     say(f"{n_reads} reads, {n_sym} symbols per strand")
+    if args.rle or args.rle_call_only:
+        return rle_main(args, api, bases, off, n_sym)
     if args.call_only:
         api.index_build(bases, off, 0).close()
         return
@@ -200,8 +306,9 @@ def main():
     if not args.no_profile:
         say("profiled child run")
         result["packer_kernels"] = kernel_times(args, n_sym)
-    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
-    Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
+    out = args.out or str(REPO / "profiles" / "index_in_memory.json")
+    Path(out).parent.mkdir(parents=True, exist_ok=True)
+    Path(out).write_text(json.dumps(result, indent=1) + "\n")
     print(json.dumps(result))
 
 
