@@ -112,6 +112,16 @@ int lrsc_index_open(const char* bwt_path, const char* rbwt_path, lrsc_index** ou
 int lrsc_index_from_units(const uint8_t* bwt_units, uint64_t n_bwt_units,
                           const uint8_t* rbwt_units, uint64_t n_rbwt_units,
                           uint64_t num_strings, uint64_t num_symbols, lrsc_index** out);
+/* lrsc_index_open / lrsc_index_from_units with the decode on `device`: what RLBWT::RLBWT(file) + initializeFMIndex
+ * (SuffixTools/RLBWT.cpp:23-32,109-248) do with the units that BWTReaderBinary.cpp:55-85 reads.  The RL units of one strand
+ * after the other go to the device as they are and are packed into rank blocks there; no host pass over the symbols.
+ * Same checks, statuses and messages as the host route; on an error nothing stays allocated and *out is untouched.
+ * On return the index is resident on `device` (lrsc_index_upload(idx, device) is a no-op) with its k-mer tables, and carries
+ * a host image, so lrsc_index_upload to any other device works as for an opened index. */
+int lrsc_index_open_device(const char* bwt_path, const char* rbwt_path, int device, lrsc_index** out);
+int lrsc_index_from_units_device(const uint8_t* bwt_units, uint64_t n_bwt_units,
+                                 const uint8_t* rbwt_units, uint64_t n_rbwt_units,
+                                 uint64_t num_strings, uint64_t num_symbols, int device, lrsc_index** out);
 int lrsc_index_info_get(const lrsc_index* idx, lrsc_index_info* out);
 /* Copy both strands into `device`'s HBM (idempotent per device). */
 int lrsc_index_upload(lrsc_index* idx, int device);

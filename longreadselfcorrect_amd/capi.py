@@ -226,6 +226,9 @@ class Lrsc:
         L.lrsc_index_open.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]
         L.lrsc_index_from_units.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
                                             C.POINTER(C.c_void_p)]
+        L.lrsc_index_open_device.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.POINTER(C.c_void_p)]
+        L.lrsc_index_from_units_device.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int,
+                                                   C.POINTER(C.c_void_p)]
         L.lrsc_index_info_get.argtypes = [C.c_void_p, C.POINTER(IndexInfo)]
         L.lrsc_index_upload.argtypes = [C.c_void_p, C.c_int]
         L.lrsc_index_close.argtypes = [C.c_void_p]
@@ -373,6 +376,22 @@ class Lrsc:
         b = np.ascontiguousarray(rbwt_units, dtype=np.uint8)
         self.check(self.lib.lrsc_index_from_units(_ptr(a), a.size, _ptr(b), b.size, num_strings, num_symbols, C.byref(h)),
                    "lrsc_index_from_units")
+        return Index(self, h)
+
+    def index_open_device(self, bwt_path: str, rbwt_path: str, device: int = 0) -> "Index":
+        """index_open with the RL units decoded and packed on `device`; the index is resident there, k-mer tables included."""
+        h = C.c_void_p()
+        self.check(self.lib.lrsc_index_open_device(str(bwt_path).encode(), str(rbwt_path).encode(), device, C.byref(h)),
+                   "lrsc_index_open_device")
+        return Index(self, h)
+
+    def index_from_units_device(self, bwt_units: np.ndarray, rbwt_units: np.ndarray, num_strings: int, num_symbols: int,
+                                device: int = 0) -> "Index":
+        h = C.c_void_p()
+        a = np.ascontiguousarray(bwt_units, dtype=np.uint8)
+        b = np.ascontiguousarray(rbwt_units, dtype=np.uint8)
+        self.check(self.lib.lrsc_index_from_units_device(_ptr(a), a.size, _ptr(b), b.size, num_strings, num_symbols, device, C.byref(h)),
+                   "lrsc_index_from_units_device")
         return Index(self, h)
 
 

@@ -1,4 +1,5 @@
-// capi_index.cpp -- the index object (open / from units / build from reads / upload with its k-mer tables / close), the
+// capi_index.cpp -- the index object (open / from units, on the host or on the device / build from reads / upload with its
+// k-mer tables / close), the
 // device BWT build, the RL units of a resident copy and the file writer.
 #include <chrono>
 #include <thread>
@@ -6,6 +7,7 @@
 #include "capi_internal.h"
 #include "fm_pack.h"
 #include "fm_rle.h"
+#include "fm_unrle.h"
 
 using namespace lrsc;
 
@@ -263,6 +265,23 @@ extern "C" int lrsc_build_bwt(const char* reads, const uint64_t* read_off, uint3
 
 extern "C" void lrsc_buffer_free(void* p) { std::free(p); }
 
+// the host image of a strand that was packed on the device: a copy of the packed arrays (a third of a byte per symbol)
+static int image_from_device(const PackedStrand& ps, uint64_t N, uint64_t n_runs, StrandImage& im, std::string& err)
+{
+    im.n_blocks = ps.n_blocks;
+    im.n_symbols = N;
+    im.n_runs = n_runs;
+    for(int c = 0; c < 5; ++c) im.pred[c] = ps.pred[c];
+    im.blocks.resize(ps.n_blocks * 64);
+    im.dollars.resize(ps.n_dollars);
+    im.dollar_dir.resize(ps.n_dir);
+    hipError_t e = hipMemcpy(im.blocks.data(), ps.blocks, im.blocks.size(), hipMemcpyDeviceToHost);
+    if(e == hipSuccess && ps.n_dollars) e = hipMemcpy(im.dollars.data(), ps.dollars, ps.n_dollars * sizeof(uint64_t), hipMemcpyDeviceToHost);
+    if(e == hipSuccess) e = hipMemcpy(im.dollar_dir.data(), ps.dollar_dir, ps.n_dir * sizeof(uint32_t), hipMemcpyDeviceToHost);
+    if(e != hipSuccess) { err = std::string("copy of the packed index to the host: ") + hipGetErrorString(e); return LRSC_ERR_DEVICE; }
+    return LRSC_OK;
+}
+
 // One strand of lrsc_index_build: BWT on the device -> packed image on the device (dc.*[s]) -> host image by a copy of the
 // packed arrays (a third of a byte per symbol).  d_bwt is gone before the next strand starts.
 static int build_strand(const char* reads, const uint64_t* off, uint32_t n_reads, int s, int device, bool wide, StrandImage& im,
@@ -284,18 +303,7 @@ static int build_strand(const char* reads, const uint64_t* off, uint32_t n_reads
     dc.dollar_dir[s] = ps.dollar_dir;
     ms[0] += std::chrono::duration<double, std::milli>(t1 - t0).count();
     ms[1] += std::chrono::duration<double, std::milli>(clk::now() - t1).count();
-    im.n_blocks = ps.n_blocks;
-    im.n_symbols = N;
-    im.n_runs = 0;
-    for(int c = 0; c < 5; ++c) im.pred[c] = ps.pred[c];
-    im.blocks.resize(ps.n_blocks * 64);
-    im.dollars.resize(ps.n_dollars);
-    im.dollar_dir.resize(ps.n_dir);
-    hipError_t e = hipMemcpy(im.blocks.data(), ps.blocks, im.blocks.size(), hipMemcpyDeviceToHost);
-    if(e == hipSuccess && ps.n_dollars) e = hipMemcpy(im.dollars.data(), ps.dollars, ps.n_dollars * sizeof(uint64_t), hipMemcpyDeviceToHost);
-    if(e == hipSuccess) e = hipMemcpy(im.dollar_dir.data(), ps.dollar_dir, ps.n_dir * sizeof(uint32_t), hipMemcpyDeviceToHost);
-    if(e != hipSuccess) { err = std::string("copy of the packed index to the host: ") + hipGetErrorString(e); return LRSC_ERR_DEVICE; }
-    return LRSC_OK;
+    return image_from_device(ps, N, 0, im, err);
 }
 
 extern "C" int lrsc_index_build(const char* reads, const uint64_t* read_off, uint32_t n_reads, int device, lrsc_index** out)
@@ -326,6 +334,100 @@ extern "C" int lrsc_index_build(const char* reads, const uint64_t* read_off, uin
         std::fprintf(stderr, "[lrsc] index build: bwt %.3f ms, pack %.3f ms, tables %.3f ms\n", ms[0], ms[1], ms[2]);
     *out = idx;
     return LRSC_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// a saved index, decoded on the device (fm_unrle.hip)
+// ---------------------------------------------------------------------------------------
+// One strand of the device route: units -> device -> packed image on the device (dc.*[s]) -> host image by a copy of the packed
+// arrays.  The units are gone from the device before the next strand starts.  ms: copy of the units, decode + pack.
+static int unrle_strand(const uint8_t* units, uint64_t n_units, uint64_t N, int s, bool wide, StrandImage& im, DeviceCopy& dc, double ms[2],
+                        std::string& err)
+{
+    using clk = std::chrono::steady_clock;
+    const auto t0 = clk::now();
+    uint8_t* d_units = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_units), std::max<uint64_t>(n_units, 1));
+    if(e == hipSuccess && n_units) e = hipMemcpy(d_units, units, n_units, hipMemcpyHostToDevice);
+    if(e != hipSuccess) {
+        if(d_units) (void)hipFree(d_units);
+        err = std::string("copy of the RL units to the device: ") + hipGetErrorString(e);
+        return LRSC_ERR_DEVICE;
+    }
+    const auto t1 = clk::now();
+    PackedStrand ps;
+    const int st = pack_units_device(d_units, n_units, N, wide, ps, nullptr, err);
+    (void)hipFree(d_units);
+    if(st != LRSC_OK) return st;
+    dc.blocks[s] = ps.blocks;
+    dc.dollars[s] = ps.dollars;
+    dc.dollar_dir[s] = ps.dollar_dir;
+    ms[0] += std::chrono::duration<double, std::milli>(t1 - t0).count();
+    ms[1] += std::chrono::duration<double, std::milli>(clk::now() - t1).count();
+    return image_from_device(ps, N, n_units, im, err);
+}
+
+static int index_from_units_device_impl(const uint8_t* u0, uint64_t n0, const uint8_t* u1, uint64_t n1, uint64_t num_strings,
+                                        uint64_t num_symbols, int device, lrsc_index** out)
+{
+    HIP_TRY(hipSetDevice(device));
+    lrsc_index* idx = new(std::nothrow) lrsc_index();
+    if(!idx) return fail(LRSC_ERR_NOMEM, "lrsc_index");
+    idx->num_strings = num_strings;
+    idx->num_symbols = num_symbols;
+    idx->wide = num_symbols >= (1ull << 31) || std::getenv("LRSC_FORCE_WIDE") != nullptr;   // as index_from_units_impl
+    const uint8_t* us[2] = {u0, u1};
+    const uint64_t ns[2] = {n0, n1};
+    DeviceCopy dc;
+    double ms[4] = {0., 0., 0., 0.};
+    std::string err;
+    int st = LRSC_OK;
+    for(int s = 0; s < 2 && st == LRSC_OK; ++s) {
+        const auto t0 = std::chrono::steady_clock::now();
+        st = unrle_strand(us[s], ns[s], num_symbols, s, idx->wide, idx->image[s], dc, ms, err);
+        if(st != LRSC_OK) st = fail(st, err);
+        ms[2] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    if(st == LRSC_OK && (idx->image[0].dollars.size() != num_strings || idx->image[1].dollars.size() != num_strings))
+        st = fail(LRSC_ERR_FORMAT, "number of '$' rows differs from the number of strings in the header");
+    if(st == LRSC_OK) {
+        const auto t0 = std::chrono::steady_clock::now();
+        std::lock_guard<std::mutex> lock(idx->mu);
+        st = register_copy(idx, device, dc);
+        ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    if(st != LRSC_OK) { free_device_copy(dc); delete idx; return st; }
+    if(std::getenv("LRSC_BWT_PROFILE"))
+        std::fprintf(stderr, "[lrsc] index open on the device: units to the device %.3f ms, decode + pack %.3f ms, image to the host %.3f ms, tables %.3f ms\n",
+                     ms[0], ms[1], ms[2] - ms[0] - ms[1], ms[3]);
+    *out = idx;
+    return LRSC_OK;
+}
+
+extern "C" int lrsc_index_from_units_device(const uint8_t* bwt_units, uint64_t n_bwt_units, const uint8_t* rbwt_units,
+                                            uint64_t n_rbwt_units, uint64_t num_strings, uint64_t num_symbols, int device,
+                                            lrsc_index** out)
+{
+    if(!bwt_units || !rbwt_units || !out || num_symbols == 0) return fail(LRSC_ERR_ARG, "null/empty index input");
+    return index_from_units_device_impl(bwt_units, n_bwt_units, rbwt_units, n_rbwt_units, num_strings, num_symbols, device, out);
+}
+
+extern "C" int lrsc_index_open_device(const char* bwt_path, const char* rbwt_path, int device, lrsc_index** out)
+{
+    if(!bwt_path || !rbwt_path || !out) return fail(LRSC_ERR_ARG, "null path");
+    std::vector<uint8_t> u[2];
+    uint64_t nstr[2] = {0, 0}, nsym[2] = {0, 0};
+    std::string err;
+    const auto t0 = std::chrono::steady_clock::now();
+    int st = read_bwt_file(bwt_path, u[0], nstr[0], nsym[0], err);
+    if(st != LRSC_OK) return fail(st, err);
+    st = read_bwt_file(rbwt_path, u[1], nstr[1], nsym[1], err);
+    if(st != LRSC_OK) return fail(st, err);
+    if(nstr[0] != nstr[1] || nsym[0] != nsym[1]) return fail(LRSC_ERR_FORMAT, ".bwt and .rbwt disagree on strings/symbols");
+    if(std::getenv("LRSC_BWT_PROFILE"))
+        std::fprintf(stderr, "[lrsc] index open on the device: file read %.3f ms\n",
+                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    return index_from_units_device_impl(u[0].data(), u[0].size(), u[1].data(), u[1].size(), nstr[0], nsym[0], device, out);
 }
 
 extern "C" int lrsc_index_units(lrsc_index* idx, int strand, int device, uint8_t** units_out, uint64_t* n_units_out)

@@ -108,6 +108,19 @@ LRSC_HD uint32_t dollar_dir_entry(const uint64_t* dollars_before, uint64_t n_blo
     return (uint32_t)dollars_before[b < n_blocks ? b : n_blocks];
 }
 
+// ---- the tile of the streaming kernels (fm_pack.hip, fm_unrle.hip) ----
+constexpr uint32_t kPackThreads = 128;          // rank blocks per workgroup, one thread each in the packer
+
+// An LDS row holds one block's symbols plus 16 bytes, a block's output 64 + 16 bytes: with these strides the 16-byte accesses
+// of the lanes of a wave, one row each, fall on different banks.
+template <class Block>
+struct PackTile {
+    static constexpr uint32_t kChunks = Block::kSyms / 16;
+    static constexpr uint32_t kRow = kChunks + 1;
+    static constexpr uint32_t kOutRow = 5;
+    static_assert(kRow >= kOutRow, "the finished blocks reuse the symbol rows");
+};
+
 // ---- the device packer (fm_pack.hip) ----
 // One strand's image in device memory, as lrsc_index_upload would have left it.
 struct PackedStrand {

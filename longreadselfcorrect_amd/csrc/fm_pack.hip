@@ -23,18 +23,6 @@
 
 namespace lrsc {
 
-static constexpr uint32_t kPackThreads = 128;   // threads, and blocks, per workgroup
-
-// An LDS row holds one block's symbols plus 16 bytes, a block's output 64 + 16 bytes: with these strides the 16-byte accesses
-// of the lanes of a wave, one row each, fall on different banks.
-template <class Block>
-struct PackTile {
-    static constexpr uint32_t kChunks = Block::kSyms / 16;
-    static constexpr uint32_t kRow = kChunks + 1;
-    static constexpr uint32_t kOutRow = 5;
-    static_assert(kRow >= kOutRow, "the finished blocks reuse the symbol rows");
-};
-
 // symbols of blocks [first_block, first_block + kPackThreads) -> rows; bytes at and beyond N read as 0
 template <class Block>
 __device__ __forceinline__ void stage_tile(const uint8_t* __restrict__ bwt, uint64_t N, uint64_t first_block, Sym16* rows)

@@ -41,6 +41,7 @@ static const char* CORRECT_USAGE_MESSAGE =
     "      -p, --prefix=PREFIX              Use PREFIX for the names of the index files\n"
     "      --build-index                    Index READSFILE in memory on the first device instead of loading PREFIX.bwt/.rbwt\n"
     "      --save-index=PREFIX              With --build-index: write the built index to PREFIX.bwt/.rbwt/.sai/.rsai\n"
+    "      --load-on-device                 With -p: decode PREFIX.bwt/.rbwt on the first device instead of on the host\n"
     "      -o, --output=DIR                 Output results in the directory\n"
     "      -b, --barcode=FILE               Barcode of raw reads\n"
     "\nPacBio correction parameters:\n"
@@ -77,11 +78,11 @@ static std::array<int, 3> offset = {{0, 0, 0}};
 static std::vector<int> devices(1, 0);
 static int workersPerDevice = 2;
 static size_t batch = 100000;
-static bool buildIndex = false;
+static bool buildIndex = false, loadOnDevice = false;
 }
 
 static const char* shortopts = "t:p:o:b:c:e:k:u:r:n:l:i:s:g:m:v";
-enum { OPT_HELP = 1, OPT_VERSION, OPT_SPLIT, OPT_FIRST, OPT_DEBUGEXTEND, OPT_DEBUGSEED, OPT_ONLYSEED, OPT_NODP, OPT_DEVICES, OPT_BATCH, OPT_WORKERS, OPT_BUILDINDEX, OPT_SAVEINDEX };
+enum { OPT_HELP = 1, OPT_VERSION, OPT_SPLIT, OPT_FIRST, OPT_DEBUGEXTEND, OPT_DEBUGSEED, OPT_ONLYSEED, OPT_NODP, OPT_DEVICES, OPT_BATCH, OPT_WORKERS, OPT_BUILDINDEX, OPT_SAVEINDEX, OPT_LOADONDEVICE };
 static const struct option longopts[] = {
     {"thread", required_argument, nullptr, 't'},       {"prefix", required_argument, nullptr, 'p'},
     {"output", required_argument, nullptr, 'o'},       {"barcode", required_argument, nullptr, 'b'},
@@ -97,6 +98,7 @@ static const struct option longopts[] = {
     {"nodp", no_argument, nullptr, OPT_NODP},          {"devices", required_argument, nullptr, OPT_DEVICES},
     {"batch", required_argument, nullptr, OPT_BATCH},  {"workers-per-device", required_argument, nullptr, OPT_WORKERS},
     {"build-index", no_argument, nullptr, OPT_BUILDINDEX}, {"save-index", required_argument, nullptr, OPT_SAVEINDEX},
+    {"load-on-device", no_argument, nullptr, OPT_LOADONDEVICE},
     {nullptr, 0, nullptr, 0}};
 
 static void lrscOrDie(int st, const char* what)
@@ -147,6 +149,7 @@ static void parsePacBioSelfCorrectionOptions(int argc, char** argv)
             case OPT_WORKERS: arg >> opt::workersPerDevice; break;
             case OPT_BUILDINDEX: opt::buildIndex = true; break;
             case OPT_SAVEINDEX: arg >> opt::saveIndex; break;
+            case OPT_LOADONDEVICE: opt::loadOnDevice = true; break;
             default: die = true; break;
         }
     }
@@ -155,6 +158,7 @@ static void parsePacBioSelfCorrectionOptions(int argc, char** argv)
     if(opt::thread <= 0) { std::cerr << SUBPROGRAM ": invalid number of threads: " << opt::thread << "\n"; die = true; }
     if(opt::buildIndex && !opt::prefix.empty()) { std::cerr << SUBPROGRAM << ": --build-index reads no index files: give either it or -p\n"; die = true; }
     if(!opt::saveIndex.empty() && !opt::buildIndex) { std::cerr << SUBPROGRAM << ": --save-index writes the index that --build-index builds: give both\n"; die = true; }
+    if(opt::loadOnDevice && opt::buildIndex) { std::cerr << SUBPROGRAM << ": --load-on-device decodes the index files that -p names: --build-index reads none\n"; die = true; }
     if(opt::prefix.empty() && !opt::buildIndex) { std::cerr << SUBPROGRAM << ": no prefix\n"; die = true; }
     if(opt::directory.empty()) { std::cerr << SUBPROGRAM << ": no directory\n"; die = true; }
     else {
@@ -240,7 +244,10 @@ static int PacBioSelfCorrectionMain(int argc, char** argv)
         }
     } else {
         std::cerr << "Loading BWT: " << opt::prefix + BWT_EXT << "\n" << "Loading RBWT: " << opt::prefix + RBWT_EXT << "\n";
-        lrscOrDie(lrsc_index_open((opt::prefix + BWT_EXT).c_str(), (opt::prefix + RBWT_EXT).c_str(), &idx), "lrsc_index_open");
+        if(opt::loadOnDevice)   // resident on the first device; the others get the host image below
+            lrscOrDie(lrsc_index_open_device((opt::prefix + BWT_EXT).c_str(), (opt::prefix + RBWT_EXT).c_str(), opt::devices[0], &idx), "lrsc_index_open_device");
+        else
+            lrscOrDie(lrsc_index_open((opt::prefix + BWT_EXT).c_str(), (opt::prefix + RBWT_EXT).c_str(), &idx), "lrsc_index_open");
     }
     for(int d : opt::devices) lrscOrDie(lrsc_index_upload(idx, d), "lrsc_index_upload");
 

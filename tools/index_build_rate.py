@@ -20,7 +20,15 @@ and with LRSC_BWT_HOST_RLE=1 (BWT to the host at a byte per symbol, one host thr
 warm-up of each, and one lrsc_index_write from a built index.  The encoder's kernel times come from a child run under
 `rocprofv3 --kernel-trace --stats` (both strands through lrsc_build_bwt: the byte BWT as the source; one lrsc_index_build +
 lrsc_index_write: the rank blocks as the source), as bytes/s counting the source bytes each kernel reads plus the units the emit
-kernel writes.  Writes profiles/index_rle.json (or --out)."""
+kernel writes.  Writes profiles/index_rle.json (or --out).
+
+--open measures the device RL decoder (csrc/fm_unrle.hip): loading a saved index of the same reads.  The .bwt/.rbwt files are
+written once (lrsc_build_bwt + lrsc_write_bwt_file) and read once, so that both routes see a warm page cache; then lrsc_index_open +
+lrsc_index_upload against lrsc_index_open_device, alternating, --runs of each after a warm-up of each.  The host route's stages are
+its two calls (read + decode on two host threads; copy + k-mer tables) beside a plain read of both files; the device route's come
+from its LRSC_BWT_PROFILE lines (file read, units to the device, decode + pack, image to the host, tables).  The decoder's kernel
+times come from a child run of lrsc_index_open_device on the same files under `rocprofv3 --kernel-trace --stats`, as bytes/s
+counting the units each kernel reads and the blocks the pack kernel writes.  Writes profiles/index_open.json (or --out)."""
 from __future__ import annotations
 
 import argparse
@@ -44,6 +52,7 @@ from longreadselfcorrect_amd import Lrsc  # noqa: E402
 
 PACK_KERNELS = ("pack_hist_kernel", "pack_blocks_kernel", "dollar_dir_kernel", "IsDollar")
 RLE_KERNELS = ("rle_summary_kernel", "rle_count_kernel", "rle_emit_kernel")
+UNRLE_KERNELS = ("unrle_tile_kernel", "unrle_pack_kernel")
 
 
 def say(*a):
@@ -256,19 +265,142 @@ def rle_main(args, api, bases, off, n_sym):
     print(json.dumps(result))
 
 
+def route_open_host(api, files, _, work: Path):
+    st = {}
+    idx = clock(st, "index_open", lambda: api.index_open(*files))
+    clock(st, "index_upload", lambda: idx.upload(0))
+    return idx, st
+
+
+def route_open_device(api, files, _, work: Path):
+    """lrsc_index_open_device with LRSC_BWT_PROFILE set and this process's stderr in a file for the length of the call"""
+    st = {}
+    log = work / "open.err"
+    sys.stderr.flush()
+    saved = os.dup(2)
+    fd = os.open(log, os.O_WRONLY | os.O_CREAT | os.O_TRUNC)
+    os.dup2(fd, 2)
+    os.environ["LRSC_BWT_PROFILE"] = "1"
+    try:
+        idx = clock(st, "index_open_device", lambda: api.index_open_device(*files, 0))
+    finally:
+        del os.environ["LRSC_BWT_PROFILE"]
+        os.dup2(saved, 2)
+        os.close(fd)
+        os.close(saved)
+    text = log.read_text()
+    m = re.search(r"file read ([\d.]+) ms", text)
+    if m:
+        st["file_read"] = float(m.group(1)) / 1e3
+    m = re.search(r"units to the device ([\d.]+) ms, decode \+ pack ([\d.]+) ms, image to the host ([\d.]+) ms, tables ([\d.]+) ms", text)
+    if m:
+        st["units_to_device"], st["decode_pack"], st["image_to_host"], st["tables"] = (float(x) / 1e3 for x in m.groups())
+    return idx, st
+
+
+def unrle_kernel_times(files, n_sym, n_units) -> dict:
+    with tempfile.TemporaryDirectory() as d:
+        cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--", sys.executable, __file__, "--open-call-only",
+               "--files", files[0], files[1]]
+        try:
+            r = subprocess.run(cmd, capture_output=True, text=True, timeout=PROFILE_TIMEOUT_S)
+        except subprocess.TimeoutExpired:
+            return {"error": f"the profiled run passed its limit of {PROFILE_TIMEOUT_S} s"}
+        if r.returncode != 0:
+            return {"error": (r.stderr or r.stdout)[-400:]}
+        out = {}
+        for f in Path(d).rglob("*kernel_stats.csv"):
+            for row in csv.DictReader(open(f)):
+                for k in UNRLE_KERNELS:
+                    if k in row.get("Name", ""):
+                        e = out.setdefault(k, {"calls": 0, "total_ms": 0.0})
+                        e["calls"] += int(row["Calls"])
+                        e["total_ms"] += float(row["TotalDurationNs"]) / 1e6
+        # both strands: each kernel reads the units once, the pack kernel writes the rank blocks (the scans over the per-tile
+        # entries are not among these kernels)
+        ksyms = 128 if n_sym >= 2**31 or os.environ.get("LRSC_FORCE_WIDE") else 192
+        counted = {"unrle_tile_kernel": sum(n_units), "unrle_pack_kernel": sum(n_units) + 2 * 64 * (n_sym // ksyms + 1)}
+        for k, e in out.items():
+            e["counted_bytes"] = counted[k]
+            e["achieved_bytes_per_s"] = counted[k] / (e["total_ms"] / 1e3) if e["total_ms"] else None
+        if out:
+            total_ms = sum(e["total_ms"] for e in out.values())
+            all_bytes = sum(e["counted_bytes"] for e in out.values())
+            out["all"] = {"total_ms": total_ms, "counted_bytes": all_bytes, "achieved_bytes_per_s": all_bytes / (total_ms / 1e3) if total_ms else None}
+        return out
+
+
+def open_main(args, api, hip, bases, off, n_sym):
+    n_reads = off.size - 1
+    with tempfile.TemporaryDirectory() as d:
+        work = Path(d)
+        files = (str(work / "reads.bwt"), str(work / "reads.rbwt"))
+        n_units = []
+        for rev, f in zip((False, True), files):
+            u = api.build_bwt(bases, off, rev, 0)
+            api.write_bwt_file(f, u, n_reads, n_sym)
+            n_units.append(int(u.size))
+            del u
+        t = time.perf_counter()
+        for f in files:
+            with open(f, "rb") as fh:
+                while fh.read(1 << 26):
+                    pass
+        plain_read_s = time.perf_counter() - t
+        say(f"files written and read once ({plain_read_s:.2f} s): {n_units} units")
+        routes = {"host": route_open_host, "device": route_open_device}
+        for name, fn in routes.items():
+            r = run(api, hip, fn, files, None, work)
+            say(f"warm-up {name}: {r['wall_s']:.2f} s")
+        runs = {k: [] for k in routes}
+        for i in range(args.runs):
+            for name, fn in routes.items():
+                r = run(api, hip, fn, files, None, work)
+                runs[name].append(r)
+                say(f"run {i} {name}: {r['wall_s']:.2f} s {r['stages_s']} peak {r['device_peak_bytes'] / 2**30:.2f} GiB")
+        walls = {k: [r["wall_s"] for r in v] for k, v in runs.items()}
+        peaks = {k: max(r["device_peak_bytes"] for r in v) for k, v in runs.items()}
+        # the host route holds both packed images and the k-mer tables at its peak and nothing else
+        bound = max(n_units) + peaks["host"]
+        result = {
+            "workload": {"genome_mb": args.genome_mb, "reads": n_reads, "symbols_per_strand": n_sym, "units_per_strand": n_units},
+            "plain_read_of_both_files_s": plain_read_s,
+            "runs": runs,
+            "wall_s": {k: {"all": v, "min": min(v), "max": max(v), "spread": max(v) - min(v)} for k, v in walls.items()},
+            "device_below_host_in_every_pairing": max(walls["device"]) < min(walls["host"]),
+            "device_peak_bytes": peaks,
+            "both_images_bytes": runs["device"][0]["index_device_bytes"],
+            "device_peak_bound_bytes": bound,
+            "device_peak_within_one_strands_units_plus_images_plus_tables": peaks["device"] <= bound,
+        }
+        if not args.no_profile:
+            say("profiled child run")
+            result["decoder_kernels"] = unrle_kernel_times(files, n_sym, n_units)
+    out = args.out or str(REPO / "profiles" / "index_open.json")
+    Path(out).parent.mkdir(parents=True, exist_ok=True)
+    Path(out).write_text(json.dumps(result, indent=1) + "\n")
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--genome-mb", type=float, default=11.1)
     ap.add_argument("--reads", type=int, default=100000)
     ap.add_argument("--runs", type=int, default=2)
-    ap.add_argument("--out", default=None, help="default: profiles/index_in_memory.json, or profiles/index_rle.json with --rle")
+    ap.add_argument("--out", default=None, help="default: profiles/index_in_memory.json; profiles/index_rle.json with --rle, index_open.json with --open")
     ap.add_argument("--rle", action="store_true", help="measure the device RL encoder instead (see the module text)")
     ap.add_argument("--rle-call-only", action="store_true", help="the encoder's calls once (the child run under the profiler)")
     ap.add_argument("--call-only", action="store_true", help="one lrsc_index_build (the child run under the profiler)")
+    ap.add_argument("--open", action="store_true", help="measure the device RL decoder instead (see the module text)")
+    ap.add_argument("--open-call-only", action="store_true", help="one lrsc_index_open_device of --files (the child run under the profiler)")
+    ap.add_argument("--files", nargs=2, metavar=("BWT", "RBWT"))
     ap.add_argument("--no-profile", action="store_true")
     args = ap.parse_args()
     api = Lrsc()
     hip = C.CDLL("libamdhip64.so")
+    if args.open_call_only:
+        api.index_open_device(args.files[0], args.files[1], 0).close()
+        return
     genome = api.synth_genome(0x5EED0001, int(args.genome_mb * 1e6))
     n_reads = args.reads
     bases, off = api.synth_reads(0x5EED0002, genome, n_reads, 10000)
@@ -276,6 +408,8 @@ def main():
     say(f"{n_reads} reads, {n_sym} symbols per strand")
     if args.rle or args.rle_call_only:
         return rle_main(args, api, bases, off, n_sym)
+    if args.open:
+        return open_main(args, api, hip, bases, off, n_sym)
     if args.call_only:
         api.index_build(bases, off, 0).close()
         return
