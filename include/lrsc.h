@@ -141,6 +141,15 @@ void lrsc_buffer_free(void* p);
  * `device` (lrsc_index_upload(idx, device) is a no-op) with its k-mer tables, and carries a host image, so
  * lrsc_index_upload to any other device works as for an opened index.  Same read checks and messages as lrsc_build_bwt. */
 int lrsc_index_build(const char* reads, const uint64_t* read_off, uint32_t n_reads, int device, lrsc_index** out);
+/* The index of a's reads followed by b's, merged on `device` from the two resident copies; byte for byte what
+ * lrsc_index_build makes of the concatenated reads.  a and b need a copy on `device` (LRSC_ERR_DEVICE otherwise), are not
+ * modified and stay usable; a == b is allowed (every read twice).  The result is resident on `device` with its k-mer tables
+ * and carries a host image, as a built index does; num_runs is 0 as for a built index.
+ * dollar_origin (may be NULL): 2 * (n_a + n_b) bytes; entry s * (n_a + n_b) + k is 1 when the k-th '$' row of strand s of
+ * the merged BWT is a row of b, else 0 (what merging the .sai/.rsai lists needs).
+ * LRSC_ERR_UNSUPPORTED for 2^32 reads or more in total and for the packer's block limit; on an error nothing stays
+ * allocated and *out is untouched. */
+int lrsc_index_merge(lrsc_index* a, lrsc_index* b, int device, lrsc_index** out, uint8_t* dollar_origin);
 /* 30-byte header + units, the reference's binary .bwt/.rbwt format (BWTWriterBinary.cpp:28-46,82-93). */
 int lrsc_write_bwt_file(const char* path, const uint8_t* units, uint64_t n_units, uint64_t num_strings,
                         uint64_t num_symbols);

@@ -238,6 +238,7 @@ class Lrsc:
         L.lrsc_buffer_free.argtypes = [C.c_void_p]
         L.lrsc_index_build.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]
         L.lrsc_buffer_free.restype = None
+        L.lrsc_index_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.c_void_p]
         L.lrsc_write_bwt_file.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64]
         L.lrsc_index_units.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.lrsc_index_write.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p]
@@ -363,6 +364,16 @@ class Lrsc:
         h = C.c_void_p()
         self.check(self.lib.lrsc_index_build(_ptr(bases), _ptr(off), off.size - 1, device, C.byref(h)), "lrsc_index_build")
         return Index(self, h)
+
+    def index_merge(self, a: "Index", b: "Index", device: int = 0, want_origin: bool = False):
+        """The index of a's reads followed by b's, merged on `device` from the two copies there (a and b stay usable).  With
+        want_origin also a uint8 array [2, n_a + n_b]: 1 where that strand's k-th '$' row of the result is a row of b."""
+        h = C.c_void_p()
+        origin = None
+        if want_origin:
+            origin = np.zeros((2, a.info().num_strings + b.info().num_strings), dtype=np.uint8)
+        self.check(self.lib.lrsc_index_merge(a.h, b.h, device, C.byref(h), _ptr(origin) if want_origin else None), "lrsc_index_merge")
+        return (Index(self, h), origin) if want_origin else Index(self, h)
 
     # ---- index / ctx ------------------------------------------------------------------------
     def index_open(self, bwt_path: str, rbwt_path: str) -> "Index":

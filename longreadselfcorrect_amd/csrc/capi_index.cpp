@@ -1,10 +1,11 @@
 // capi_index.cpp -- the index object (open / from units, on the host or on the device / build from reads / upload with its
 // k-mer tables / close), the
-// device BWT build, the RL units of a resident copy and the file writer.
+// device BWT build, the merge of two resident indexes, the RL units of a resident copy and the file writer.
 #include <chrono>
 #include <thread>
 
 #include "capi_internal.h"
+#include "fm_merge.h"
 #include "fm_pack.h"
 #include "fm_rle.h"
 #include "fm_unrle.h"
@@ -332,6 +333,87 @@ extern "C" int lrsc_index_build(const char* reads, const uint64_t* read_off, uin
     if(st != LRSC_OK) { free_device_copy(dc); delete idx; return st; }
     if(std::getenv("LRSC_BWT_PROFILE"))
         std::fprintf(stderr, "[lrsc] index build: bwt %.3f ms, pack %.3f ms, tables %.3f ms\n", ms[0], ms[1], ms[2]);
+    *out = idx;
+    return LRSC_OK;
+}
+
+// ---------------------------------------------------------------------------------------
+// two resident indexes merged on the device (fm_merge.hip)
+// ---------------------------------------------------------------------------------------
+// One strand of lrsc_index_merge: walk + interleave -> BWT of the union on the device -> packed image on the device (dc.*[s]) ->
+// host image, as build_strand does after its sort.  rank[] goes once the origin is read from it, the BWT once it is packed.
+// ms: walk, interleave, pack.
+static int merge_strand(const FmStrand& a, bool wide_a, const FmStrand& b, bool wide_b, int s, bool wide, uint8_t* origin, StrandImage& im,
+                        DeviceCopy& dc, double ms[3], std::string& err)
+{
+    uint8_t* d_bwt = nullptr;
+    uint64_t* d_rank = nullptr;
+    int st = merge_strand_device(a, wide_a, b, wide_b, &d_bwt, &d_rank, ms, err);
+    if(st != LRSC_OK) return st;
+    if(origin) st = merge_origin_device(a, b, d_rank, origin, err);
+    (void)hipFree(d_rank);
+    if(st != LRSC_OK) { (void)hipFree(d_bwt); return st; }
+    const auto t0 = std::chrono::steady_clock::now();
+    const uint64_t N = a.n_symbols + b.n_symbols;
+    PackedStrand ps;
+    st = pack_strand_device(d_bwt, N, wide, ps, err);
+    (void)hipFree(d_bwt);
+    if(st != LRSC_OK) return st;
+    dc.blocks[s] = ps.blocks;
+    dc.dollars[s] = ps.dollars;
+    dc.dollar_dir[s] = ps.dollar_dir;
+    ms[2] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return image_from_device(ps, N, 0, im, err);
+}
+
+// the strands of idx's copy on `device`
+static int resident_strands(lrsc_index* idx, int device, FmStrand fs[2], bool& wide)
+{
+    std::lock_guard<std::mutex> lock(idx->mu);
+    auto it = idx->copies.find(device);
+    if(it == idx->copies.end()) return fail(LRSC_ERR_DEVICE, "index not uploaded to this device (call lrsc_index_upload)");
+    fs[0] = it->second.dev.strand[0];
+    fs[1] = it->second.dev.strand[1];
+    wide = idx->wide;
+    return LRSC_OK;
+}
+
+extern "C" int lrsc_index_merge(lrsc_index* a, lrsc_index* b, int device, lrsc_index** out, uint8_t* dollar_origin)
+{
+    if(!a || !b || !out) return fail(LRSC_ERR_ARG, "null");
+    FmStrand fa[2], fb[2];
+    bool wide_a = false, wide_b = false;
+    int st = resident_strands(a, device, fa, wide_a);
+    if(st == LRSC_OK) st = resident_strands(b, device, fb, wide_b);
+    if(st != LRSC_OK) return st;
+    const uint64_t n_reads = a->num_strings + b->num_strings;
+    if(n_reads >= (1ull << 32)) return fail(LRSC_ERR_UNSUPPORTED, "more than 2^32 reads");
+    HIP_TRY(hipSetDevice(device));
+    lrsc_index* idx = new(std::nothrow) lrsc_index();
+    if(!idx) return fail(LRSC_ERR_NOMEM, "lrsc_index");
+    idx->num_strings = n_reads;
+    idx->num_symbols = a->num_symbols + b->num_symbols;
+    idx->wide = idx->num_symbols >= (1ull << 31) || std::getenv("LRSC_FORCE_WIDE") != nullptr;   // as index_from_units_impl
+    std::vector<uint8_t> origin(dollar_origin ? 2 * n_reads : 0);
+    DeviceCopy dc;
+    double ms[4] = {0., 0., 0., 0.};
+    std::string err;
+    for(int s = 0; s < 2 && st == LRSC_OK; ++s) {
+        st = merge_strand(fa[s], wide_a, fb[s], wide_b, s, idx->wide, dollar_origin ? origin.data() + s * n_reads : nullptr, idx->image[s], dc, ms, err);
+        if(st != LRSC_OK) st = fail(st, err);
+    }
+    if(st == LRSC_OK && (idx->image[0].dollars.size() != n_reads || idx->image[1].dollars.size() != n_reads))
+        st = fail(LRSC_ERR_DEVICE, "index merge: the '$' rows of the result are not those of its inputs");
+    if(st == LRSC_OK) {
+        const auto t0 = std::chrono::steady_clock::now();
+        std::lock_guard<std::mutex> lock(idx->mu);
+        st = register_copy(idx, device, dc);
+        ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    if(st != LRSC_OK) { free_device_copy(dc); delete idx; return st; }
+    if(std::getenv("LRSC_BWT_PROFILE"))
+        std::fprintf(stderr, "[lrsc] index merge: walk %.3f ms, interleave %.3f ms, pack %.3f ms, tables %.3f ms\n", ms[0], ms[1], ms[2], ms[3]);
+    if(dollar_origin) std::memcpy(dollar_origin, origin.data(), origin.size());
     *out = idx;
     return LRSC_OK;
 }

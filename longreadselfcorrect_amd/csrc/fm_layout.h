@@ -1,6 +1,8 @@
 // fm_layout.h -- host image of the FM-index in the HBM block layout (see fm_device.h).
 #pragma once
+#include <cstddef>
 #include <cstdint>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -8,8 +10,21 @@
 
 namespace lrsc {
 
+// Host memory at the rank blocks' own alignment: the image's bytes are read and written as Block32 / Block64 (alignas(64)).
+template <class T>
+struct BlockAligned {
+    using value_type = T;
+    BlockAligned() = default;
+    template <class U> BlockAligned(const BlockAligned<U>&) {}
+    T* allocate(std::size_t n) { return static_cast<T*>(::operator new(n * sizeof(T), std::align_val_t(alignof(Block32)))); }
+    void deallocate(T* p, std::size_t) { ::operator delete(p, std::align_val_t(alignof(Block32))); }
+    template <class U> bool operator==(const BlockAligned<U>&) const { return true; }
+    template <class U> bool operator!=(const BlockAligned<U>&) const { return false; }
+};
+static_assert(alignof(Block32) == alignof(Block64), "one alignment for both layouts");
+
 struct StrandImage {
-    std::vector<uint8_t> blocks;      // n_blocks * 64 bytes (Block32 or Block64)
+    std::vector<uint8_t, BlockAligned<uint8_t>> blocks;   // n_blocks * 64 bytes (Block32 or Block64)
     std::vector<uint64_t> dollars;    // sorted positions of '$' rows
     std::vector<uint32_t> dollar_dir; // '$' rows before every group of 2^kDollarDirShift blocks (+ one terminal entry)
     uint64_t n_blocks = 0;

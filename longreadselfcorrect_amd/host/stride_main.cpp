@@ -1,4 +1,4 @@
-// stride_main.cpp -- `stride pbcorrect` (a.k.a. PacBioSelfCorrection) and `stride index` on the
+// stride_main.cpp -- `stride pbcorrect` (a.k.a. PacBioSelfCorrection), `stride index` and `stride merge` on the
 // MI355X back end.  Option surface, defaults, validation messages and exit codes follow the reference's
 // StriDe/PacBioSelfCorrection.cpp:32-140,262-434 and StriDe/StriDe.cpp:62-126; extra flags: --devices, --batch.
 #include <getopt.h>
@@ -41,6 +41,8 @@ static const char* CORRECT_USAGE_MESSAGE =
     "      -p, --prefix=PREFIX              Use PREFIX for the names of the index files\n"
     "      --build-index                    Index READSFILE in memory on the first device instead of loading PREFIX.bwt/.rbwt\n"
     "      --save-index=PREFIX              With --build-index: write the built index to PREFIX.bwt/.rbwt/.sai/.rsai\n"
+    "      --merge-index=PREFIX             With --build-index: correct against the index of PREFIX's reads followed by READSFILE's,\n"
+    "                                       merged on the first device from PREFIX.bwt/.rbwt and the built index\n"
     "      --load-on-device                 With -p: decode PREFIX.bwt/.rbwt on the first device instead of on the host\n"
     "      -o, --output=DIR                 Output results in the directory\n"
     "      -b, --barcode=FILE               Barcode of raw reads\n"
@@ -69,7 +71,7 @@ static const char* CORRECT_USAGE_MESSAGE =
 
 namespace opt {
 static int thread = 1;
-static std::string prefix, directory, barcode, readsFile, saveIndex;
+static std::string prefix, directory, barcode, readsFile, saveIndex, mergeIndex;
 static size_t PBcoverage = 90;
 static double ErrorRate = 0.15;
 static int startKmerLen = 19, nextTarget = 1, maxLeaves = 32, idmerLen = 9, minKmerLen = 13, genome = 10, mode = 1, verbose = 0;
@@ -82,7 +84,7 @@ static bool buildIndex = false, loadOnDevice = false;
 }
 
 static const char* shortopts = "t:p:o:b:c:e:k:u:r:n:l:i:s:g:m:v";
-enum { OPT_HELP = 1, OPT_VERSION, OPT_SPLIT, OPT_FIRST, OPT_DEBUGEXTEND, OPT_DEBUGSEED, OPT_ONLYSEED, OPT_NODP, OPT_DEVICES, OPT_BATCH, OPT_WORKERS, OPT_BUILDINDEX, OPT_SAVEINDEX, OPT_LOADONDEVICE };
+enum { OPT_HELP = 1, OPT_VERSION, OPT_SPLIT, OPT_FIRST, OPT_DEBUGEXTEND, OPT_DEBUGSEED, OPT_ONLYSEED, OPT_NODP, OPT_DEVICES, OPT_BATCH, OPT_WORKERS, OPT_BUILDINDEX, OPT_SAVEINDEX, OPT_LOADONDEVICE, OPT_MERGEINDEX };
 static const struct option longopts[] = {
     {"thread", required_argument, nullptr, 't'},       {"prefix", required_argument, nullptr, 'p'},
     {"output", required_argument, nullptr, 'o'},       {"barcode", required_argument, nullptr, 'b'},
@@ -98,7 +100,7 @@ static const struct option longopts[] = {
     {"nodp", no_argument, nullptr, OPT_NODP},          {"devices", required_argument, nullptr, OPT_DEVICES},
     {"batch", required_argument, nullptr, OPT_BATCH},  {"workers-per-device", required_argument, nullptr, OPT_WORKERS},
     {"build-index", no_argument, nullptr, OPT_BUILDINDEX}, {"save-index", required_argument, nullptr, OPT_SAVEINDEX},
-    {"load-on-device", no_argument, nullptr, OPT_LOADONDEVICE},
+    {"load-on-device", no_argument, nullptr, OPT_LOADONDEVICE}, {"merge-index", required_argument, nullptr, OPT_MERGEINDEX},
     {nullptr, 0, nullptr, 0}};
 
 static void lrscOrDie(int st, const char* what)
@@ -150,6 +152,7 @@ static void parsePacBioSelfCorrectionOptions(int argc, char** argv)
             case OPT_BUILDINDEX: opt::buildIndex = true; break;
             case OPT_SAVEINDEX: arg >> opt::saveIndex; break;
             case OPT_LOADONDEVICE: opt::loadOnDevice = true; break;
+            case OPT_MERGEINDEX: arg >> opt::mergeIndex; break;
             default: die = true; break;
         }
     }
@@ -159,6 +162,7 @@ static void parsePacBioSelfCorrectionOptions(int argc, char** argv)
     if(opt::buildIndex && !opt::prefix.empty()) { std::cerr << SUBPROGRAM << ": --build-index reads no index files: give either it or -p\n"; die = true; }
     if(!opt::saveIndex.empty() && !opt::buildIndex) { std::cerr << SUBPROGRAM << ": --save-index writes the index that --build-index builds: give both\n"; die = true; }
     if(opt::loadOnDevice && opt::buildIndex) { std::cerr << SUBPROGRAM << ": --load-on-device decodes the index files that -p names: --build-index reads none\n"; die = true; }
+    if(!opt::mergeIndex.empty() && !opt::buildIndex) { std::cerr << SUBPROGRAM << ": --merge-index merges PREFIX with the index that --build-index builds: give both\n"; die = true; }
     if(opt::prefix.empty() && !opt::buildIndex) { std::cerr << SUBPROGRAM << ": no prefix\n"; die = true; }
     if(opt::directory.empty()) { std::cerr << SUBPROGRAM << ": no directory\n"; die = true; }
     else {
@@ -201,7 +205,7 @@ static void loadReads(const std::string& path, std::string& bases, std::vector<u
 // read back to its '$' row; that row's rank among the '$' rows is the rank of the read among all reads compared as
 // strings ('$' < A < C < G < T, so a proper prefix sorts first) with equal reads in input order (sentinel order
 // MR_SO_IO) -- computed directly here.  `pbcorrect` only needs the file to exist.
-static bool writeLexicoIndex(const std::string& path, const std::string& bases, const std::vector<uint64_t>& off, bool rev)
+static std::vector<uint32_t> lexicoOrder(const std::string& bases, const std::vector<uint64_t>& off, bool rev)
 {
     const uint32_t n = (uint32_t)(off.size() - 1);
     std::vector<uint32_t> order(n);
@@ -217,11 +221,44 @@ static bool writeLexicoIndex(const std::string& path, const std::string& bases, 
         if(lx != ly) return lx < ly;
         return x < y;
     });
+    return order;
+}
+static bool writeSai(const std::string& path, const std::vector<uint32_t>& order)
+{
+    const size_t n = order.size();
     std::ofstream sai(path.c_str());
     sai << 51914 << "\n" << n << "\n" << n << "\n";
-    for(uint32_t i = 0; i < n; ++i) sai << order[i] << " 0\n";
+    for(size_t i = 0; i < n; ++i) sai << order[i] << " 0\n";
     if(!sai) { std::cerr << "index: cannot write " << path << "\n"; return false; }
     return true;
+}
+static bool writeLexicoIndex(const std::string& path, const std::string& bases, const std::vector<uint64_t>& off, bool rev)
+{
+    return writeSai(path, lexicoOrder(bases, off, rev));
+}
+// a .sai / .rsai file as writeSai leaves it: the read of every '$' row, in row order
+static bool readSai(const std::string& path, uint64_t n_reads, std::vector<uint32_t>& order)
+{
+    std::ifstream sai(path.c_str());
+    uint64_t magic = 0, n = 0, n2 = 0;
+    sai >> magic >> n >> n2;
+    order.assign(sai && magic == 51914 && n == n2 && n == n_reads ? n : 0, 0);
+    uint64_t zero = 0;
+    for(uint32_t& id : order) sai >> id >> zero;
+    if(!sai || order.size() != n_reads) { std::cerr << "merge: " << path << " is no lexicographic index of " << n_reads << " reads\n"; return false; }
+    return true;
+}
+// the union's list from its inputs': row k is b's next entry, its read ids behind a's, where from_b[k] is set, else a's next
+// (lrsc_index_merge's dollar_origin of that strand)
+static std::vector<uint32_t> mergeSai(const std::vector<uint32_t>& a, const std::vector<uint32_t>& b, const uint8_t* from_b)
+{
+    std::vector<uint32_t> out(a.size() + b.size());
+    size_t ia = 0, ib = 0;
+    for(size_t k = 0; k < out.size(); ++k) {
+        if(from_b[k] ? ib >= b.size() : ia >= a.size()) { std::cerr << "merge: the '$' rows of the merged index do not add up\n"; exit(EXIT_FAILURE); }
+        out[k] = from_b[k] ? (uint32_t)(b[ib++] + a.size()) : a[ia++];
+    }
+    return out;
 }
 
 static int PacBioSelfCorrectionMain(int argc, char** argv)
@@ -237,10 +274,33 @@ static int PacBioSelfCorrectionMain(int argc, char** argv)
         std::vector<uint64_t> off;
         loadReads(opt::readsFile, bases, off);
         lrscOrDie(lrsc_index_build(bases.data(), off.data(), (uint32_t)(off.size() - 1), opt::devices[0], &idx), "lrsc_index_build");
+        std::vector<uint32_t> order[2];
+        if(!opt::saveIndex.empty())
+            for(int rev = 0; rev < 2; ++rev) order[rev] = lexicoOrder(bases, off, rev != 0);
+        if(!opt::mergeIndex.empty()) {
+            // the index to correct against: PREFIX's reads, then the reads just indexed
+            std::cerr << "Merging it with " << opt::mergeIndex + BWT_EXT << " and " << opt::mergeIndex + RBWT_EXT << "\n";
+            lrsc_index *old = nullptr, *both = nullptr;
+            lrscOrDie(lrsc_index_open_device((opt::mergeIndex + BWT_EXT).c_str(), (opt::mergeIndex + RBWT_EXT).c_str(), opt::devices[0], &old), "lrsc_index_open_device");
+            lrsc_index_info io, in;
+            lrscOrDie(lrsc_index_info_get(old, &io), "lrsc_index_info_get");
+            lrscOrDie(lrsc_index_info_get(idx, &in), "lrsc_index_info_get");
+            const uint64_t n_all = io.num_strings + in.num_strings;
+            std::vector<uint8_t> origin(opt::saveIndex.empty() ? 0 : 2 * n_all);
+            lrscOrDie(lrsc_index_merge(old, idx, opt::devices[0], &both, origin.empty() ? nullptr : origin.data()), "lrsc_index_merge");
+            lrsc_index_close(old);
+            lrsc_index_close(idx);
+            idx = both;
+            for(int rev = 0; rev < 2 && !opt::saveIndex.empty(); ++rev) {
+                std::vector<uint32_t> had;
+                if(!readSai(opt::mergeIndex + (rev ? ".rsai" : ".sai"), io.num_strings, had)) exit(EXIT_FAILURE);
+                order[rev] = mergeSai(had, order[rev], origin.data() + rev * n_all);
+            }
+        }
         if(!opt::saveIndex.empty()) {
             lrscOrDie(lrsc_index_write(idx, opt::devices[0], (opt::saveIndex + BWT_EXT).c_str(), (opt::saveIndex + RBWT_EXT).c_str()), "lrsc_index_write");
             for(int rev = 0; rev < 2; ++rev)
-                if(!writeLexicoIndex(opt::saveIndex + (rev ? ".rsai" : ".sai"), bases, off, rev != 0)) exit(EXIT_FAILURE);
+                if(!writeSai(opt::saveIndex + (rev ? ".rsai" : ".sai"), order[rev])) exit(EXIT_FAILURE);
         }
     } else {
         std::cerr << "Loading BWT: " << opt::prefix + BWT_EXT << "\n" << "Loading RBWT: " << opt::prefix + RBWT_EXT << "\n";
@@ -325,15 +385,73 @@ static int indexMain(int argc, char** argv)
     return 0;
 }
 
+// `stride merge -p OUT PREFIX_A PREFIX_B [PREFIX_C ...]`: the index of A's reads followed by B's (then C's ...), merged on the
+// device from the saved indexes; what `stride index` writes for the concatenated read files
+static const char* MERGE_USAGE_MESSAGE =
+    "Usage: " PACKAGE_NAME " merge -p OUT [--device=N] PREFIX_A PREFIX_B [PREFIX_C ...]\n"
+    "Merge the FM-indexes PREFIX_A, PREFIX_B, ... (.bwt, .rbwt, .sai, .rsai) into the index OUT of all their reads, in that order\n"
+    "\n"
+    "      -p, --prefix=OUT                 Write OUT.bwt, OUT.rbwt, OUT.sai and OUT.rsai\n"
+    "      --device=N                       HIP device to merge on (default: 0)\n"
+    "      --help                           Display this help and exit\n\n";
+
+static int mergeMain(int argc, char** argv)
+{
+    std::string prefix;
+    std::vector<std::string> inputs;
+    int device = 0;
+    for(int i = 1; i < argc; ++i) {
+        const std::string a = argv[i];
+        if((a == "-p" || a == "--prefix") && i + 1 < argc) prefix = argv[++i];
+        else if(a.rfind("--prefix=", 0) == 0) prefix = a.substr(9);
+        else if(a.rfind("--device=", 0) == 0) device = atoi(a.c_str() + 9);
+        else if(a == "--help") { std::cerr << MERGE_USAGE_MESSAGE; return 0; }
+        else if(!a.empty() && a[0] != '-') inputs.push_back(a);
+        else { std::cerr << "merge: unrecognized option " << a << "\n\n" << MERGE_USAGE_MESSAGE; return EXIT_FAILURE; }
+    }
+    if(prefix.empty()) { std::cerr << "merge: no prefix for the merged index (-p)\n\n" << MERGE_USAGE_MESSAGE; return EXIT_FAILURE; }
+    if(inputs.size() < 2) { std::cerr << "merge: at least two indexes to merge\n\n" << MERGE_USAGE_MESSAGE; return EXIT_FAILURE; }
+
+    struct Part { lrsc_index* idx = nullptr; uint64_t n_reads = 0; std::vector<uint32_t> order[2]; };
+    auto open = [&](const std::string& p) {
+        Part part;
+        lrscOrDie(lrsc_index_open_device((p + BWT_EXT).c_str(), (p + RBWT_EXT).c_str(), device, &part.idx), "lrsc_index_open_device");
+        lrsc_index_info info;
+        lrscOrDie(lrsc_index_info_get(part.idx, &info), "lrsc_index_info_get");
+        part.n_reads = info.num_strings;
+        for(int rev = 0; rev < 2; ++rev)
+            if(!readSai(p + (rev ? ".rsai" : ".sai"), part.n_reads, part.order[rev])) exit(EXIT_FAILURE);
+        return part;
+    };
+    std::cout << "Merging " << inputs.size() << " indexes on the GPU\n";
+    Part cur = open(inputs[0]);
+    for(size_t k = 1; k < inputs.size(); ++k) {                   // ((A + B) + C) ...
+        Part next = open(inputs[k]), both;
+        both.n_reads = cur.n_reads + next.n_reads;
+        std::vector<uint8_t> origin(2 * both.n_reads);
+        lrscOrDie(lrsc_index_merge(cur.idx, next.idx, device, &both.idx, origin.data()), "lrsc_index_merge");
+        for(int rev = 0; rev < 2; ++rev) both.order[rev] = mergeSai(cur.order[rev], next.order[rev], origin.data() + rev * both.n_reads);
+        lrsc_index_close(cur.idx);
+        lrsc_index_close(next.idx);
+        cur = std::move(both);
+    }
+    lrscOrDie(lrsc_index_write(cur.idx, device, (prefix + BWT_EXT).c_str(), (prefix + RBWT_EXT).c_str()), "lrsc_index_write");
+    for(int rev = 0; rev < 2; ++rev)
+        if(!writeSai(prefix + (rev ? ".rsai" : ".sai"), cur.order[rev])) return EXIT_FAILURE;
+    lrsc_index_close(cur.idx);
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
     // several workers on one device (--devices 0,0) only overlap if their streams get hardware queues of their own (default: 4)
     setenv("GPU_MAX_HW_QUEUES", "16", 0);
-    if(argc <= 1) { std::cerr << "Usage: " PACKAGE_NAME " <command> [options]\nCommands: index, pbcorrect, kmerfreq, kmercheck\n"; return EXIT_FAILURE; }
+    if(argc <= 1) { std::cerr << "Usage: " PACKAGE_NAME " <command> [options]\nCommands: index, merge, pbcorrect, kmerfreq, kmercheck\n"; return EXIT_FAILURE; }
     const std::string command(argv[1]);
-    if(command == "help" || command == "--help") { std::cout << "Usage: " PACKAGE_NAME " <command> [options]\nCommands: index, pbcorrect, kmerfreq, kmercheck\n"; return 0; }
+    if(command == "help" || command == "--help") { std::cout << "Usage: " PACKAGE_NAME " <command> [options]\nCommands: index, merge, pbcorrect, kmerfreq, kmercheck\n"; return 0; }
     if(command == "pbcorrect" || command == SUBPROGRAM) return PacBioSelfCorrectionMain(argc - 1, argv + 1);
     if(command == "index") return indexMain(argc - 1, argv + 1);
+    if(command == "merge") return mergeMain(argc - 1, argv + 1);
     if(command == "kmerfreq") return kmerfreqMain(argc - 1, argv + 1);
     if(command == "kmercheck") return kmercheckMain(argc - 1, argv + 1);
     std::cerr << "Unrecognized command: " << command << "\n";

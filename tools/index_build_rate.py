@@ -28,7 +28,13 @@ lrsc_index_upload against lrsc_index_open_device, alternating, --runs of each af
 its two calls (read + decode on two host threads; copy + k-mer tables) beside a plain read of both files; the device route's come
 from its LRSC_BWT_PROFILE lines (file read, units to the device, decode + pack, image to the host, tables).  The decoder's kernel
 times come from a child run of lrsc_index_open_device on the same files under `rocprofv3 --kernel-trace --stats`, as bytes/s
-counting the units each kernel reads and the blocks the pack kernel writes.  Writes profiles/index_open.json (or --out)."""
+counting the units each kernel reads and the blocks the pack kernel writes.  Writes profiles/index_open.json (or --out).
+
+--merge measures the device merge (csrc/fm_merge.hip): adding reads to an index that exists.  A = the first 90 % of the reads and
+B = the last 10 % are built once and stay resident; then lrsc_index_merge(A, B) against lrsc_index_build of all the reads,
+alternating, --runs of each after a warm-up of each.  The merge's stages come from its LRSC_BWT_PROFILE line (walk, interleave, pack,
+tables), the rebuild's from lrsc_index_build's; the device-memory peak of either is what it takes above A and B.  Writes
+profiles/index_merge.json (or --out)."""
 from __future__ import annotations
 
 import argparse
@@ -382,17 +388,92 @@ def open_main(args, api, hip, bases, off, n_sym):
     print(json.dumps(result))
 
 
+def with_profile_line(work: Path, fn):
+    """fn() with LRSC_BWT_PROFILE set and this process's stderr in a file for the length of the call -> (result, the text)"""
+    log = work / "call.err"
+    sys.stderr.flush()
+    saved = os.dup(2)
+    fd = os.open(log, os.O_WRONLY | os.O_CREAT | os.O_TRUNC)
+    os.dup2(fd, 2)
+    os.environ["LRSC_BWT_PROFILE"] = "1"
+    try:
+        out = fn()
+    finally:
+        del os.environ["LRSC_BWT_PROFILE"]
+        os.dup2(saved, 2)
+        os.close(fd)
+        os.close(saved)
+    return out, log.read_text()
+
+
+def merge_main(args, api, hip, bases, off, n_sym):
+    n_reads = off.size - 1
+    cut = n_reads * 9 // 10
+    at = int(off[cut])
+    part_a = (bases[:at], off[: cut + 1].copy())
+    part_b = (bases[at:], (off[cut:] - off[cut]).astype(off.dtype))
+    setup = {}
+    a = clock(setup, "index_build_a", lambda: api.index_build(*part_a, 0))
+    b = clock(setup, "index_build_b", lambda: api.index_build(*part_b, 0))
+    say(f"A: {cut} reads, B: {n_reads - cut} reads, built in {setup}")
+
+    def route_merge(api_, _bases, _off, work):
+        st = {}
+        idx, text = with_profile_line(work, lambda: clock(st, "index_merge", lambda: api_.index_merge(a, b, 0)))
+        m = re.search(r"index merge: walk ([\d.]+) ms, interleave ([\d.]+) ms, pack ([\d.]+) ms, tables ([\d.]+) ms", text)
+        if m:
+            st["walk"], st["interleave"], st["pack"], st["tables"] = (float(x) / 1e3 for x in m.groups())
+        return idx, st
+
+    with tempfile.TemporaryDirectory() as d:
+        work = Path(d)
+        routes = {"merge": route_merge, "rebuild": route_build}
+        units = {}
+        for name, fn in routes.items():                           # warm-up, and the two routes' indexes are one
+            idx, _ = fn(api, bases, off, work)
+            units[name] = [hash(idx.units(s, 0).tobytes()) for s in (0, 1)]
+            idx.close()
+        assert units["merge"] == units["rebuild"], "the merged index is not the rebuilt one"
+        runs = {k: [] for k in routes}
+        for i in range(args.runs):
+            for name, fn in routes.items():
+                r = run(api, hip, fn, bases, off, work)
+                runs[name].append(r)
+                say(f"run {i} {name}: {r['wall_s']:.2f} s {r['stages_s']} peak {r['device_peak_bytes'] / 2**30:.2f} GiB")
+    walls = {k: [r["wall_s"] for r in v] for k, v in runs.items()}
+    n_b = int(part_b[1][-1]) + n_reads - cut
+    result = {
+        "workload": {"genome_mb": args.genome_mb, "reads": n_reads, "symbols_per_strand": n_sym, "reads_a": cut, "reads_b": n_reads - cut,
+                     "symbols_per_strand_b": n_b},
+        "setup_s": setup,
+        "runs": runs,
+        "wall_s": {k: {"all": v, "min": min(v), "max": max(v), "spread": max(v) - min(v)} for k, v in walls.items()},
+        "merge_below_rebuild_in_every_pairing": max(walls["merge"]) < min(walls["rebuild"]),
+        "merge_over_rebuild": {"best": min(walls["merge"]) / max(walls["rebuild"]), "worst": max(walls["merge"]) / min(walls["rebuild"])},
+        # above the resident A and B: one strand's BWT and ranks or packer workspace, the packed images, the k-mer tables
+        "device_peak_bytes": {k: max(r["device_peak_bytes"] for r in v) for k, v in runs.items()},
+        "bwt_plus_ranks_bytes": n_sym + 8 * n_b,
+    }
+    a.close()
+    b.close()
+    out = args.out or str(REPO / "profiles" / "index_merge.json")
+    Path(out).parent.mkdir(parents=True, exist_ok=True)
+    Path(out).write_text(json.dumps(result, indent=1) + "\n")
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--genome-mb", type=float, default=11.1)
     ap.add_argument("--reads", type=int, default=100000)
     ap.add_argument("--runs", type=int, default=2)
-    ap.add_argument("--out", default=None, help="default: profiles/index_in_memory.json; profiles/index_rle.json with --rle, index_open.json with --open")
+    ap.add_argument("--out", default=None, help="default: profiles/index_in_memory.json; profiles/index_rle.json with --rle, index_open.json with --open, index_merge.json with --merge")
     ap.add_argument("--rle", action="store_true", help="measure the device RL encoder instead (see the module text)")
     ap.add_argument("--rle-call-only", action="store_true", help="the encoder's calls once (the child run under the profiler)")
     ap.add_argument("--call-only", action="store_true", help="one lrsc_index_build (the child run under the profiler)")
     ap.add_argument("--open", action="store_true", help="measure the device RL decoder instead (see the module text)")
     ap.add_argument("--open-call-only", action="store_true", help="one lrsc_index_open_device of --files (the child run under the profiler)")
+    ap.add_argument("--merge", action="store_true", help="measure the device merge instead (see the module text)")
     ap.add_argument("--files", nargs=2, metavar=("BWT", "RBWT"))
     ap.add_argument("--no-profile", action="store_true")
     args = ap.parse_args()
@@ -410,6 +491,8 @@ def main():
         return rle_main(args, api, bases, off, n_sym)
     if args.open:
         return open_main(args, api, hip, bases, off, n_sym)
+    if args.merge:
+        return merge_main(args, api, hip, bases, off, n_sym)
     if args.call_only:
         api.index_build(bases, off, 0).close()
         return
