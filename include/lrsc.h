@@ -11,6 +11,8 @@
  *                         (loaded at StriDe/PacBioSelfCorrection.cpp:155-172)
  *   lrsc_rank             RLBWT::getOcc / getPC                    SuffixTools/RLBWT.h:118-140
  *   lrsc_bwt_chars        RLBWT::getChar                           SuffixTools/RLBWT.h:42-63
+ *   lrsc_index_locate_*,  SampledSuffixArray::build / buildLexicoIndex / calcSA    SuffixTools/SampledSuffixArray.cpp:44-190
+ *   lrsc_index_lexico_order, lrsc_locate
  *   lrsc_find_kmers       BWTAlgorithms::findInterval/findBiInterval  SuffixTools/BWTAlgorithms.cpp:14-38
  *   lrsc_kmer_grid        KmerFeature grid of LongReadProbe::getSeqAttribute
  *                         PacBio/LongReadProbe.cpp:139-150, PacBio/KmerFeature.h:37-64,92-99
@@ -160,6 +162,24 @@ int lrsc_index_units(lrsc_index* idx, int strand, int device, uint8_t** units_ou
 /* Both strands through lrsc_index_units and lrsc_write_bwt_file's header and layout. */
 int lrsc_index_write(lrsc_index* idx, int device, const char* bwt_path, const char* rbwt_path);
 
+/* ---- locate: which read and offset a BWT row belongs to (SuffixTools/SampledSuffixArray.cpp) -------------------------- */
+/* SAElem (SuffixTools/SampledSuffixArray.h): SA[row] = the suffix of `read` that starts at `pos` (pos == the read's length at
+ * its sentinel row, 0 at its '$' row) */
+typedef struct lrsc_sa_elem { uint32_t read, pos; } lrsc_sa_elem;
+/* Builds both strands' locate tables on `device` from the resident copy and keeps them with that copy: order (k-th '$' row ->
+ * read), read lengths, and for sample_rate > 0 the SA of every row that is a multiple of sample_rate
+ * (SampledSuffixArray::build, SampledSuffixArray.cpp:90-155; 0 = the lexicographic index only, as SSA_FT_SAI /
+ * buildLexicoIndex, :158-190).  (num_symbols / sample_rate + 1) * 8 bytes per strand plus 8 bytes per read.
+ * A no-op when tables of the same rate are there; LRSC_ERR_ARG ("already prepared with rate R") for another rate: contexts may
+ * be using the tables.  LRSC_ERR_DEVICE if the index has no copy on `device`, LRSC_ERR_FORMAT for an index whose backward walks
+ * do not end (no BWT of a string set), LRSC_ERR_NOMEM when the tables do not fit; on an error nothing stays allocated.
+ * lrsc_index_close frees the tables. */
+int lrsc_index_locate_prepare(lrsc_index* idx, int device, uint32_t sample_rate);
+/* The .sai (strand LRSC_BWT) / .rsai (LRSC_RBWT) content, SampledSuffixArray::buildLexicoIndex + writeLexicoIndex
+ * (SampledSuffixArray.cpp:158-190,248-258): order[k] = the read of the k-th '$' row, read_len[i] = the length of read i
+ * (may be NULL); num_strings entries each.  Prepares with rate 0 if not prepared. */
+int lrsc_index_lexico_order(lrsc_index* idx, int strand, int device, uint32_t* order, uint32_t* read_len);
+
 /* ---- context ------------------------------------------------------------------------ */
 int lrsc_ctx_create(const lrsc_index* idx, const lrsc_params* params, int device, lrsc_ctx** out);
 void lrsc_ctx_destroy(lrsc_ctx* ctx);
@@ -173,6 +193,11 @@ int lrsc_bwt_chars(lrsc_ctx* ctx, int strand, const uint64_t* idx, uint64_t n, c
  * fwd searched in the rbwt with reverse(w), rvc in the bwt with revcomp(w), each stopping at
  * the first invalid interval exactly as BWTAlgorithms.cpp:14-31. */
 int lrsc_find_kmers(lrsc_ctx* ctx, const char* kmers, uint32_t k, uint64_t n, lrsc_biinterval* out);
+
+/* SampledSuffixArray::calcSA (SuffixTools/SampledSuffixArray.cpp:44-81) for n rows of `strand` (rows < num_symbols, LRSC_ERR_ARG
+ * otherwise), on the ctx's device, from the tables lrsc_index_locate_prepare left there (LRSC_ERR_DEVICE if there are none).
+ * For strand LRSC_RBWT, pos counts in the reversed read.  Counted under LRSC_K_LOCATE; rank_queries = LF steps. */
+int lrsc_locate(lrsc_ctx* ctx, int strand, const uint64_t* rows, uint64_t n, lrsc_sa_elem* out);
 
 /* ---- LongReadProbe k-mer feature grid -------------------------------------------------- */
 /* reads: concatenated ACGT bytes, read_off: n_reads+1 offsets.  ks: ascending k-mer sizes
@@ -433,9 +458,10 @@ typedef struct lrsc_kernel_stats {
 } lrsc_kernel_stats;
 /* LRSC_K_EXTEND_WIDE: the wide walk launches of max_leaves above 32 (one per round with escalated walks; none at <= 32)
  * LRSC_K_SAIPB: lrsc_saipb_merge's merge launches, one per workspace chunk; total_ms spans a call's chunks together, the query
- *   counters are not kept for it */
+ *   counters are not kept for it
+ * LRSC_K_LOCATE: lrsc_locate's launches; rank_queries = the LF steps taken */
 enum { LRSC_K_RANK = 0, LRSC_K_FIND = 1, LRSC_K_GRID = 2, LRSC_K_SEEDS = 3, LRSC_K_EXTEND = 4, LRSC_K_LF = 5, LRSC_K_DP = 6, LRSC_K_MSA = 7,
-       LRSC_K_EXTEND_WIDE = 8, LRSC_K_SAIPB = 9, LRSC_K_COUNT = 10 };
+       LRSC_K_EXTEND_WIDE = 8, LRSC_K_SAIPB = 9, LRSC_K_LOCATE = 10, LRSC_K_COUNT = 11 };
 int lrsc_ctx_stats(lrsc_ctx* ctx, int kernel, lrsc_kernel_stats* out);
 int lrsc_ctx_stats_reset(lrsc_ctx* ctx);
 /* Block until everything queued on the ctx stream is done. */

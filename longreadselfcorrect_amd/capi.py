@@ -185,13 +185,14 @@ class KernelStats(C.Structure):
     ]
 
 
-K_RANK, K_FIND, K_GRID, K_SEEDS, K_EXTEND, K_LF, K_DP, K_MSA, K_EXTEND_WIDE, K_SAIPB = range(10)
+K_RANK, K_FIND, K_GRID, K_SEEDS, K_EXTEND, K_LF, K_DP, K_MSA, K_EXTEND_WIDE, K_SAIPB, K_LOCATE = range(11)
 SEED_DTYPE = np.dtype([("start", "<i4"), ("len", "<i4"), ("max_freq", "<i4"), ("repeat", "<i4"), ("start_k", "<i4"),
                        ("end_k", "<i4"), ("start_freq", "<i4"), ("end_freq", "<i4")])
 BWT, RBWT = 0, 1
 
 RANK_DTYPE = np.dtype([("idx", "<i8"), ("base", "u1"), ("strand", "u1"), ("pad", "u1", (6,))])
 BIIV_DTYPE = np.dtype([("fwd_lower", "<i8"), ("fwd_upper", "<i8"), ("rvc_lower", "<i8"), ("rvc_upper", "<i8")])
+SA_DTYPE = np.dtype([("read", "<u4"), ("pos", "<u4")])          # lrsc_sa_elem
 assert RANK_DTYPE.itemsize == C.sizeof(RankQuery) and BIIV_DTYPE.itemsize == C.sizeof(BiInterval)
 
 
@@ -242,6 +243,9 @@ class Lrsc:
         L.lrsc_write_bwt_file.argtypes = [C.c_char_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64]
         L.lrsc_index_units.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         L.lrsc_index_write.argtypes = [C.c_void_p, C.c_int, C.c_char_p, C.c_char_p]
+        L.lrsc_index_locate_prepare.argtypes = [C.c_void_p, C.c_int, C.c_uint32]
+        L.lrsc_index_lexico_order.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.lrsc_locate.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
         L.lrsc_params_default.argtypes = [C.c_int, C.c_int, C.POINTER(Params)]
         L.lrsc_ctx_create.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int, C.POINTER(C.c_void_p)]
         L.lrsc_ctx_destroy.argtypes = [C.c_void_p]
@@ -287,6 +291,7 @@ class Lrsc:
         # the synthetic workload generator + test hook live in their own library (longreadselfcorrect_amd/testkit), not in the ABI
         self.kit = K = C.CDLL(str(lib_path().with_name("liblrsc_testkit.so")))
         K.lrsc_debug_sort_order.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
+        K.lrsc_host_lexico_order.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
         K.lrsc_synth_genome.argtypes = [C.c_uint64, C.c_uint64, C.c_void_p]
         K.lrsc_synth_reads.argtypes = [C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32,
                                        C.c_double, C.c_double, C.c_double, C.c_void_p, C.c_uint64, C.c_void_p]
@@ -306,6 +311,14 @@ class Lrsc:
         perm = np.zeros(keys.size, dtype=np.uint32)
         self.check(self.kit.lrsc_debug_sort_order(_ptr(keys), keys.size, _ptr(perm)), "lrsc_debug_sort_order")
         return perm
+
+    def host_lexico_order(self, bases: np.ndarray, off: np.ndarray, reverse_reads: bool) -> np.ndarray:
+        """The .sai / .rsai order by the host sort of whole reads that `stride index` uses (the testkit's hook into it)."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        order = np.empty(off.size - 1, dtype=np.uint32)
+        self.check(self.kit.lrsc_host_lexico_order(_ptr(bases), _ptr(off), off.size - 1, int(reverse_reads), _ptr(order)), "lrsc_host_lexico_order")
+        return order
 
     def kmer_thresholds(self, coverage: int) -> np.ndarray:
         out = np.zeros((3, 52), dtype=np.float32)
@@ -432,6 +445,20 @@ class Index:
         """Both strands as the reference's .bwt/.rbwt files, from the copy on `device`."""
         self.api.check(self.api.lib.lrsc_index_write(self.h, device, str(bwt_path).encode(), str(rbwt_path).encode()), "lrsc_index_write")
 
+    def locate_prepare(self, sample_rate: int = 0, device: int = 0):
+        """Both strands' locate tables on `device`, kept with the copy there: order, read lengths and, for sample_rate > 0, the
+        suffix array of every row that is a multiple of it."""
+        self.api.check(self.api.lib.lrsc_index_locate_prepare(self.h, device, sample_rate), "lrsc_index_locate_prepare")
+
+    def lexico_order(self, strand: int, device: int = 0, want_len: bool = False):
+        """The .sai (strand 0) / .rsai content: uint32 order[k] = the read of the k-th '$' row; with want_len also the read lengths."""
+        n = self.info().num_strings
+        order = np.empty(n, dtype=np.uint32)
+        read_len = np.empty(n, dtype=np.uint32) if want_len else None
+        self.api.check(self.api.lib.lrsc_index_lexico_order(self.h, strand, device, _ptr(order), _ptr(read_len) if want_len else None),
+                       "lrsc_index_lexico_order")
+        return (order, read_len) if want_len else order
+
     def ctx(self, params: Params | None = None, device: int = 0) -> "Ctx":
         h = C.c_void_p()
         pp = C.byref(params) if params is not None else None
@@ -467,6 +494,13 @@ class Ctx:
         idx = np.ascontiguousarray(idx, dtype=np.uint64)
         out = np.empty(idx.size, dtype=np.uint8)
         self.api.check(self.api.lib.lrsc_bwt_chars(self.h, strand, _ptr(idx), idx.size, _ptr(out)), "lrsc_bwt_chars")
+        return out
+
+    def locate(self, strand: int, rows: np.ndarray) -> np.ndarray:
+        """SA_DTYPE per row: the read the row's suffix belongs to and where in it the suffix starts (calcSA)."""
+        rows = np.ascontiguousarray(rows, dtype=np.uint64)
+        out = np.empty(rows.size, dtype=SA_DTYPE)
+        self.api.check(self.api.lib.lrsc_locate(self.h, strand, _ptr(rows), rows.size, _ptr(out)), "lrsc_locate")
         return out
 
     def find_kmers(self, kmers: np.ndarray, k: int) -> np.ndarray:

@@ -1,10 +1,11 @@
 // capi_index.cpp -- the index object (open / from units, on the host or on the device / build from reads / upload with its
 // k-mer tables / close), the
-// device BWT build, the merge of two resident indexes, the RL units of a resident copy and the file writer.
+// device BWT build, the merge of two resident indexes, the locate tables of a resident copy, its RL units and the file writer.
 #include <chrono>
 #include <thread>
 
 #include "capi_internal.h"
+#include "fm_locate.h"
 #include "fm_merge.h"
 #include "fm_pack.h"
 #include "fm_rle.h"
@@ -87,6 +88,8 @@ static void free_device_copy(DeviceCopy& dc)
         dc.blocks[s] = nullptr; dc.dollars[s] = nullptr; dc.dollar_dir[s] = nullptr;
     }
     for(int t = 0; t < 5; ++t) { if(dc.ktab[t]) (void)hipFree(dc.ktab[t]); dc.ktab[t] = nullptr; }
+    for(int s = 0; s < 2; ++s) locate_free_device(dc.locate[s]);
+    dc.located = false;
 }
 
 // first half of an upload: the host image of both strands -> the current device
@@ -510,6 +513,58 @@ extern "C" int lrsc_index_open_device(const char* bwt_path, const char* rbwt_pat
         std::fprintf(stderr, "[lrsc] index open on the device: file read %.3f ms\n",
                      std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     return index_from_units_device_impl(u[0].data(), u[0].size(), u[1].data(), u[1].size(), nstr[0], nsym[0], device, out);
+}
+
+// ---------------------------------------------------------------------------------------
+// the locate tables of a resident copy (fm_locate.hip)
+// ---------------------------------------------------------------------------------------
+// Builds both strands' tables of dc at `rate` on the current device.  The caller holds idx->mu; on an error dc has none.
+static int locate_prepare_copy(const lrsc_index* idx, DeviceCopy& dc, uint32_t rate)
+{
+    std::string err;
+    for(int s = 0; s < 2; ++s) {
+        const int st = locate_prepare_device(dc.dev.strand[s], idx->wide, rate, dc.locate[s], err);
+        if(st != LRSC_OK) {
+            for(int u = 0; u < s; ++u) locate_free_device(dc.locate[u]);
+            return fail(st, err);
+        }
+    }
+    dc.located = true;
+    return LRSC_OK;
+}
+
+extern "C" int lrsc_index_locate_prepare(lrsc_index* idx, int device, uint32_t sample_rate)
+{
+    if(!idx) return fail(LRSC_ERR_ARG, "null index");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    auto it = idx->copies.find(device);
+    if(it == idx->copies.end()) return fail(LRSC_ERR_DEVICE, "index not uploaded to this device (call lrsc_index_upload)");
+    DeviceCopy& dc = it->second;
+    if(dc.located) {
+        if(dc.locate[0].rate == sample_rate) return LRSC_OK;
+        return fail(LRSC_ERR_ARG, "locate tables already prepared with rate " + std::to_string(dc.locate[0].rate));
+    }
+    HIP_TRY(hipSetDevice(device));
+    return locate_prepare_copy(idx, dc, sample_rate);
+}
+
+extern "C" int lrsc_index_lexico_order(lrsc_index* idx, int strand, int device, uint32_t* order, uint32_t* read_len)
+{
+    if(!idx || !order) return fail(LRSC_ERR_ARG, "null");
+    if(strand != LRSC_BWT && strand != LRSC_RBWT) return fail(LRSC_ERR_ARG, "strand must be LRSC_BWT or LRSC_RBWT");
+    std::lock_guard<std::mutex> lock(idx->mu);
+    auto it = idx->copies.find(device);
+    if(it == idx->copies.end()) return fail(LRSC_ERR_DEVICE, "index not uploaded to this device (call lrsc_index_upload)");
+    DeviceCopy& dc = it->second;
+    HIP_TRY(hipSetDevice(device));
+    if(!dc.located) {
+        const int st = locate_prepare_copy(idx, dc, 0);
+        if(st != LRSC_OK) return st;
+    }
+    const LocateTables& t = dc.locate[strand];
+    HIP_TRY(hipMemcpy(order, t.order, idx->num_strings * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if(read_len) HIP_TRY(hipMemcpy(read_len, t.read_len, idx->num_strings * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    return LRSC_OK;
 }
 
 extern "C" int lrsc_index_units(lrsc_index* idx, int strand, int device, uint8_t** units_out, uint64_t* n_units_out)

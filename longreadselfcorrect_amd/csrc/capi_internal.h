@@ -19,6 +19,7 @@
 
 #include "../../include/lrsc.h"
 #include "fm_layout.h"
+#include "fm_locate.h"
 #include "kernels.h"
 #include "extend.h"
 #include "correct_dev.h"
@@ -98,6 +99,9 @@ struct DeviceCopy {
     uint32_t* dollar_dir[2] = {nullptr, nullptr};
     void* ktab[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
     FmIndexDev dev{};
+    // the locate tables of both strands (lrsc_index_locate_prepare); located = false: none yet
+    LocateTables locate[2];
+    bool located = false;
 };
 
 // The DP stage for a set of requests whose queries are already on the device: seeds -> (chunked by memory)
@@ -142,7 +146,7 @@ struct lrsc_index {
     uint64_t num_strings = 0;
     uint64_t num_symbols = 0;
     bool wide = false;
-    std::mutex mu;
+    mutable std::mutex mu;          // guards copies, the locate tables of a copy included
     std::map<int, lrsc::DeviceCopy> copies;
 };
 

@@ -1,4 +1,4 @@
-// capi_query.cpp -- point queries on a context: rank, BWT characters, LF walks, k-mer look-ups and the k-mer grid of a read set.
+// capi_query.cpp -- point queries on a context: rank, BWT characters, LF walks, locate, k-mer look-ups and the k-mer grid of a read set.
 #include "capi_internal.h"
 
 using namespace lrsc;
@@ -74,6 +74,38 @@ extern "C" int lrsc_lf_walk(lrsc_ctx* ctx, const uint64_t* rows, const uint8_t* 
     HIP_TRY(hipMemcpy(codes.data(), d_out.p, need, hipMemcpyDeviceToHost));
     for(uint64_t i = 0; i < n; ++i)
         for(uint32_t t = 0; t < out_len[i]; ++t) out[out_off[i] + t] = "ACGT"[codes[out_off[i] + t] & 3];
+    return LRSC_OK;
+}
+
+extern "C" int lrsc_locate(lrsc_ctx* ctx, int strand, const uint64_t* rows, uint64_t n, lrsc_sa_elem* out)
+{
+    if(!ctx || (!rows && n) || (!out && n)) return fail(LRSC_ERR_ARG, "null");
+    if(strand != LRSC_BWT && strand != LRSC_RBWT) return fail(LRSC_ERR_ARG, "strand must be LRSC_BWT or LRSC_RBWT");
+    const uint64_t N = ctx->index->num_symbols;
+    for(uint64_t i = 0; i < n; ++i)
+        if(rows[i] >= N) return fail(LRSC_ERR_ARG, "BWT row out of range");
+    // the tables of the ctx's device, under the index's mutex: lrsc_index_locate_prepare may be filling another copy's
+    std::lock_guard<std::mutex> lock(ctx->index->mu);
+    auto it = ctx->index->copies.find(ctx->device);
+    if(it == ctx->index->copies.end() || !it->second.located)
+        return fail(LRSC_ERR_DEVICE, "no locate tables on this device (call lrsc_index_locate_prepare)");
+    if(n == 0) return LRSC_OK;
+    const LocateTables& t = it->second.locate[strand];
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(ctx->s_in.reserve(n * sizeof(uint64_t)));
+    HIP_TRY(ctx->s_out.reserve(n * sizeof(lrsc_sa_elem)));
+    HIP_TRY(ctx->s_flag.reserve(1));
+    HIP_TRY(hipMemcpyAsync(ctx->s_in.p, rows, n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemsetAsync(ctx->s_flag.p, 0, sizeof(int), ctx->stream));
+    const int st = timed_launch(ctx, LRSC_K_LOCATE, [&]() {
+        return launch_locate(ctx->fm.strand[strand], ctx->fm.wide != 0, t, reinterpret_cast<const uint64_t*>(ctx->s_in.p), n,
+                             reinterpret_cast<SaElem*>(ctx->s_out.p), reinterpret_cast<uint32_t*>(ctx->s_flag.p), ctx->d_ctr, ctx->stream);
+    });
+    if(st != LRSC_OK) return st;
+    int broken = 0;
+    HIP_TRY(hipMemcpy(&broken, ctx->s_flag.p, sizeof(int), hipMemcpyDeviceToHost));
+    if(broken) return fail(LRSC_ERR_FORMAT, "locate: a backward walk does not end (the index is no BWT of a string set)");
+    HIP_TRY(hipMemcpy(out, ctx->s_out.p, n * sizeof(lrsc_sa_elem), hipMemcpyDeviceToHost));
     return LRSC_OK;
 }
 

@@ -91,6 +91,12 @@ hipError_t launch_rank(const FmIndexDev& fm, const lrsc_rank_query* q, uint64_t 
 struct LfJob { uint64_t row; uint64_t out_off; uint32_t max_steps; uint32_t strand; };
 hipError_t launch_lf_walk(const FmIndexDev& fm, const LfJob* jobs, uint64_t n, uint8_t* out, uint32_t* out_len,
                           DevCounters* ctr, hipStream_t stream);
+// SampledSuffixArray::calcSA of n rows of one strand (fm_locate.hip): out[i] = SA[rows[i]] from the strand's locate tables; *broken
+// is set to 1 when a walk does not end (an index that is no BWT of a string set); the LF steps go to ctr->rank_queries
+struct LocateTables;
+struct SaElem;
+hipError_t launch_locate(const FmStrand& s, bool wide, const LocateTables& t, const uint64_t* rows, uint64_t n, SaElem* out, uint32_t* broken,
+                         DevCounters* ctr, hipStream_t stream);
 hipError_t launch_bwt_chars(const FmIndexDev& fm, int strand, const uint64_t* idx, uint64_t n, char* out,
                             hipStream_t stream);
 hipError_t launch_find_kmers(const FmIndexDev& fm, const uint8_t* kmer_codes, uint32_t k, uint64_t n,

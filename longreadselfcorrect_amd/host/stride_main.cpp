@@ -1,5 +1,5 @@
-// stride_main.cpp -- `stride pbcorrect` (a.k.a. PacBioSelfCorrection), `stride index` and `stride merge` on the
-// MI355X back end.  Option surface, defaults, validation messages and exit codes follow the reference's
+// stride_main.cpp -- `stride pbcorrect` (a.k.a. PacBioSelfCorrection), `stride index`, `stride merge`, `stride sai` and
+// `stride grep` on the MI355X back end.  Option surface, defaults, validation messages and exit codes follow the reference's
 // StriDe/PacBioSelfCorrection.cpp:32-140,262-434 and StriDe/StriDe.cpp:62-126; extra flags: --devices, --batch.
 #include <getopt.h>
 
@@ -8,6 +8,7 @@
 #include <cstring>
 #include <fstream>
 #include <iostream>
+#include <map>
 #include <sstream>
 #include <algorithm>
 #include <string>
@@ -15,6 +16,7 @@
 
 #include "../../include/lrsc.h"
 #include "BCode.h"
+#include "LexicoOrder.h"
 #include "PacBioSelfCorrectionProcess.h"
 #include "SequenceProcessFramework.h"
 
@@ -201,27 +203,11 @@ static void loadReads(const std::string& path, std::string& bases, std::vector<u
 }
 
 // .sai / .rsai: lexicographic rank -> read index (SampledSuffixArray::buildLexicoIndex + writeLexicoIndex,
-// SuffixTools/SampledSuffixArray.cpp:158-190,248-258; text format of SAWriter.cpp:32-54).  The reference LF-walks each
-// read back to its '$' row; that row's rank among the '$' rows is the rank of the read among all reads compared as
-// strings ('$' < A < C < G < T, so a proper prefix sorts first) with equal reads in input order (sentinel order
-// MR_SO_IO) -- computed directly here.  `pbcorrect` only needs the file to exist.
+// SuffixTools/SampledSuffixArray.cpp:158-190,248-258; text format of SAWriter.cpp:32-54), here by the host sort of LexicoOrder.h:
+// the reads are in hand.  `pbcorrect` only needs the file to exist.
 static std::vector<uint32_t> lexicoOrder(const std::string& bases, const std::vector<uint64_t>& off, bool rev)
 {
-    const uint32_t n = (uint32_t)(off.size() - 1);
-    std::vector<uint32_t> order(n);
-    for(uint32_t i = 0; i < n; ++i) order[i] = i;
-    const char* B = bases.data();
-    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
-        const uint64_t lx = off[x + 1] - off[x], ly = off[y + 1] - off[y];
-        const uint64_t m = lx < ly ? lx : ly;
-        for(uint64_t t = 0; t < m; ++t) {
-            const char cx = rev ? B[off[x + 1] - 1 - t] : B[off[x] + t], cy = rev ? B[off[y + 1] - 1 - t] : B[off[y] + t];
-            if(cx != cy) return cx < cy;
-        }
-        if(lx != ly) return lx < ly;
-        return x < y;
-    });
-    return order;
+    return stride::lexicoOrder(bases.data(), off.data(), (uint32_t)(off.size() - 1), rev);
 }
 static bool writeSai(const std::string& path, const std::vector<uint32_t>& order)
 {
@@ -246,6 +232,15 @@ static bool readSai(const std::string& path, uint64_t n_reads, std::vector<uint3
     uint64_t zero = 0;
     for(uint32_t& id : order) sai >> id >> zero;
     if(!sai || order.size() != n_reads) { std::cerr << "merge: " << path << " is no lexicographic index of " << n_reads << " reads\n"; return false; }
+    return true;
+}
+// The '$' rows' reads of one strand of a saved index that is resident on `device`: its .sai / .rsai file where there is one,
+// read and checked as ever; else from the index itself (lrsc_index_lexico_order, the reference's buildLexicoIndex).
+static bool loadOrder(lrsc_index* idx, int device, const std::string& path, int rev, uint64_t n_reads, std::vector<uint32_t>& order)
+{
+    if(std::ifstream(path.c_str()).good()) return readSai(path, n_reads, order);
+    order.assign(n_reads, 0);
+    lrscOrDie(lrsc_index_lexico_order(idx, rev ? LRSC_RBWT : LRSC_BWT, device, order.data(), nullptr), "lrsc_index_lexico_order");
     return true;
 }
 // the union's list from its inputs': row k is b's next entry, its read ids behind a's, where from_b[k] is set, else a's next
@@ -288,14 +283,14 @@ static int PacBioSelfCorrectionMain(int argc, char** argv)
             const uint64_t n_all = io.num_strings + in.num_strings;
             std::vector<uint8_t> origin(opt::saveIndex.empty() ? 0 : 2 * n_all);
             lrscOrDie(lrsc_index_merge(old, idx, opt::devices[0], &both, origin.empty() ? nullptr : origin.data()), "lrsc_index_merge");
+            for(int rev = 0; rev < 2 && !opt::saveIndex.empty(); ++rev) {
+                std::vector<uint32_t> had;
+                if(!loadOrder(old, opt::devices[0], opt::mergeIndex + (rev ? ".rsai" : ".sai"), rev, io.num_strings, had)) exit(EXIT_FAILURE);
+                order[rev] = mergeSai(had, order[rev], origin.data() + rev * n_all);
+            }
             lrsc_index_close(old);
             lrsc_index_close(idx);
             idx = both;
-            for(int rev = 0; rev < 2 && !opt::saveIndex.empty(); ++rev) {
-                std::vector<uint32_t> had;
-                if(!readSai(opt::mergeIndex + (rev ? ".rsai" : ".sai"), io.num_strings, had)) exit(EXIT_FAILURE);
-                order[rev] = mergeSai(had, order[rev], origin.data() + rev * n_all);
-            }
         }
         if(!opt::saveIndex.empty()) {
             lrscOrDie(lrsc_index_write(idx, opt::devices[0], (opt::saveIndex + BWT_EXT).c_str(), (opt::saveIndex + RBWT_EXT).c_str()), "lrsc_index_write");
@@ -390,6 +385,7 @@ static int indexMain(int argc, char** argv)
 static const char* MERGE_USAGE_MESSAGE =
     "Usage: " PACKAGE_NAME " merge -p OUT [--device=N] PREFIX_A PREFIX_B [PREFIX_C ...]\n"
     "Merge the FM-indexes PREFIX_A, PREFIX_B, ... (.bwt, .rbwt, .sai, .rsai) into the index OUT of all their reads, in that order\n"
+    "(an input's .sai / .rsai may be missing: it is then taken from its .bwt / .rbwt)\n"
     "\n"
     "      -p, --prefix=OUT                 Write OUT.bwt, OUT.rbwt, OUT.sai and OUT.rsai\n"
     "      --device=N                       HIP device to merge on (default: 0)\n"
@@ -420,7 +416,7 @@ static int mergeMain(int argc, char** argv)
         lrscOrDie(lrsc_index_info_get(part.idx, &info), "lrsc_index_info_get");
         part.n_reads = info.num_strings;
         for(int rev = 0; rev < 2; ++rev)
-            if(!readSai(p + (rev ? ".rsai" : ".sai"), part.n_reads, part.order[rev])) exit(EXIT_FAILURE);
+            if(!loadOrder(part.idx, device, p + (rev ? ".rsai" : ".sai"), rev, part.n_reads, part.order[rev])) exit(EXIT_FAILURE);
         return part;
     };
     std::cout << "Merging " << inputs.size() << " indexes on the GPU\n";
@@ -442,16 +438,157 @@ static int mergeMain(int argc, char** argv)
     return 0;
 }
 
+// `stride sai -p PREFIX`: PREFIX.sai and PREFIX.rsai from PREFIX.bwt and PREFIX.rbwt alone, the reference's buildLexicoIndex +
+// writeLexicoIndex (SuffixTools/SampledSuffixArray.cpp:158-190,248-258) on an index that already exists
+static const char* SAI_USAGE_MESSAGE =
+    "Usage: " PACKAGE_NAME " sai -p PREFIX [--device=N]\n"
+    "Write the lexicographic index PREFIX.sai and PREFIX.rsai of the FM-index PREFIX.bwt and PREFIX.rbwt\n"
+    "\n"
+    "      -p, --prefix=PREFIX              Read PREFIX.bwt and PREFIX.rbwt, write PREFIX.sai and PREFIX.rsai\n"
+    "      --device=N                       HIP device to work on (default: 0)\n"
+    "      --help                           Display this help and exit\n\n";
+
+static int saiMain(int argc, char** argv)
+{
+    std::string prefix;
+    int device = 0;
+    for(int i = 1; i < argc; ++i) {
+        const std::string a = argv[i];
+        if((a == "-p" || a == "--prefix") && i + 1 < argc) prefix = argv[++i];
+        else if(a.rfind("--prefix=", 0) == 0) prefix = a.substr(9);
+        else if(a.rfind("--device=", 0) == 0) device = atoi(a.c_str() + 9);
+        else if(a == "--help") { std::cerr << SAI_USAGE_MESSAGE; return 0; }
+        else if(!a.empty() && a[0] != '-') { std::cerr << "sai: too many arguments\n\n" << SAI_USAGE_MESSAGE; return EXIT_FAILURE; }
+        else { std::cerr << "sai: unrecognized option " << a << "\n\n" << SAI_USAGE_MESSAGE; return EXIT_FAILURE; }
+    }
+    if(prefix.empty()) { std::cerr << "sai: no prefix of the index (-p)\n\n" << SAI_USAGE_MESSAGE; return EXIT_FAILURE; }
+    lrsc_index* idx = nullptr;
+    lrscOrDie(lrsc_index_open_device((prefix + BWT_EXT).c_str(), (prefix + RBWT_EXT).c_str(), device, &idx), "lrsc_index_open_device");
+    lrsc_index_info info;
+    lrscOrDie(lrsc_index_info_get(idx, &info), "lrsc_index_info_get");
+    std::cout << "Building the lexicographic index of " << prefix << " on the GPU\n";
+    for(int rev = 0; rev < 2; ++rev) {
+        std::vector<uint32_t> order(info.num_strings);
+        lrscOrDie(lrsc_index_lexico_order(idx, rev ? LRSC_RBWT : LRSC_BWT, device, order.data(), nullptr), "lrsc_index_lexico_order");
+        if(!writeSai(prefix + (rev ? ".rsai" : ".sai"), order)) return EXIT_FAILURE;
+    }
+    lrsc_index_close(idx);
+    return 0;
+}
+
+// `stride grep READSFILE < queries`: the reads that hold a substring, the reference's grep (StriDe/grep.cpp:56-138): per query
+// the rows of its interval in the .bwt, each located to its read (SampledSuffixArray::calcSA) and printed with the query's first
+// occurrence in yellow; then every distinct read once, in first-seen order
+static const char* GREP_USAGE_MESSAGE =
+    "Usage: " PACKAGE_NAME " grep [-p PREFIX] [--device=N] [--sample-rate=R] READSFILE\n"
+    "Print the reads of READSFILE that hold the substrings given on the standard input, separated by white space\n"
+    "\n"
+    "      -p, --prefix=PREFIX              Use the FM-index PREFIX.bwt and PREFIX.rbwt (default: READSFILE's name without its suffix)\n"
+    "      --device=N                       HIP device to work on (default: 0)\n"
+    "      --sample-rate=R                  Keep the suffix array of every R-th row; 0: walk every row back to the start of its read\n"
+    "                                       (default: 32)\n"
+    "      --help                           Display this help and exit\n\n";
+
+static int grepMain(int argc, char** argv)
+{
+    std::string prefix;
+    std::vector<std::string> files;
+    int device = 0;
+    long rate = 32;
+    for(int i = 1; i < argc; ++i) {
+        const std::string a = argv[i];
+        if((a == "-p" || a == "--prefix") && i + 1 < argc) prefix = argv[++i];
+        else if(a.rfind("--prefix=", 0) == 0) prefix = a.substr(9);
+        else if(a.rfind("--device=", 0) == 0) device = atoi(a.c_str() + 9);
+        else if(a.rfind("--sample-rate=", 0) == 0) {
+            char* end = nullptr;
+            rate = strtol(a.c_str() + 14, &end, 10);
+            if(end == a.c_str() + 14 || *end != 0 || rate < 0 || rate > 0x7FFFFFFFl) { std::cerr << "grep: invalid sample rate " << a.substr(14) << "\n\n" << GREP_USAGE_MESSAGE; return EXIT_FAILURE; }
+        }
+        else if(a == "--help") { std::cerr << GREP_USAGE_MESSAGE; return 0; }
+        else if(!a.empty() && a[0] != '-') files.push_back(a);
+        else { std::cerr << "grep: unrecognized option " << a << "\n\n" << GREP_USAGE_MESSAGE; return EXIT_FAILURE; }
+    }
+    if(files.empty()) { std::cerr << "grep: missing arguments\n\n" << GREP_USAGE_MESSAGE; return EXIT_FAILURE; }
+    if(files.size() > 1) { std::cerr << "grep: too many arguments\n\n" << GREP_USAGE_MESSAGE; return EXIT_FAILURE; }
+    const std::string& reads = files[0];
+    if(prefix.empty()) { prefix = reads.substr(reads.find_last_of('/') + 1); prefix = prefix.substr(0, prefix.find_last_of('.')); }
+
+    std::vector<SeqRecord> table;                                 // the reference's ReadTable
+    {
+        SeqReader reader(reads);
+        SeqRecord r;
+        while(reader.get(r)) { r.qual.clear(); table.push_back(r); }
+    }
+    lrsc_index* idx = nullptr;
+    lrsc_ctx* ctx = nullptr;
+    lrscOrDie(lrsc_index_open_device((prefix + BWT_EXT).c_str(), (prefix + RBWT_EXT).c_str(), device, &idx), "lrsc_index_open_device");
+    lrsc_index_info info;
+    lrscOrDie(lrsc_index_info_get(idx, &info), "lrsc_index_info_get");
+    if(info.num_strings != table.size()) { std::cerr << "grep: " << prefix << " is no index of the " << table.size() << " reads of " << reads << "\n"; return EXIT_FAILURE; }
+    lrscOrDie(lrsc_index_locate_prepare(idx, device, (uint32_t)rate), "lrsc_index_locate_prepare");
+    lrscOrDie(lrsc_ctx_create(idx, nullptr, device, &ctx), "lrsc_ctx_create");
+
+    // the queries; their intervals in the .bwt, one lrsc_find_kmers call per length (field rvc of the reverse complement's search)
+    std::vector<std::string> queries;
+    for(std::string q; std::cin >> q;) queries.push_back(q);
+    std::vector<lrsc_interval> interval(queries.size(), lrsc_interval{0, -1});
+    std::map<size_t, std::vector<size_t>> by_len;
+    for(size_t i = 0; i < queries.size(); ++i)
+        if(queries[i].find_first_not_of("ACGT") == std::string::npos) by_len[queries[i].size()].push_back(i);
+    for(const auto& kv : by_len) {
+        std::string kmers;
+        for(size_t i : kv.second) {
+            const std::string& q = queries[i];
+            for(size_t t = q.size(); t-- > 0;) kmers += q[t] == 'A' ? 'T' : q[t] == 'C' ? 'G' : q[t] == 'G' ? 'C' : 'A';
+        }
+        std::vector<lrsc_biinterval> iv(kv.second.size());
+        lrscOrDie(lrsc_find_kmers(ctx, kmers.data(), (uint32_t)kv.first, kv.second.size(), iv.data()), "lrsc_find_kmers");
+        for(size_t j = 0; j < kv.second.size(); ++j) interval[kv.second[j]] = iv[j].rvc;
+    }
+    // every row of every interval, located in one call
+    std::vector<uint64_t> rows;
+    for(const lrsc_interval& iv : interval)
+        for(int64_t r = iv.lower; r <= iv.upper; ++r) rows.push_back((uint64_t)r);
+    std::vector<lrsc_sa_elem> sa(rows.size());
+    lrscOrDie(lrsc_locate(ctx, LRSC_BWT, rows.data(), rows.size(), sa.data()), "lrsc_locate");
+
+    const char *yellow = "\033[33m", *plain = "\033[0m";
+    std::vector<uint32_t> seen_order;
+    std::vector<uint8_t> seen(table.size(), 0);
+    size_t at = 0;
+    for(size_t i = 0; i < queries.size(); ++i) {
+        const std::string& q = queries[i];
+        std::cout << "--\n";
+        for(int64_t r = interval[i].lower; r <= interval[i].upper; ++r, ++at) {
+            const uint32_t id = sa[at].read;
+            const size_t found = id < table.size() ? table[id].seq.find(q) : std::string::npos;
+            if(found == std::string::npos) { std::cerr << "grep: " << prefix << " is no index of the reads of " << reads << "\n"; return EXIT_FAILURE; }
+            const std::string& read = table[id].seq;
+            if(!seen[id]) { seen[id] = 1; seen_order.push_back(id); }
+            std::cout << table[id].id << "\n" << read.substr(0, found) << yellow << read.substr(found, q.size()) << plain << read.substr(found + q.size()) << "\n";
+        }
+        std::cout << "--\n";
+    }
+    for(uint32_t id : seen_order) std::cout << ">" << table[id].id << "\n" << table[id].seq << "\n";
+    std::cout.flush();
+    lrsc_ctx_destroy(ctx);
+    lrsc_index_close(idx);
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
     // several workers on one device (--devices 0,0) only overlap if their streams get hardware queues of their own (default: 4)
     setenv("GPU_MAX_HW_QUEUES", "16", 0);
-    if(argc <= 1) { std::cerr << "Usage: " PACKAGE_NAME " <command> [options]\nCommands: index, merge, pbcorrect, kmerfreq, kmercheck\n"; return EXIT_FAILURE; }
+    if(argc <= 1) { std::cerr << "Usage: " PACKAGE_NAME " <command> [options]\nCommands: index, merge, sai, grep, pbcorrect, kmerfreq, kmercheck\n"; return EXIT_FAILURE; }
     const std::string command(argv[1]);
-    if(command == "help" || command == "--help") { std::cout << "Usage: " PACKAGE_NAME " <command> [options]\nCommands: index, merge, pbcorrect, kmerfreq, kmercheck\n"; return 0; }
+    if(command == "help" || command == "--help") { std::cout << "Usage: " PACKAGE_NAME " <command> [options]\nCommands: index, merge, sai, grep, pbcorrect, kmerfreq, kmercheck\n"; return 0; }
     if(command == "pbcorrect" || command == SUBPROGRAM) return PacBioSelfCorrectionMain(argc - 1, argv + 1);
     if(command == "index") return indexMain(argc - 1, argv + 1);
     if(command == "merge") return mergeMain(argc - 1, argv + 1);
+    if(command == "sai") return saiMain(argc - 1, argv + 1);
+    if(command == "grep") return grepMain(argc - 1, argv + 1);
     if(command == "kmerfreq") return kmerfreqMain(argc - 1, argv + 1);
     if(command == "kmercheck") return kmercheckMain(argc - 1, argv + 1);
     std::cerr << "Unrecognized command: " << command << "\n";

@@ -20,6 +20,9 @@ int lrsc_synth_reads(uint64_t seed, const char* genome, uint64_t genome_len,
 /* The permutation std::sort (libstdc++ introsort, comparator a.start > b.start) leaves n (key, index) pairs in -- the
  * product's own re-implementation (csrc/introsort_emul.h), run on the host.  perm_out[j] = index. */
 int lrsc_debug_sort_order(const uint64_t* keys, uint32_t n, uint32_t* perm_out);
+/* The .sai (reverse_reads == 0) / .rsai order of the reads by the host sort of whole reads that `stride index` uses
+ * (host/LexicoOrder.h): order_out[k] = the read of lexicographic rank k. */
+int lrsc_host_lexico_order(const char* bases, const uint64_t* off, uint32_t n_reads, int reverse_reads, uint32_t* order_out);
 #ifdef __cplusplus
 }
 #endif

@@ -34,7 +34,15 @@ counting the units each kernel reads and the blocks the pack kernel writes.  Wri
 B = the last 10 % are built once and stay resident; then lrsc_index_merge(A, B) against lrsc_index_build of all the reads,
 alternating, --runs of each after a warm-up of each.  The merge's stages come from its LRSC_BWT_PROFILE line (walk, interleave, pack,
 tables), the rebuild's from lrsc_index_build's; the device-memory peak of either is what it takes above A and B.  Writes
-profiles/index_merge.json (or --out)."""
+profiles/index_merge.json (or --out).
+
+--locate measures the device locate (csrc/fm_locate.hip) on the same reads.  The index is built once and its RL units kept; for
+rate 0 and rate 32 a fresh index of those units (lrsc_index_from_units_device) gets its tables (lrsc_index_locate_prepare, timed
+with a host clock around the synchronous call, --runs indexes per rate) and locates --rows (default 1 M) random rows of the .bwt
+strand: rows/s and LF steps per row from the LRSC_K_LOCATE statistics, after one warm-up call.  The device bytes of the tables are
+the fall of hipMemGetInfo's free memory across the prepare.  Beside them the host sort of whole reads that `stride index` uses
+for the same .sai and .rsai (the testkit's hook into host/LexicoOrder.h), whose order the device's must equal.  Writes
+profiles/index_locate.json (or --out)."""
 from __future__ import annotations
 
 import argparse
@@ -462,18 +470,74 @@ def merge_main(args, api, hip, bases, off, n_sym):
     print(json.dumps(result))
 
 
+def locate_main(args, api, hip, bases, off, n_sym):
+    import numpy as np
+
+    from longreadselfcorrect_amd.capi import K_LOCATE
+
+    n_reads = off.size - 1
+    mem = MemPeak(hip)
+    setup, host = {}, {}
+    built = clock(setup, "index_build", lambda: api.index_build(bases, off, 0))
+    units = [built.units(s, 0) for s in (0, 1)]
+    built.close()
+    host_order = [clock(host, name, lambda rev=rev: api.host_lexico_order(bases, off, rev)) for rev, name in ((False, "sai"), (True, "rsai"))]
+    say(f"index built in {setup}; host sort of whole reads {host}")
+    rows = np.random.default_rng(0x10CA7E).integers(0, n_sym, size=args.rows, dtype=np.uint64)
+    rates, answers = {}, {}
+    for rate in (0, 32):
+        prepare, table_bytes, calls = [], [], []
+        for run_i in range(args.runs):
+            idx = api.index_from_units_device(units[0], units[1], n_reads, n_sym, 0)
+            free0 = mem.free()
+            st = {}
+            clock(st, "prepare", lambda: idx.locate_prepare(rate, 0))
+            table_bytes.append(free0 - mem.free())
+            prepare.append(st["prepare"])
+            for strand in (0, 1):
+                assert np.array_equal(idx.lexico_order(strand, 0), host_order[strand]), "the device's order is not the host sort's"
+            ctx = idx.ctx(None, 0)
+            ctx.locate(0, rows[:1024])                            # warm-up
+            ctx.stats_reset()
+            wall = {}
+            got = clock(wall, "locate", lambda: ctx.locate(0, rows))
+            ks = ctx.stats(K_LOCATE)
+            calls.append({"wall_s": wall["locate"], "kernel_ms": ks.total_ms, "rows_per_s_kernel": rows.size / (ks.total_ms / 1e3),
+                          "rows_per_s_call": rows.size / wall["locate"], "lf_steps_per_row": ks.rank_queries / rows.size})
+            answers.setdefault(rate, got)
+            assert np.array_equal(got, answers[rate])
+            say(f"rate {rate} run {run_i}: prepare {st['prepare']:.3f} s, tables {table_bytes[-1] / 2**20:.1f} MiB, {calls[-1]}")
+            ctx.close()
+            idx.close()
+        rates[str(rate)] = {"prepare_s": {"all": prepare, "min": min(prepare), "max": max(prepare)}, "table_device_bytes": max(table_bytes),
+                            "table_bytes_by_formula": 2 * ((n_sym // rate + 1) * 8 if rate else 0) + 2 * 8 * n_reads, "locate": calls}
+    assert np.array_equal(answers[0], answers[32]), "the two rates locate differently"
+    result = {
+        "workload": {"genome_mb": args.genome_mb, "reads": n_reads, "symbols_per_strand": n_sym, "rows": int(rows.size)},
+        "setup_s": setup,
+        "host_lexico_order_s": {**host, "both": sum(host.values())},
+        "rates": rates,
+    }
+    out = args.out or str(REPO / "profiles" / "index_locate.json")
+    Path(out).parent.mkdir(parents=True, exist_ok=True)
+    Path(out).write_text(json.dumps(result, indent=1) + "\n")
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--genome-mb", type=float, default=11.1)
     ap.add_argument("--reads", type=int, default=100000)
     ap.add_argument("--runs", type=int, default=2)
-    ap.add_argument("--out", default=None, help="default: profiles/index_in_memory.json; profiles/index_rle.json with --rle, index_open.json with --open, index_merge.json with --merge")
+    ap.add_argument("--out", default=None, help="default: profiles/index_in_memory.json; profiles/index_rle.json with --rle, index_open.json with --open, index_merge.json with --merge, index_locate.json with --locate")
     ap.add_argument("--rle", action="store_true", help="measure the device RL encoder instead (see the module text)")
     ap.add_argument("--rle-call-only", action="store_true", help="the encoder's calls once (the child run under the profiler)")
     ap.add_argument("--call-only", action="store_true", help="one lrsc_index_build (the child run under the profiler)")
     ap.add_argument("--open", action="store_true", help="measure the device RL decoder instead (see the module text)")
     ap.add_argument("--open-call-only", action="store_true", help="one lrsc_index_open_device of --files (the child run under the profiler)")
     ap.add_argument("--merge", action="store_true", help="measure the device merge instead (see the module text)")
+    ap.add_argument("--locate", action="store_true", help="measure the device locate instead (see the module text)")
+    ap.add_argument("--rows", type=int, default=1000000, help="--locate: random rows to locate")
     ap.add_argument("--files", nargs=2, metavar=("BWT", "RBWT"))
     ap.add_argument("--no-profile", action="store_true")
     args = ap.parse_args()
@@ -493,6 +557,8 @@ def main():
         return open_main(args, api, hip, bases, off, n_sym)
     if args.merge:
         return merge_main(args, api, hip, bases, off, n_sym)
+    if args.locate:
+        return locate_main(args, api, hip, bases, off, n_sym)
     if args.call_only:
         api.index_build(bases, off, 0).close()
         return
