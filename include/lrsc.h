@@ -199,6 +199,38 @@ int lrsc_find_kmers(lrsc_ctx* ctx, const char* kmers, uint32_t k, uint64_t n, lr
  * For strand LRSC_RBWT, pos counts in the reversed read.  Counted under LRSC_K_LOCATE; rank_queries = LF steps. */
 int lrsc_locate(lrsc_ctx* ctx, int strand, const uint64_t* rows, uint64_t n, lrsc_sa_elem* out);
 
+/* ---- duplicate check and read removal: `stride filter` (Algorithm/QCProcess.cpp:206-265, StriDe/filter.cpp) ----------------- */
+/* QCProcess::performDuplicateCheck's DuplicateCheckResult, plus LRSC_DUP_ABSENT: neither the read nor its reverse complement is
+ * a read of the index (the reference then tests bit INT64_MAX of its bit vector; here the bit vector is left alone). */
+enum lrsc_dup_class { LRSC_DUP_UNIQUE = 0, LRSC_DUP_SUBSTRING = 1, LRSC_DUP_FULL_LENGTH = 2, LRSC_DUP_ABSENT = 3 };
+typedef struct lrsc_dup_result {
+    lrsc_interval fwd_dollar;   /* ranks among the '$' rows of .bwt of the reads equal to w (interval[0] after updateBothL(.., '$')); lower > upper: none ({0, -1}) */
+    lrsc_interval rvc_dollar;   /* the same for reverseComplement(w) */
+    int32_t cls; uint32_t pad;
+} lrsc_dup_result;
+typedef struct lrsc_dupcheck lrsc_dupcheck;      /* the shared bit vector of filterMain (num_strings bits), on the ctx's device, all clear */
+/* The bit vector and a 32-bit word per read of the index (the read that claims a slot within one call).  The ctx must outlive it. */
+int  lrsc_dupcheck_create(lrsc_ctx* ctx, lrsc_dupcheck** out);
+/* performDuplicateCheck for n_reads reads (concatenated ACGT bytes, n_reads + 1 offsets) against the ctx's index.  A read w with
+ * reverse complement rc is SUBSTRING when w or rc is a proper substring of a read of the index, ABSENT when neither is a read of
+ * it; otherwise its canonical index is the smaller valid lower of the two '$' intervals, and it is UNIQUE when that bit is clear
+ * (it sets the bit) and FULL_LENGTH when the bit is set.  Both '$' intervals are filled for every class.
+ * The order is that of the reference's serial mode (-t 1): within a call in read order, across the calls of one lrsc_dupcheck in
+ * call order.  The reference with threads lets a compare-and-swap race decide which copy of a duplicate survives; this
+ * implementation does not race: the result is the serial one however the device schedules its lanes.
+ * LRSC_ERR_ARG for an empty read (the reference reads w[-1]) and for a base other than A,C,G,T; on an error the bit vector is
+ * as it was.  The search launches are counted under LRSC_K_FIND. */
+int  lrsc_dupcheck_reads(lrsc_dupcheck* dc, const char* reads, const uint64_t* read_off, uint32_t n_reads, lrsc_dup_result* out);
+void lrsc_dupcheck_destroy(lrsc_dupcheck* dc);
+/* The index of idx's reads whose drop[] byte is 0, in their order; byte for byte what lrsc_index_build makes of those reads.
+ * Made on `device` from idx's copy there (LRSC_ERR_DEVICE without one) with no suffix sort: the rows of the dropped reads are
+ * marked by backward walks and the rest is compacted and packed.  idx is not modified and stays usable.  The result is resident
+ * on `device` with its k-mer tables and carries a host image, as a built index does; num_runs is 0.
+ * LRSC_ERR_ARG if n_reads != num_strings or nothing is kept, LRSC_ERR_FORMAT if a walk does not end at a '$' row or the marked
+ * rows are not the dropped reads' (an index that is no BWT of a string set), LRSC_ERR_UNSUPPORTED at the packer's and locate's
+ * limits; on an error nothing stays allocated and *out is untouched. */
+int lrsc_index_remove(lrsc_index* idx, const uint8_t* drop, uint64_t n_reads, int device, lrsc_index** out);
+
 /* ---- LongReadProbe k-mer feature grid -------------------------------------------------- */
 /* reads: concatenated ACGT bytes, read_off: n_reads+1 offsets.  ks: ascending k-mer sizes
  * (the "pool", e.g. {5,9,15,17,19}), n_k <= 8.  For read r, position p, pool slot j the record

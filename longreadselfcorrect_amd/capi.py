@@ -193,6 +193,9 @@ BWT, RBWT = 0, 1
 RANK_DTYPE = np.dtype([("idx", "<i8"), ("base", "u1"), ("strand", "u1"), ("pad", "u1", (6,))])
 BIIV_DTYPE = np.dtype([("fwd_lower", "<i8"), ("fwd_upper", "<i8"), ("rvc_lower", "<i8"), ("rvc_upper", "<i8")])
 SA_DTYPE = np.dtype([("read", "<u4"), ("pos", "<u4")])          # lrsc_sa_elem
+# lrsc_dup_result; cls is one of DUP_UNIQUE .. DUP_ABSENT
+DUP_DTYPE = np.dtype([("fwd_lower", "<i8"), ("fwd_upper", "<i8"), ("rvc_lower", "<i8"), ("rvc_upper", "<i8"), ("cls", "<i4"), ("pad", "<u4")])
+DUP_UNIQUE, DUP_SUBSTRING, DUP_FULL_LENGTH, DUP_ABSENT = range(4)
 assert RANK_DTYPE.itemsize == C.sizeof(RankQuery) and BIIV_DTYPE.itemsize == C.sizeof(BiInterval)
 
 
@@ -246,6 +249,11 @@ class Lrsc:
         L.lrsc_index_locate_prepare.argtypes = [C.c_void_p, C.c_int, C.c_uint32]
         L.lrsc_index_lexico_order.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.lrsc_locate.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.lrsc_dupcheck_create.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+        L.lrsc_dupcheck_reads.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]
+        L.lrsc_dupcheck_destroy.argtypes = [C.c_void_p]
+        L.lrsc_dupcheck_destroy.restype = None
+        L.lrsc_index_remove.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]
         L.lrsc_params_default.argtypes = [C.c_int, C.c_int, C.POINTER(Params)]
         L.lrsc_ctx_create.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int, C.POINTER(C.c_void_p)]
         L.lrsc_ctx_destroy.argtypes = [C.c_void_p]
@@ -459,6 +467,14 @@ class Index:
                        "lrsc_index_lexico_order")
         return (order, read_len) if want_len else order
 
+    def remove(self, drop: np.ndarray, device: int = 0) -> "Index":
+        """The index of the reads whose drop[] entry is 0, in their order, made on `device` from the copy there without a suffix
+        sort; this index stays usable."""
+        drop = np.ascontiguousarray(np.asarray(drop) != 0, dtype=np.uint8)
+        h = C.c_void_p()
+        self.api.check(self.api.lib.lrsc_index_remove(self.h, _ptr(drop), drop.size, device, C.byref(h)), "lrsc_index_remove")
+        return Index(self.api, h)
+
     def ctx(self, params: Params | None = None, device: int = 0) -> "Ctx":
         h = C.c_void_p()
         pp = C.byref(params) if params is not None else None
@@ -471,6 +487,26 @@ class Index:
             self.h = None
 
 
+class DupCheck:
+    """lrsc_dupcheck: close it before its context."""
+
+    def __init__(self, api: Lrsc, ctx: "Ctx", handle):
+        self.api, self.ctx, self.h = api, ctx, handle
+
+    def reads(self, bases: np.ndarray, off: np.ndarray) -> np.ndarray:
+        """DUP_DTYPE per read (ASCII bases, n + 1 offsets): both '$' intervals and the class, in the serial order of the calls."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        out = np.zeros(off.size - 1, dtype=DUP_DTYPE)
+        self.api.check(self.api.lib.lrsc_dupcheck_reads(self.h, _ptr(bases), _ptr(off), off.size - 1, _ptr(out)), "lrsc_dupcheck_reads")
+        return out
+
+    def close(self):
+        if self.h:
+            self.api.lib.lrsc_dupcheck_destroy(self.h)
+            self.h = None
+
+
 class Ctx:
     def __init__(self, api: Lrsc, index: Index, handle):
         self.api, self.index, self.h = api, index, handle
@@ -479,6 +515,12 @@ class Ctx:
         if self.h:
             self.api.lib.lrsc_ctx_destroy(self.h)
             self.h = None
+
+    def dupcheck(self) -> "DupCheck":
+        """A duplicate-check session on this context's index: the bit vector of a `stride filter` run, all clear."""
+        h = C.c_void_p()
+        self.api.check(self.api.lib.lrsc_dupcheck_create(self.h, C.byref(h)), "lrsc_dupcheck_create")
+        return DupCheck(self.api, self, h)
 
     def rank(self, bases: np.ndarray, idx: np.ndarray, strand: np.ndarray | int) -> np.ndarray:
         n = len(idx)

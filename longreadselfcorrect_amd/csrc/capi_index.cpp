@@ -79,7 +79,7 @@ extern "C" int lrsc_index_info_get(const lrsc_index* idx, lrsc_index_info* out)
     return LRSC_OK;
 }
 
-static void free_device_copy(DeviceCopy& dc)
+void lrsc::free_device_copy(DeviceCopy& dc)
 {
     for(int s = 0; s < 2; ++s) {
         if(dc.blocks[s]) (void)hipFree(dc.blocks[s]);
@@ -111,7 +111,7 @@ static int copy_image(const lrsc_index* idx, DeviceCopy& dc)
 
 // second half: describe the image that dc holds on the current device (copied there, or packed there by lrsc_index_build),
 // build its k-mer tables and enter it as `device`'s copy.  The caller holds idx->mu and frees dc on failure.
-static int register_copy(lrsc_index* idx, int device, DeviceCopy& dc)
+int lrsc::register_copy(lrsc_index* idx, int device, DeviceCopy& dc)
 {
     dc.dev.wide = idx->wide ? 1u : 0u;
     for(int s = 0; s < 2; ++s) {
@@ -270,7 +270,7 @@ extern "C" int lrsc_build_bwt(const char* reads, const uint64_t* read_off, uint3
 extern "C" void lrsc_buffer_free(void* p) { std::free(p); }
 
 // the host image of a strand that was packed on the device: a copy of the packed arrays (a third of a byte per symbol)
-static int image_from_device(const PackedStrand& ps, uint64_t N, uint64_t n_runs, StrandImage& im, std::string& err)
+int lrsc::image_from_device(const PackedStrand& ps, uint64_t N, uint64_t n_runs, StrandImage& im, std::string& err)
 {
     im.n_blocks = ps.n_blocks;
     im.n_symbols = N;
@@ -370,7 +370,7 @@ static int merge_strand(const FmStrand& a, bool wide_a, const FmStrand& b, bool 
 }
 
 // the strands of idx's copy on `device`
-static int resident_strands(lrsc_index* idx, int device, FmStrand fs[2], bool& wide)
+int lrsc::resident_strands(lrsc_index* idx, int device, FmStrand fs[2], bool& wide)
 {
     std::lock_guard<std::mutex> lock(idx->mu);
     auto it = idx->copies.find(device);

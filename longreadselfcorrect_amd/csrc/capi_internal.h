@@ -20,6 +20,7 @@
 #include "../../include/lrsc.h"
 #include "fm_layout.h"
 #include "fm_locate.h"
+#include "fm_pack.h"
 #include "kernels.h"
 #include "extend.h"
 #include "correct_dev.h"
@@ -231,6 +232,16 @@ void kmer_freq_table(const lrsc_params& p, double freqs[101]);
 int encode_acgt(const char* seq, uint64_t n, uint8_t* codes);
 // upload ASCII bases, encode to 2-bit codes on the device, reject non-ACGT
 int upload_and_encode(lrsc_ctx* ctx, const char* ascii, uint64_t n, uint8_t* d_codes);
+
+// what the entries that make an index on the device share (capi_index.cpp)
+void free_device_copy(DeviceCopy& dc);
+// describes the image that dc holds on the current device, builds its k-mer tables and enters it as `device`'s copy; the caller
+// holds idx->mu and frees dc on failure
+int register_copy(lrsc_index* idx, int device, DeviceCopy& dc);
+// the host image of a strand that was packed on the device
+int image_from_device(const PackedStrand& ps, uint64_t N, uint64_t n_runs, StrandImage& im, std::string& err);
+// the strands of idx's copy on `device` (LRSC_ERR_DEVICE without one)
+int resident_strands(lrsc_index* idx, int device, FmStrand fs[2], bool& wide);
 
 // Bracket one kernel launch with HIP events on the ctx stream and fold the device counters
 // into the per-kernel stats.  `launch` enqueues on ctx->stream.

@@ -97,6 +97,17 @@ struct LocateTables;
 struct SaElem;
 hipError_t launch_locate(const FmStrand& s, bool wide, const LocateTables& t, const uint64_t* rows, uint64_t n, SaElem* out, uint32_t* broken,
                          DevCounters* ctr, hipStream_t stream);
+// The duplicate check of n reads (fm_dup.hip): words = their codes, one per byte, in a buffer that can be read as 32-bit words up
+// to the one that holds the last base; read_off = n + 1 offsets.  launch_dup_chains runs the four chains of every read into
+// chains[kind * n + read]; launch_dup_classify joins them into results[] and slots[], lets the first read of the call claim each
+// slot in winner[] (n_slots entries, all kDupNoWinner before and after), classifies against bits[] and then sets the claimed bits.
+// *broken is set to 1 when an interval leaves the strand (an index that is no BWT of a string set).
+struct DupChainOut;
+struct DupResult;
+hipError_t launch_dup_chains(const FmIndexDev& fm, const uint32_t* words, const uint64_t* read_off, uint32_t n, DupChainOut* chains, DevCounters* ctr,
+                             hipStream_t stream);
+hipError_t launch_dup_classify(const FmIndexDev& fm, const DupChainOut* chains, uint32_t n, uint64_t n_slots, DupResult* results, uint64_t* slots, uint32_t* winner,
+                               uint32_t* bits, uint32_t* broken, hipStream_t stream);
 hipError_t launch_bwt_chars(const FmIndexDev& fm, int strand, const uint64_t* idx, uint64_t n, char* out,
                             hipStream_t stream);
 hipError_t launch_find_kmers(const FmIndexDev& fm, const uint8_t* kmer_codes, uint32_t k, uint64_t n,

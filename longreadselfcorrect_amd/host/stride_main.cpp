@@ -1,5 +1,5 @@
-// stride_main.cpp -- `stride pbcorrect` (a.k.a. PacBioSelfCorrection), `stride index`, `stride merge`, `stride sai` and
-// `stride grep` on the MI355X back end.  Option surface, defaults, validation messages and exit codes follow the reference's
+// stride_main.cpp -- `stride pbcorrect` (a.k.a. PacBioSelfCorrection), `stride index`, `stride merge`, `stride sai`,
+// `stride grep` and `stride filter` on the MI355X back end.  Option surface, defaults, validation messages and exit codes follow the reference's
 // StriDe/PacBioSelfCorrection.cpp:32-140,262-434 and StriDe/StriDe.cpp:62-126; extra flags: --devices, --batch.
 #include <getopt.h>
 
@@ -18,6 +18,7 @@
 #include "BCode.h"
 #include "LexicoOrder.h"
 #include "PacBioSelfCorrectionProcess.h"
+#include "QCProcess.h"
 #include "SequenceProcessFramework.h"
 
 #define PACKAGE_NAME "StriDe"
@@ -577,18 +578,209 @@ static int grepMain(int argc, char** argv)
     return 0;
 }
 
+// `stride filter READSFILE`: the reference's filter (StriDe/filter.cpp:48-70,120-319): every read is looked up in the index as a
+// whole string; exact duplicates, reverse-complement duplicates and reads contained in another read go to the discard file, the
+// others to the pass file, and the index of the passing reads is written beside them.  That index is the input's with the
+// discarded reads taken out on the device (lrsc_index_remove), where the reference runs its index construction a second time.
+static const char* FILTER_USAGE_MESSAGE =
+    "Usage: " PACKAGE_NAME " filter [OPTION] ... READSFILE\n"
+    "Remove reads from a data set.\n"
+    "The currently available filters are removing exact-match duplicates\n"
+    "and removing reads with low-frequency k-mers.\n"
+    "Automatically rebuilds the FM-index without the discarded reads.\n"
+    "\n"
+    "      --help                           display this help and exit\n"
+    "      -v, --verbose                    display verbose output\n"
+    "      -p, --prefix=PREFIX              use PREFIX for the names of the index files (default: prefix of the input file)\n"
+    "      --build-index                    index READSFILE in memory on the device instead of loading PREFIX.bwt/.rbwt\n"
+    "      -o, --outfile=FILE               write the qc-passed reads to FILE (default: READSFILE.filter.pass.fa)\n"
+    "      -t, --threads=NUM                use NUM threads to compute the overlaps (default: 1)\n"
+    "      -d, --sample-rate=N              use occurrence array sample rate of N in the FM-index. Higher values use significantly\n"
+    "                                       less memory at the cost of higher runtime. This value must be a power of 2 (default: 128)\n"
+    "      --no-duplicate-check             turn off duplicate removal\n"
+    "      --substring-only                 when removing duplicates, only remove substring sequences, not full-length matches\n"
+    "      --no-kmer-check                  turn off the kmer check\n"
+    "      --homopolymer-check              check reads for hompolymer run length sequencing errors\n"
+    "      --low-complexity-check           filter out low complexity reads\n"
+    "      --device=N                       HIP device to work on (default: 0)\n"
+    "\nK-mer filter options:\n"
+    "      -k, --kmer-size=N                The length of the kmer to use. (default: 31)\n"
+    "      -x, --kmer-threshold=N           Require at least N kmer coverage for each kmer in a read. (default: 3)\n"
+    "\nReport bugs to " PACKAGE_BUGREPORT "\n\n";
+
+namespace filteropt {
+static unsigned int verbose = 0;
+static int numThreads = 8, sampleRate = 128, kmerLength = 31, kmerThreshold = 3, device = 0;
+static std::string prefix, readsFile, outFile, discardFile;
+static bool dupCheck = true, substringOnly = false, hpCheck = false, lowComplexityCheck = false, buildIndex = false;
+static const size_t batch = 100000;                             // reads per device call
+}
+
+// file name without its directory, a .gz suffix and its extension (Util/Util.cpp:218-225)
+static std::string getFilename(const std::string& path)
+{
+    std::string out = path.substr(path.find_last_of('/') + 1);
+    if(out.size() >= 3 && out.compare(out.size() - 3, 3, ".gz") == 0) out = out.substr(0, out.size() - 3);
+    return out.substr(0, out.find_last_of('.'));
+}
+
+static void parseFilterOptions(int argc, char** argv)
+{
+    enum { F_HELP = 1, F_SUBSTRING_ONLY, F_NO_RMDUP, F_NO_KMER, F_CHECK_HPRUNS, F_CHECK_COMPLEXITY, F_DEVICE, F_BUILDINDEX };
+    static const struct option filter_longopts[] = {
+        {"verbose", no_argument, nullptr, 'v'},               {"threads", required_argument, nullptr, 't'},
+        {"outfile", required_argument, nullptr, 'o'},         {"prefix", required_argument, nullptr, 'p'},
+        {"sample-rate", required_argument, nullptr, 'd'},     {"kmer-size", required_argument, nullptr, 'k'},
+        {"kmer-threshold", required_argument, nullptr, 'x'},  {"help", no_argument, nullptr, F_HELP},
+        {"no-duplicate-check", no_argument, nullptr, F_NO_RMDUP}, {"no-kmer-check", no_argument, nullptr, F_NO_KMER},
+        {"homopolymer-check", no_argument, nullptr, F_CHECK_HPRUNS}, {"low-complexity-check", no_argument, nullptr, F_CHECK_COMPLEXITY},
+        {"substring-only", no_argument, nullptr, F_SUBSTRING_ONLY}, {"device", required_argument, nullptr, F_DEVICE},
+        {"build-index", no_argument, nullptr, F_BUILDINDEX},  {nullptr, 0, nullptr, 0}};
+    optind = 1;
+    bool die = false;
+    for(int c; (c = getopt_long(argc, argv, "p:d:t:o:k:x:v", filter_longopts, nullptr)) != -1;) {
+        std::istringstream arg(optarg != nullptr ? optarg : "");
+        switch(c) {
+            case 'p': arg >> filteropt::prefix; break;
+            case 'o': arg >> filteropt::outFile; break;
+            case 't': arg >> filteropt::numThreads; break;
+            case 'd': arg >> filteropt::sampleRate; break;
+            case 'k': arg >> filteropt::kmerLength; break;
+            case 'x': arg >> filteropt::kmerThreshold; break;
+            case 'v': filteropt::verbose++; break;
+            case F_NO_RMDUP: filteropt::dupCheck = false; break;
+            case F_NO_KMER: break;                              // the k-mer check starts switched off and nothing switches it on
+            case F_CHECK_HPRUNS: filteropt::hpCheck = true; break;
+            case F_CHECK_COMPLEXITY: filteropt::lowComplexityCheck = true; break;
+            case F_SUBSTRING_ONLY: filteropt::substringOnly = true; break;
+            case F_DEVICE: arg >> filteropt::device; break;
+            case F_BUILDINDEX: filteropt::buildIndex = true; break;
+            case F_HELP: std::cout << FILTER_USAGE_MESSAGE; exit(EXIT_SUCCESS);
+            default: die = true; break;
+        }
+    }
+    if(argc - optind < 1) { std::cerr << "filter: missing arguments\n"; die = true; }
+    else if(argc - optind > 1) { std::cerr << "filter: too many arguments\n"; die = true; }
+    if(filteropt::numThreads <= 0) { std::cerr << "filter: invalid number of threads: " << filteropt::numThreads << "\n"; die = true; }
+    if(filteropt::kmerLength <= 0) { std::cerr << "filter: invalid kmer length: " << filteropt::kmerLength << ", must be greater than zero\n"; die = true; }
+    if(filteropt::kmerThreshold <= 0) { std::cerr << "filter: invalid kmer threshold: " << filteropt::kmerThreshold << ", must be greater than zero\n"; die = true; }
+    if(die) { std::cout << "\n" << FILTER_USAGE_MESSAGE; exit(EXIT_FAILURE); }
+    filteropt::readsFile = argv[optind++];
+    if(filteropt::prefix.empty()) filteropt::prefix = getFilename(filteropt::readsFile);
+    if(filteropt::outFile.empty()) {
+        filteropt::outFile = filteropt::prefix + ".filter.pass.fa";
+        filteropt::discardFile = filteropt::prefix + ".discard.fa";
+    } else
+        filteropt::discardFile = getFilename(filteropt::outFile) + ".discard.fa";
+}
+
+static int filterMain(int argc, char** argv)
+{
+    parseFilterOptions(argc, argv);
+    const int device = filteropt::device;
+    lrsc_index* idx = nullptr;
+    if(filteropt::buildIndex) {
+        std::string bases;
+        std::vector<uint64_t> off;
+        loadReads(filteropt::readsFile, bases, off);
+        lrscOrDie(lrsc_index_build(bases.data(), off.data(), (uint32_t)(off.size() - 1), device, &idx), "lrsc_index_build");
+    } else
+        lrscOrDie(lrsc_index_open_device((filteropt::prefix + BWT_EXT).c_str(), (filteropt::prefix + RBWT_EXT).c_str(), device, &idx), "lrsc_index_open_device");
+    lrsc_index_info info;
+    lrscOrDie(lrsc_index_info_get(idx, &info), "lrsc_index_info_get");
+    lrsc_ctx* ctx = nullptr;
+    lrsc_dupcheck* session = nullptr;
+    lrscOrDie(lrsc_ctx_create(idx, nullptr, device, &ctx), "lrsc_ctx_create");
+    lrscOrDie(lrsc_dupcheck_create(ctx, &session), "lrsc_dupcheck_create");
+
+    QCParameters params;
+    params.ctx = ctx;
+    params.dupcheck = session;
+    params.checkDuplicates = filteropt::dupCheck;
+    params.substringOnly = filteropt::substringOnly;
+    params.checkKmer = false;
+    params.checkHPRuns = filteropt::hpCheck;
+    params.checkDegenerate = filteropt::lowComplexityCheck;
+    params.verbose = (int)filteropt::verbose;
+    params.kmerLength = filteropt::kmerLength;
+    params.kmerThreshold = filteropt::kmerThreshold;
+
+    // the reads in file order, a batch per device call; drop[i] and the '$' interval of read i are kept for the index
+    std::vector<uint8_t> drop;
+    std::vector<lrsc_interval> own;
+    {
+        std::ofstream pass(filteropt::outFile.c_str()), discard(filteropt::discardFile.c_str());
+        if(!pass || !discard) { std::cerr << "Error: could not open " << filteropt::outFile << " / " << filteropt::discardFile << " for write\n"; return EXIT_FAILURE; }
+        QCProcess processor(params);
+        QCPostProcess post(&pass, &discard);
+        SeqReader reader(filteropt::readsFile);
+        WorkItemGenerator<SequenceWorkItem> generator(&reader);
+        std::vector<SequenceWorkItem> items;
+        std::vector<lrsc_dup_result> dup;
+        for(bool more = true; more;) {
+            items.clear();
+            SequenceWorkItem item;
+            while(items.size() < filteropt::batch && (more = generator.generate(item))) items.push_back(item);
+            const std::vector<QCResult> results = processor.process_batch(items, &dup);
+            for(size_t i = 0; i < items.size(); ++i) {
+                post.process(items[i], results[i]);
+                drop.push_back(results[i].passed() ? 0 : 1);
+                own.push_back(dup[i].fwd_dollar);
+            }
+        }
+    }                                                             // the counters are printed here
+    lrsc_dupcheck_destroy(session);
+    lrsc_ctx_destroy(ctx);
+
+    // Reads are taken out of the index by their number: the file has to be the index's read set.  Read i's own '$' row, the
+    // inverse of the lexicographic order, must be one of the '$' rows of the reads equal to it.
+    if(drop.size() != info.num_strings) {
+        std::cerr << "filter: " << filteropt::readsFile << " holds " << drop.size() << " reads, the index " << filteropt::prefix << " " << info.num_strings
+                  << ": no index written\n";
+        return EXIT_FAILURE;
+    }
+    {
+        std::vector<uint32_t> order(info.num_strings), row(info.num_strings);
+        lrscOrDie(lrsc_index_lexico_order(idx, LRSC_BWT, device, order.data(), nullptr), "lrsc_index_lexico_order");
+        for(size_t k = 0; k < order.size(); ++k) row[order[k]] = (uint32_t)k;
+        for(size_t i = 0; i < row.size(); ++i)
+            if((int64_t)row[i] < own[i].lower || (int64_t)row[i] > own[i].upper) {
+                std::cerr << "filter: read " << i << " of " << filteropt::readsFile << " is not read " << i << " of the index " << filteropt::prefix
+                          << " (the file is not the read set the index was made of): no index written\n";
+                return EXIT_FAILURE;
+            }
+    }
+    const std::string out_prefix = getFilename(filteropt::outFile);
+    if(std::count(drop.begin(), drop.end(), 0) == 0) { std::cerr << "filter: no read passed: no index written\n"; return EXIT_FAILURE; }
+    std::cout << "Making the index of " << filteropt::outFile << " from " << filteropt::prefix << " without the discarded reads on the GPU\n";
+    lrsc_index* kept = nullptr;
+    lrscOrDie(lrsc_index_remove(idx, drop.data(), drop.size(), device, &kept), "lrsc_index_remove");
+    lrsc_index_close(idx);
+    lrscOrDie(lrsc_index_write(kept, device, (out_prefix + BWT_EXT).c_str(), (out_prefix + RBWT_EXT).c_str()), "lrsc_index_write");
+    lrsc_index_info kept_info;
+    lrscOrDie(lrsc_index_info_get(kept, &kept_info), "lrsc_index_info_get");
+    for(int rev = 0; rev < 2; ++rev) {
+        std::vector<uint32_t> order(kept_info.num_strings);
+        lrscOrDie(lrsc_index_lexico_order(kept, rev ? LRSC_RBWT : LRSC_BWT, device, order.data(), nullptr), "lrsc_index_lexico_order");
+        if(!writeSai(out_prefix + (rev ? ".rsai" : ".sai"), order)) return EXIT_FAILURE;
+    }
+    lrsc_index_close(kept);
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
     // several workers on one device (--devices 0,0) only overlap if their streams get hardware queues of their own (default: 4)
     setenv("GPU_MAX_HW_QUEUES", "16", 0);
-    if(argc <= 1) { std::cerr << "Usage: " PACKAGE_NAME " <command> [options]\nCommands: index, merge, sai, grep, pbcorrect, kmerfreq, kmercheck\n"; return EXIT_FAILURE; }
+    if(argc <= 1) { std::cerr << "Usage: " PACKAGE_NAME " <command> [options]\nCommands: index, merge, sai, grep, filter, pbcorrect, kmerfreq, kmercheck\n"; return EXIT_FAILURE; }
     const std::string command(argv[1]);
-    if(command == "help" || command == "--help") { std::cout << "Usage: " PACKAGE_NAME " <command> [options]\nCommands: index, merge, sai, grep, pbcorrect, kmerfreq, kmercheck\n"; return 0; }
+    if(command == "help" || command == "--help") { std::cout << "Usage: " PACKAGE_NAME " <command> [options]\nCommands: index, merge, sai, grep, filter, pbcorrect, kmerfreq, kmercheck\n"; return 0; }
     if(command == "pbcorrect" || command == SUBPROGRAM) return PacBioSelfCorrectionMain(argc - 1, argv + 1);
     if(command == "index") return indexMain(argc - 1, argv + 1);
     if(command == "merge") return mergeMain(argc - 1, argv + 1);
     if(command == "sai") return saiMain(argc - 1, argv + 1);
     if(command == "grep") return grepMain(argc - 1, argv + 1);
+    if(command == "filter") return filterMain(argc - 1, argv + 1);
     if(command == "kmerfreq") return kmerfreqMain(argc - 1, argv + 1);
     if(command == "kmercheck") return kmercheckMain(argc - 1, argv + 1);
     std::cerr << "Unrecognized command: " << command << "\n";

@@ -1,0 +1,122 @@
+// dup_driver.cpp -- the device duplicate check's per-lane functions (csrc/fm_dup.h) compiled for the CPU and run in the kernels' order.
+//
+//   dup_driver <wide: 0|1> < input
+//
+// input:  for .bwt, then for .rbwt: u64 N, u64 n_units, the RL units of the strand's BWT; u64 n_calls; per call u64 n, n + 1
+//         offsets as u64, the bases as codes 0..3, one per byte.
+// The two images come from build_strand_image (fm_layout.cpp), Block64 where wide, as lrsc_index_upload would hold them.  One
+// session (bit vector, winner words) serves all calls, as one lrsc_dupcheck does.  Per call, as fm_dup.hip does: dup_chain for
+// every read, kind by kind; dup_combine and the claim of the slot for every read; dup_classify for every read; then the bits
+// are set and the winner words released.  A broken chain or a winner word left claimed ends the run.
+// output: per call n records of 40 bytes (lrsc_dup_result); then u64 Occ queries, u64 block loads of all chains.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../longreadselfcorrect_amd/csrc/fm_dup.h"
+#include "../../longreadselfcorrect_amd/csrc/fm_layout.h"
+
+using namespace lrsc;
+
+static void die(const char* what)
+{
+    std::fprintf(stderr, "dup_driver: %s\n", what);
+    std::exit(1);
+}
+
+static FmStrand strand_of(const StrandImage& im, bool wide)
+{
+    FmStrand fs;
+    fs.blocks = im.blocks.data();
+    fs.dollars = im.dollars.data();
+    fs.dollar_dir = im.dollar_dir.data();
+    fs.dollar_group_syms = (uint64_t)(wide ? Block64::kSyms : Block32::kSyms) << kDollarDirShift;
+    fs.n_dollars = im.dollars.size();
+    fs.n_symbols = im.n_symbols;
+    fs.n_blocks = im.n_blocks;
+    for(int c = 0; c < 5; ++c) fs.pred[c] = im.pred[c];
+    return fs;
+}
+
+static void read_exact(void* p, size_t n)
+{
+    if(n && std::fread(p, 1, n, stdin) != n) die("short input");
+}
+
+static void read_image(bool wide, StrandImage& im)
+{
+    uint64_t hdr[2];
+    read_exact(hdr, 16);
+    std::vector<uint8_t> units(hdr[1]);
+    read_exact(units.data(), units.size());
+    std::string err;
+    if(build_strand_image(units.data(), units.size(), hdr[0], wide, im, err) != 0) die(err.c_str());
+}
+
+template <class Block>
+static void run(const StrandImage& i0, const StrandImage& i1, bool wide)
+{
+    static_assert(sizeof(DupResult) == 40, "lrsc_dup_result");
+    const FmStrand f0 = strand_of(i0, wide), f1 = strand_of(i1, wide);
+    const MergeStrand<Block> S[2] = {merge_strand<Block>(f0), merge_strand<Block>(f1)};
+    std::vector<uint32_t> mtab(MergeMaskTab<Block>::kWords);
+    for(uint32_t i = 0; i < mtab.size(); ++i) mtab[i] = merge_mask_word<Block>(i);
+    const uint64_t n_slots = S[0].n_dollars;
+    if(n_slots == 0 || S[1].n_dollars != n_slots) die("the strands hold no reads, or not the same number");
+    std::vector<uint32_t> bits((n_slots + 31) / 32, 0u), winner(n_slots, kDupNoWinner);
+    uint64_t n_calls = 0, totals[2] = {0, 0};
+    read_exact(&n_calls, 8);
+    for(uint64_t call = 0; call < n_calls; ++call) {
+        uint64_t n = 0;
+        read_exact(&n, 8);
+        std::vector<uint64_t> off(n + 1);
+        read_exact(off.data(), off.size() * 8);
+        const uint64_t total = off[n];
+        std::vector<uint32_t> words(total / 4 + 1, 0xA5A5A5A5u);  // what lies behind the last base is anything
+        read_exact(words.data(), total);
+        // 1. the chains, kind by kind
+        std::vector<DupChainOut> chains(kDupKinds * n);
+        for(uint32_t kind = 0; kind < kDupKinds; ++kind)
+            for(uint64_t r = 0; r < n; ++r) {
+                if(off[r + 1] <= off[r] || off[r + 1] - off[r] >= (1ull << 32)) die("an empty read");
+                uint32_t n_rank = 0, n_blk = 0;
+                chains[kind * n + r] = dup_chain<Block>(S[dup_kind_strand(kind)], mtab.data(), words.data(), off[r], (uint32_t)(off[r + 1] - off[r]), kind,
+                                                        n_rank, n_blk);
+                totals[0] += n_rank;
+                totals[1] += n_blk;
+            }
+        // 2. combine and claim
+        std::vector<DupResult> res(n);
+        std::vector<uint64_t> slots(n);
+        for(uint64_t r = 0; r < n; ++r) {
+            if(!dup_combine(dup_dollars(S[0]), S[0].N, chains[r], chains[n + r], chains[2 * n + r], chains[3 * n + r], n_slots, res[r], slots[r])) die("a broken chain");
+            if(slots[r] < n_slots && (uint32_t)r < winner[slots[r]]) winner[slots[r]] = (uint32_t)r;
+        }
+        // 3. classify
+        for(uint64_t r = 0; r < n; ++r)
+            if(slots[r] < n_slots) res[r].cls = dup_classify(((bits[slots[r] >> 5] >> (slots[r] & 31)) & 1u) != 0, winner[slots[r]], (uint32_t)r);
+        // 4. commit
+        for(uint64_t r = 0; r < n; ++r)
+            if(slots[r] < n_slots) {
+                bits[slots[r] >> 5] |= 1u << (slots[r] & 31);
+                winner[slots[r]] = kDupNoWinner;
+            }
+        for(uint32_t w : winner) if(w != kDupNoWinner) die("a winner word left claimed");
+        if(n) std::fwrite(res.data(), sizeof(DupResult), n, stdout);
+    }
+    std::fwrite(totals, 8, 2, stdout);
+}
+
+int main(int argc, char** argv)
+{
+    if(argc != 2) { std::fprintf(stderr, "usage: dup_driver <wide> < input\n"); return 2; }
+    const bool wide = std::atoi(argv[1]) != 0;
+    StrandImage i0, i1;
+    read_image(wide, i0);
+    read_image(wide, i1);
+    if(wide) run<Block64>(i0, i1, true);
+    else run<Block32>(i0, i1, false);
+    return 0;
+}

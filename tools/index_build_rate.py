@@ -42,7 +42,17 @@ with a host clock around the synchronous call, --runs indexes per rate) and loca
 strand: rows/s and LF steps per row from the LRSC_K_LOCATE statistics, after one warm-up call.  The device bytes of the tables are
 the fall of hipMemGetInfo's free memory across the prepare.  Beside them the host sort of whole reads that `stride index` uses
 for the same .sai and .rsai (the testkit's hook into host/LexicoOrder.h), whose order the device's must equal.  Writes
-profiles/index_locate.json (or --out)."""
+profiles/index_locate.json (or --out).
+
+--filter measures the duplicate check and the read removal (csrc/fm_dup.hip, fm_remove.hip): `stride filter`'s two device steps.
+Every tenth read is replaced: by a copy of the read before it, by that read's reverse complement, or by a substring of it, in
+turn.  The index of these reads is built once and stays resident.  lrsc_dupcheck_reads over all reads in batches of 10 000 (a
+fresh session per run): Mbases/s by the call's wall clock and by the kernel's events, rank queries and block loads from the
+LRSC_K_FIND statistics.  Then lrsc_index_remove of the reads it does not call UNIQUE against lrsc_index_build of the kept reads,
+the only route to that index without the removal, alternating, --runs of each after a warm-up of each (which also checks that
+the two routes' units are the same).  The removal's stages come from its LRSC_BWT_PROFILE line (walk, compact, pack, tables),
+the rebuild's from lrsc_index_build's; the device-memory peak of either is what it takes above the resident input.  Writes
+profiles/index_filter.json (or --out)."""
 from __future__ import annotations
 
 import argparse
@@ -524,12 +534,104 @@ def locate_main(args, api, hip, bases, off, n_sym):
     print(json.dumps(result))
 
 
+def filter_main(args, api, hip, bases, off, n_sym):
+    import numpy as np
+
+    from longreadselfcorrect_amd.capi import DUP_UNIQUE, K_FIND
+
+    n_reads = off.size - 1
+    comp = np.zeros(256, dtype=np.uint8)
+    comp[list(b"ACGT")] = list(b"TGCA")
+    reads = []
+    for i in range(n_reads):
+        r = bases[int(off[i]): int(off[i + 1])]
+        if i % 10 == 9:
+            src = reads[i - 1]
+            r = (src, comp[src[::-1]], src[src.size // 4: src.size // 4 * 3])[(i // 10) % 3]
+        reads.append(r)
+    off = np.concatenate([[0], np.cumsum([r.size for r in reads])]).astype(np.uint64)
+    bases = np.concatenate(reads)
+    del reads
+    n_sym = int(off[-1]) + n_reads
+    setup = {}
+    index = clock(setup, "index_build", lambda: api.index_build(bases, off, 0))
+    say(f"{n_reads} reads with every tenth replaced, {n_sym} symbols per strand, built in {setup}")
+
+    batch, checks, cls = 10000, [], None
+    for run_i in range(args.runs + 1):                            # the first is the warm-up
+        ctx = index.ctx(None, 0)
+        session = ctx.dupcheck()
+        t = time.perf_counter()
+        got = [session.reads(bases[int(off[a]): int(off[min(a + batch, n_reads)])], off[a: min(a + batch, n_reads) + 1] - off[a])
+               for a in range(0, n_reads, batch)]
+        wall = time.perf_counter() - t
+        ks = ctx.stats(K_FIND)
+        session.close()
+        ctx.close()
+        got = np.concatenate(got)["cls"]
+        assert cls is None or np.array_equal(cls, got), "the classes differ between two runs"
+        cls = got
+        if run_i:
+            checks.append({"wall_s": wall, "kernel_ms": ks.total_ms, "mbases_per_s_call": int(off[-1]) / wall / 1e6,
+                           "mbases_per_s_kernel": int(off[-1]) / (ks.total_ms / 1e3) / 1e6, "launches": ks.launches, "rank_queries": ks.rank_queries,
+                           "block_loads": ks.block_loads})
+            say(f"duplicate check run {run_i}: {checks[-1]}")
+    drop = (cls != DUP_UNIQUE).astype(np.uint8)
+    keep = np.flatnonzero(drop == 0)
+    kept_bases = np.concatenate([bases[int(off[i]): int(off[i + 1])] for i in keep])
+    kept_off = np.concatenate([[0], np.cumsum((off[1:] - off[:-1])[keep])]).astype(np.uint64)
+    say(f"classes: {np.bincount(cls, minlength=4).tolist()} (unique, substring, full length, absent); {keep.size} reads kept")
+
+    def route_remove(api_, _bases, _off, work):
+        st = {}
+        idx, text = with_profile_line(work, lambda: clock(st, "index_remove", lambda: index.remove(drop, 0)))
+        m = re.search(r"index remove: walk ([\d.]+) ms, compact ([\d.]+) ms, pack ([\d.]+) ms, tables ([\d.]+) ms", text)
+        if m:
+            st["walk"], st["compact"], st["pack"], st["tables"] = (float(x) / 1e3 for x in m.groups())
+        return idx, st
+
+    with tempfile.TemporaryDirectory() as d:
+        work = Path(d)
+        routes = {"remove": route_remove, "rebuild": route_build}
+        units = {}
+        for name, fn in routes.items():                           # warm-up, and the two routes' indexes are one
+            idx, _ = fn(api, kept_bases, kept_off, work)
+            units[name] = [hash(idx.units(s, 0).tobytes()) for s in (0, 1)]
+            idx.close()
+        assert units["remove"] == units["rebuild"], "the index without the dropped reads is not the rebuilt one"
+        runs = {k: [] for k in routes}
+        for i in range(args.runs):
+            for name, fn in routes.items():
+                r = run(api, hip, fn, kept_bases, kept_off, work)
+                runs[name].append(r)
+                say(f"run {i} {name}: {r['wall_s']:.2f} s {r['stages_s']} peak {r['device_peak_bytes'] / 2**30:.2f} GiB")
+    walls = {k: [r["wall_s"] for r in v] for k, v in runs.items()}
+    result = {
+        "workload": {"genome_mb": args.genome_mb, "reads": n_reads, "symbols_per_strand": n_sym, "bases": int(off[-1]),
+                     "classes_unique_substring_full_absent": np.bincount(cls, minlength=4).tolist(), "reads_kept": int(keep.size),
+                     "symbols_per_strand_kept": int(kept_off[-1]) + int(keep.size), "dupcheck_batch": batch},
+        "setup_s": setup,
+        "dupcheck": checks,
+        "runs": runs,
+        "wall_s": {k: {"all": v, "min": min(v), "max": max(v), "spread": max(v) - min(v)} for k, v in walls.items()},
+        "remove_below_rebuild_in_every_pairing": max(walls["remove"]) < min(walls["rebuild"]),
+        "remove_over_rebuild": {"best": min(walls["remove"]) / max(walls["rebuild"]), "worst": max(walls["remove"]) / min(walls["rebuild"])},
+        # above the resident input: the bitmap, one strand's BWT of the kept reads or the sort's workspace, the packed images, the k-mer tables
+        "device_peak_bytes": {k: max(r["device_peak_bytes"] for r in v) for k, v in runs.items()},
+    }
+    index.close()
+    out = args.out or str(REPO / "profiles" / "index_filter.json")
+    Path(out).parent.mkdir(parents=True, exist_ok=True)
+    Path(out).write_text(json.dumps(result, indent=1) + "\n")
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--genome-mb", type=float, default=11.1)
     ap.add_argument("--reads", type=int, default=100000)
     ap.add_argument("--runs", type=int, default=2)
-    ap.add_argument("--out", default=None, help="default: profiles/index_in_memory.json; profiles/index_rle.json with --rle, index_open.json with --open, index_merge.json with --merge, index_locate.json with --locate")
+    ap.add_argument("--out", default=None, help="default: profiles/index_in_memory.json; profiles/index_rle.json with --rle, index_open.json with --open, index_merge.json with --merge, index_locate.json with --locate, index_filter.json with --filter")
     ap.add_argument("--rle", action="store_true", help="measure the device RL encoder instead (see the module text)")
     ap.add_argument("--rle-call-only", action="store_true", help="the encoder's calls once (the child run under the profiler)")
     ap.add_argument("--call-only", action="store_true", help="one lrsc_index_build (the child run under the profiler)")
@@ -537,6 +639,7 @@ def main():
     ap.add_argument("--open-call-only", action="store_true", help="one lrsc_index_open_device of --files (the child run under the profiler)")
     ap.add_argument("--merge", action="store_true", help="measure the device merge instead (see the module text)")
     ap.add_argument("--locate", action="store_true", help="measure the device locate instead (see the module text)")
+    ap.add_argument("--filter", action="store_true", help="measure the duplicate check and the read removal instead (see the module text)")
     ap.add_argument("--rows", type=int, default=1000000, help="--locate: random rows to locate")
     ap.add_argument("--files", nargs=2, metavar=("BWT", "RBWT"))
     ap.add_argument("--no-profile", action="store_true")
@@ -559,6 +662,8 @@ def main():
         return merge_main(args, api, hip, bases, off, n_sym)
     if args.locate:
         return locate_main(args, api, hip, bases, off, n_sym)
+    if args.filter:
+        return filter_main(args, api, hip, bases, off, n_sym)
     if args.call_only:
         api.index_build(bases, off, 0).close()
         return
