@@ -27,6 +27,7 @@ struct lrsc::CorrectScratch {
     DevBuf<WpRequest> d_req;
     DevBuf<uint8_t> d_prep, d_lane, d_lane_side, d_lane_wide;
     DevBuf<uint32_t> d_wide_list;          // the escalated walks of a round (-l above the narrow cap)
+    DevBuf<uint32_t> d_sort9;              // the interval lists of a round that take the sort (WpArgs::sort9)
     hipStream_t side = nullptr;
     hipEvent_t ev_ready = nullptr;
     DevBuf<unsigned long long> d_prof;
@@ -103,6 +104,7 @@ struct WpFlow {
         bool long_launch = false;          // they go to the side stream, beside the first DP call ...
         bool long_pending = false;         // ... and are running there
         uint32_t n_items = 0;              // DP requests of the round
+        unsigned long long begin_stats[4] = {};    // WpArgs::begin_stats (LRSC_CORRECT_PROFILE)
     };
 
     WpFlow(lrsc_ctx* ctx_, lrsc_batch* b_)
@@ -209,6 +211,7 @@ int WpFlow::bind_args()
     a.psz = ctx->fm.wide ? 8 : 4; a.lbytes = lbytes;
     a.plan_stats = small(kWpSmallPlanStats); a.queue = small(kWpSmallQueue); a.n_dp_items = small(kWpSmallDpItems);
     a.n_req_out = small(kWpSmallReqOut);
+    a.n_sort9 = small(kWpSmallSort9); a.begin_sort = tn.wp_begin_sort ? 1u : 0u;
     a.req_out = sc.d_req.p; a.req_cap = n;
     a.out_codes = sc.d_codes_out.p; a.piece_start = sc.d_pieces.p;
     a.auto_dp = (!p.no_dp && p.next_target == 1) ? 1u : 0u;
@@ -221,9 +224,10 @@ int WpFlow::bind_args()
         b->walk_log_done = false;
     }
     if(tn.profile) {
-        HIP_TRY(sc.d_prof.reserve(32));                                      // [16..32): the long-gap walks' side launch on its own
-        HIP_TRY(hipMemsetAsync(sc.d_prof.p, 0, 32 * sizeof(unsigned long long), ctx->stream));
+        HIP_TRY(sc.d_prof.reserve(36));                                      // [16..32): the long-gap walks' side launch on its own
+        HIP_TRY(hipMemsetAsync(sc.d_prof.p, 0, 36 * sizeof(unsigned long long), ctx->stream));
         a.prof = sc.d_prof.p;
+        a.begin_stats = sc.d_prof.p + 32;                                    // [32..36): wp_begin's interval lists, zeroed every round
     }
     // side stream: the few walks across long gaps run beside the DP stage of the bulk's failed walks instead of before it (they are
     // latency-bound on their own: a walk is a chain of dependent steps)
@@ -270,7 +274,11 @@ int WpFlow::run_range()
         if(st == LRSC_OK) st = stitch();
         if(st == LRSC_OK && tn.profile && round == 0 && tn.wp_dump) st = dump_range_walks();
         if(st != LRSC_OK) return st;
-        if(tn.profile) print_round(R);
+        if(tn.profile) {
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+            HIP_TRY(hipMemcpy(R.begin_stats, a.begin_stats, sizeof(R.begin_stats), hipMemcpyDeviceToHost));
+            print_round(R);
+        }
         if(round > 100000) return fail(LRSC_ERR_LIMIT, "walk-parallel flow: too many rounds");
     }
     return LRSC_OK;
@@ -301,6 +309,9 @@ int WpFlow::round_entries(Round& R, bool* done)
     HIP_TRY(sc.d_list.reserve(n_ent));
     HIP_TRY(sc.d_list_tmp.reserve(n_ent));
     HIP_TRY(sc.d_items.reserve(n_ent));
+    HIP_TRY(sc.d_sort9.reserve(2 * (size_t)n_ent));
+    a.sort9 = sc.d_sort9.p;
+    if(a.begin_stats) HIP_TRY(hipMemsetAsync(a.begin_stats, 0, 4 * sizeof(unsigned long long), ctx->stream));
     a.sz_q = sc.d_sz.p; a.sz_prep = sc.d_sz.p + (n_ent + 1); a.sz_path = sc.d_sz.p + 2 * ((size_t)n_ent + 1);
     a.sort_key = sc.d_key.p;
     a.n_list = n_ent;
@@ -588,6 +599,13 @@ void WpFlow::print_round(const Round& R) const
     std::fprintf(stderr, "[lrsc] wp reads [%u, %u) round %u: %u entries, %u DP requests (%llu strings), arenas q %.1f MB prep %.1f MB path %.1f MB, %llu walks escalated so far\n",
                  r0, r1, R.index, R.n_ent, R.n_items, (unsigned long long)sc.stage.n_strings, R.tot[0] / 1048576.0, R.tot[1] / 1048576.0, R.tot[2] / 1048576.0,
                  (unsigned long long)n_escalated);
+    const unsigned long long* g = R.begin_stats;
+    if(tn.wp_begin_sort)                                                     // every list sorted: repeats are not looked for
+        std::fprintf(stderr, "[lrsc] wp reads [%u, %u) round %u: wp_begin %llu interval lists, %llu entries, every list sorted (LRSC_WP_BEGIN_SORT)\n",
+                     r0, r1, R.index, g[0], g[2] + g[3]);
+    else
+        std::fprintf(stderr, "[lrsc] wp reads [%u, %u) round %u: wp_begin %llu interval lists, %llu with a repeated code (%.1f%%); entries %llu in the lists without one, %llu in those with one\n",
+                     r0, r1, R.index, g[0], g[1], 100.0 * g[1] / std::max(g[0], 1ull), g[2], g[3]);
 }
 
 // per-region lane ticks of the extension kernels over the whole call

@@ -88,6 +88,7 @@ struct DevArena {
 struct Tunables {
     bool profile, wp_dump, dp_debug;
     uint32_t wp_wide_cap, wp_wave, wp_lanes;
+    bool wp_begin_sort;
     uint64_t wp_prep_bytes, wp_lane_bytes;
     uint32_t wp_gen_quorum, wp_gen_wait;
     uint64_t dp_chunk_bytes;

@@ -221,7 +221,7 @@ struct Walk : WalkCap<BIG> {
     // workspace
     SortItem *it9f, *it9r;
     uint32_t n9f, n9r;
-    uint16_t *next9f, *next9r, *head9f, *head9r;      // chains in sorted order, 256 hash buckets
+    uint16_t *next9f, *next9r, *head9f, *head9r;      // chains of equal-code entries in post-sort order, 256 hash buckets
     uint16_t *next5, *head5;                          // 5-mer chains by code (1024 heads), flags5 tells strand validity
     const uint8_t* flags5;
     const P* term;
@@ -790,6 +790,9 @@ struct Walk : WalkCap<BIG> {
     // maxLeaves is a narrow launch's capacity below the walk's true -l: overflowing it (or the result slots) is not the walk's end
     // but LRSC_WALK_NEEDS_WIDE from finish()
     bool escalate = false;
+    // test hook (LRSC_WP_BEGIN_SORT): every interval list takes the sort, repeated code or not
+    bool sort_always = false;
+    uint32_t rep9 = 0;                 // begin_static: bit 0 / 1 = it9f / it9r holds a repeated code (not looked for with sort_always)
 
     // The constructor's lengths of a walk across a gap of `dis` characters from a k-mer of initk characters (.cpp:55-58,78-79: double
     // expressions truncated to size_t)
@@ -800,31 +803,81 @@ struct Walk : WalkCap<BIG> {
         minLength = (uint64_t)((0.8 * (dis - 20)) + (double)(2 * (uint64_t)initk));
     }
 
-    // The constructor's per-walk tables that stay fixed during the walk (.cpp:90-94,127-152 after the bulk look-ups of
-    // prepare_offset): the interval "trees" as sorted k-mer chains, the 5-mer chains, the isTerminated filter.
-    LRSC_WALK_FN LRSC_WALK_NOINLINE void begin_static()
+    // ---- the interval "trees" of the constructor (.cpp:127-152; PacBio/IntervalTree.cpp:18): per strand, the valid idmer entries of
+    //      m_query sorted by interval start with std::sort, here as chains of equal-code entries through 256 hash buckets --------
+    // build9: compact (emplace_back order), then chain; the step-for-step introsort runs only for a list in which some code occurs
+    // twice among the valid entries.  Why any order is exact for the others:
+    //  1. The consumer filters by code.  seed_support_core is the only reader of it9f / it9r: it walks one bucket's chain, skips
+    //     every entry whose pad differs from the leaf's code and reads val of the rest, in chain order.  All it can see of the
+    //     sort is the relative order of the entries that carry the same code.
+    //  2. Equal key <=> equal code.  The key is the start of the idmer's suffix-array interval (reverse(kmer) in the rbwt,
+    //     revcomp(kmer) in the bwt).  Equal k-mers have the same interval; different k-mers of one length have disjoint
+    //     non-empty intervals, hence different starts.  So a list without a repeated code has no two equal keys and no two
+    //     entries whose relative order can be observed; a list with one keeps the exact sort.  (The check compares pad, what the
+    //     consumer compares: with seedSize > 16 pad holds the last 16 characters only, different k-mers can share it, and such a
+    //     list takes the sort like any other repeat.)
+    //  3. Entries with kNoKey (empty interval on this strand) are compacted away before the check: a repeat among them is never
+    //     chained, and a code that is valid on one strand only counts on that strand only.
+    LRSC_WALK_FN __forceinline__ uint32_t compact9(SortItem* it, uint32_t n_all) const
     {
-        // --- interval "trees": compact the valid 9-mer entries (emplace_back order), introsort, chain by k-mer ---
-        auto build9 = [&](SortItem* it, uint32_t n_all, uint16_t* head, uint16_t* next) -> uint32_t {
-            uint32_t n = 0;
-            for(uint32_t i = 0; i < n_all; ++i)
-                if(it[i].key != kNoKey) { if(n != i) it[n] = it[i]; ++n; }
-            introsort(it, (int64_t)n);
-            for(uint32_t b = 0; b < 256; ++b) head[b] = 0xFFFFu;
-            // append in sorted order: chains keep the post-sort order of equal keys
-            uint16_t tail[256];
-            for(uint32_t j = 0; j < n; ++j) {
-                const uint32_t code = it[j].pad;
-                const uint32_t hb = (code ^ (code >> 9)) & 255u;
-                next[j] = 0xFFFFu;
-                if(head[hb] == 0xFFFFu) head[hb] = (uint16_t)j; else next[tail[hb]] = (uint16_t)j;
-                tail[hb] = (uint16_t)j;
+        uint32_t n = 0;
+        for(uint32_t i = 0; i < n_all; ++i)
+            if(it[i].key != kNoKey) { if(n != i) it[n] = it[i]; ++n; }
+        return n;
+    }
+    // chains over it[0, n) in array order, stopping at the first entry whose code is already in its bucket: true = a code repeats
+    // (the chains are unfinished then: sort9 rebuilds them)
+    LRSC_WALK_FN __forceinline__ bool chain9_unique(const SortItem* it, uint32_t n, uint16_t* head, uint16_t* next) const
+    {
+        for(uint32_t b = 0; b < 256; ++b) head[b] = 0xFFFFu;
+        for(uint32_t j = 0; j < n; ++j) {
+            const uint32_t code = it[j].pad;
+            const uint32_t hb = (code ^ (code >> 9)) & 255u;
+            uint32_t last = 0xFFFFu;
+            for(uint32_t k = head[hb]; k != 0xFFFFu; k = next[k]) {
+                if(it[k].pad == code) return true;
+                last = k;
             }
-            return n;
-        };
+            next[j] = 0xFFFFu;
+            if(last == 0xFFFFu) head[hb] = (uint16_t)j; else next[last] = (uint16_t)j;
+        }
+        return false;
+    }
+    // introsort, then the chains appended in sorted order: they keep the post-sort order of equal keys
+    LRSC_WALK_FN static __forceinline__ void sort9(SortItem* it, uint32_t n, uint16_t* head, uint16_t* next)
+    {
+        introsort(it, (int64_t)n);
+        for(uint32_t b = 0; b < 256; ++b) head[b] = 0xFFFFu;
+        uint16_t tail[256];
+        for(uint32_t j = 0; j < n; ++j) {
+            const uint32_t code = it[j].pad;
+            const uint32_t hb = (code ^ (code >> 9)) & 255u;
+            next[j] = 0xFFFFu;
+            if(head[hb] == 0xFFFFu) head[hb] = (uint16_t)j; else next[tail[hb]] = (uint16_t)j;
+            tail[hb] = (uint16_t)j;
+        }
+    }
+
+    // The constructor's per-walk tables that stay fixed during the walk (.cpp:90-94,127-152 after the bulk look-ups of
+    // prepare_offset): the interval "trees" as k-mer chains (build9 above), the 5-mer chains, the isTerminated filter.
+    // defer: a list with a repeated code is left compacted and unsorted; the returned mask names it (bit 0 it9f, bit 1 it9r) and
+    // the caller runs sort9() on it (wp_begin_kernel: the sorting lanes of a launch in wavefronts of their own).  0 otherwise.
+    LRSC_WALK_FN LRSC_WALK_NOINLINE uint32_t begin_static(bool defer = false)
+    {
         const uint32_t n9_all = Lq >= seedSize ? Lq - seedSize + 1 : 0;
-        n9f = build9(it9f, n9_all, head9f, next9f);
-        n9r = build9(it9r, n9_all, head9r, next9r);
+        rep9 = 0;
+        uint32_t todo = 0;
+        for(uint32_t s = 0; s < 2; ++s) {
+            SortItem* it = s ? it9r : it9f;
+            uint16_t* head = s ? head9r : head9f;
+            uint16_t* next = s ? next9r : next9f;
+            const uint32_t n = compact9(it, n9_all);
+            if(s) n9r = n; else n9f = n;
+            bool sort = sort_always;
+            if(!sort) { sort = chain9_unique(it, n, head, next); if(sort) rep9 |= 1u << s; }
+            if(!sort) continue;
+            if(defer) todo |= 1u << s; else sort9(it, n, head, next);
+        }
         for(uint32_t c = 0; c < 1024; ++c) head5[c] = 0xFFFFu;
         const uint32_t n5 = Lq >= 5 ? Lq - 5 + 1 : 0;
         for(uint32_t i = n5; i-- > 0;) {                       // prepend while walking backwards: ascending chains
@@ -848,6 +901,7 @@ struct Walk : WalkCap<BIG> {
                 if(h < 64) tmask0 |= 1ull << h; else tmask1 |= 1ull << (h - 64);
             }
         }
+        return todo;
     }
 
     // --- root (initialRootNode, .cpp:108-124; leafInfo ctor, .h:156-171).  root_iv: the root k-mer's bi-interval {fwd.lo,

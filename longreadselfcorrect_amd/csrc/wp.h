@@ -192,6 +192,12 @@ struct WpArgs {
     DevCounters* ctr;
     unsigned long long* prof;    // LRSC_CORRECT_PROFILE: 16 tick totals of the extension kernel (per-lane wall ticks summed over lanes)
     uint32_t escalate;           // max_leaves is the narrow cap below the true -l: a walk that outgrows it ends with LRSC_WALK_NEEDS_WIDE
+    // wp_begin's two passes: pass 1 appends 2 * entry + strand of every interval list that needs the sort (a repeated code among
+    // its valid entries; every list with begin_sort, LRSC_WP_BEGIN_SORT), pass 2 sorts exactly those
+    uint32_t* sort9;             // [2 * n_list]
+    uint32_t* n_sort9;
+    uint32_t begin_sort;
+    unsigned long long* begin_stats; // LRSC_CORRECT_PROFILE: lists, lists with a repeated code, entries of the lists without / with one
 };
 
 constexpr uint32_t kWpPathwSmall = 64, kWpPathwMid = 256;
@@ -203,6 +209,7 @@ enum WpSmall : uint32_t {
     kWpSmallQueue = 4,            // WpArgs::queue outside the extension launches
     kWpSmallDpItems = 5,          // WpArgs::n_dp_items
     kWpSmallReqOut = 6,           // WpArgs::n_req_out
+    kWpSmallSort9 = 7,            // WpArgs::n_sort9
     kWpSmallExtQueue = 8,         // queue of an extension launch on the ctx stream ...
     kWpSmallSideQueue = 9,        // ... and of the long-gap walks' side launch
     kWpSmallSideDpItems = 12,     // n_dp_items of the side launch
@@ -217,6 +224,7 @@ hipError_t launch_wp_bounds(const WpArgs& a, ReadPlan* plan, hipStream_t stream)
 hipError_t launch_wp_plan(const WpArgs& a, hipStream_t stream);
 hipError_t launch_wp_materialize(const WpArgs& a, hipStream_t stream);
 hipError_t launch_wp_prepare(const FmIndexDev& fm, const WpArgs& a, hipStream_t stream);
+// two launches: the tables of every walk without the sort, then the sort for the lists that pass 1 put on a.sort9
 hipError_t launch_wp_begin(const FmIndexDev& fm, const WpArgs& a, hipStream_t stream);
 hipError_t launch_wp_extend(const FmIndexDev& fm, const WpArgs& a, hipStream_t stream);
 // lane_stride 64 launches with the frontier across the wavefront (wp_wave.hip): one wavefront per walk in flight (a.n_lanes of them)

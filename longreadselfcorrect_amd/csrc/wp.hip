@@ -5,7 +5,8 @@
 //                          repeat-to-unique walk, PacBioSelfCorrectionProcess.cpp:176-184) and the forward DP query
 //   wp_prepare_kernel      wavefront per walk, lane per query offset: bi-intervals of every 5-mer, 9-mer and target 13-mer
 //                          (LongReadCorrectByOverlap.cpp:82-94,127-152) -- one k-mer table entry each
-//   wp_begin_kernel        lane per walk: interval "trees" (introsort + chains), 5-mer chains, isTerminated filter, root interval
+//   wp_begin_kernel        lane per walk: interval "trees" (compaction + chains), 5-mer chains, isTerminated filter, root interval
+//   wp_begin_sort_kernel   lane per interval list with a repeated idmer code: the exact introsort and the chains in sorted order
 //   wp_extend_kernel       persistent lanes, each pulls walks from a queue and runs extendOverlap (.cpp:155-211, walk_device.h);
 //                          a failed walk is handed to the DP stage of the same round
 //   wp_dp_collect_kernel   DP answers -> slots
@@ -24,11 +25,15 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
+#include <algorithm>
+
 #include "walk_device.h"
 #include "wp.h"
 #include "wp_walk.h"
 
 namespace lrsc {
+
+constexpr uint64_t kWpBeginSortBlocks = 32768;      // grid cap of wp_begin_sort_kernel (2 M lanes: a block without work only reads the count)
 
 #ifndef LRSC_WP_EXTEND_OCC
 #define LRSC_WP_EXTEND_OCC 2          // wavefronts per SIMD the extension kernel is compiled for (capi_core.cpp sizes LRSC_WP_LANES to match)
@@ -282,8 +287,20 @@ __global__ __launch_bounds__(64) void wp_begin_kernel(FmIndexDev fm, WpArgs a)
             W.fm = &fm; W.mtab = mtab;
             W.seedSize = a.seed_size; W.minOverlap = a.min_overlap;
             W.n_rank = 0; W.n_blk = 0; W.prof = nullptr;
+            W.sort_always = a.begin_sort != 0;
             wp_bind_static<WIDE>(W, a, s);
-            W.begin_static();
+            // a lane that sorted here would hold its wavefront for the length of the sort: the lists that need it go to pass 2
+            const uint32_t todo = W.begin_static(true);
+            for(uint32_t t = 0; t < 2; ++t)
+                if((todo >> t) & 1u) a.sort9[atomicAdd(a.n_sort9, 1u)] = 2u * i + t;
+            if(a.begin_stats) {
+                const unsigned long long rep = (W.rep9 & 1u) + (W.rep9 >> 1);
+                const unsigned long long e_rep = ((W.rep9 & 1u) ? W.n9f : 0u) + (unsigned long long)((W.rep9 & 2u) ? W.n9r : 0u);
+                atomicAdd(&a.begin_stats[0], 2ull);
+                if(rep) atomicAdd(&a.begin_stats[1], rep);
+                atomicAdd(&a.begin_stats[2], (unsigned long long)W.n9f + W.n9r - e_rep);
+                if(e_rep) atomicAdd(&a.begin_stats[3], e_rep);
+            }
             Leaf<P> root;
             root.suf_lo = 0; root.suf_hi = 0;
             for(uint32_t t = 0; t < s.k; ++t) suf_push(root, s.q[t]);
@@ -295,6 +312,21 @@ __global__ __launch_bounds__(64) void wp_begin_kernel(FmIndexDev fm, WpArgs a)
         }
     }
     flush_counters(a.ctr, n_rank, n_blk);
+}
+
+// pass 2 of wp_begin: entry j of a.sort9 names an interval list that pass 1 left compacted (its length in the walk's header)
+__global__ __launch_bounds__(64) void wp_begin_sort_kernel(WpArgs a)
+{
+    const uint32_t n = *a.n_sort9;
+    for(uint32_t j = blockIdx.x * 64 + threadIdx.x; j < n; j += gridDim.x * 64) {
+        const uint32_t e = a.sort9[j], i = e >> 1, r = e & 1u;
+        const WpSlot& s = a.slots[a.list ? a.list[i] : (uint32_t)a.slot_base + i];
+        const WpPrepLayout L = wp_prep_layout(s.lq, s.trg_len, a.seed_size, a.min_overlap, a.psz);
+        uint8_t* ws = s.prep;
+        const WpStatic* H = reinterpret_cast<const WpStatic*>(ws);
+        Walk<false>::sort9(reinterpret_cast<SortItem*>(ws + (r ? L.item9r : L.item9f)), r ? H->n9r : H->n9f,
+                           reinterpret_cast<uint16_t*>(ws + L.head9) + 256u * r, reinterpret_cast<uint16_t*>(ws + (r ? L.next9r : L.next9f)));
+    }
 }
 
 // ---------------------------------------------------------------------------------------
@@ -652,9 +684,15 @@ hipError_t launch_wp_prepare(const FmIndexDev& fm, const WpArgs& a, hipStream_t 
 hipError_t launch_wp_begin(const FmIndexDev& fm, const WpArgs& a, hipStream_t stream)
 {
     if(a.n_list == 0) return hipSuccess;
+    if(a.n_list >= (1u << 31)) return hipErrorInvalidValue;          // a.sort9 entries are 2 * entry + strand
     const unsigned nb = (a.n_list + 63) / 64;
     if(fm.wide) hipLaunchKernelGGL(wp_begin_kernel<true>, dim3(nb), dim3(64), 0, stream, fm, a);
     else        hipLaunchKernelGGL(wp_begin_kernel<false>, dim3(nb), dim3(64), 0, stream, fm, a);
+    hipError_t e = hipGetLastError();
+    if(e != hipSuccess) return e;
+    // at most one list per lane while the lists fit; the lanes loop over the count that pass 1 left on the device
+    const unsigned ns = (unsigned)std::min<uint64_t>((2ull * a.n_list + 63) / 64, kWpBeginSortBlocks);
+    hipLaunchKernelGGL(wp_begin_sort_kernel, dim3(ns), dim3(64), 0, stream, a);
     return hipGetLastError();
 }
 
