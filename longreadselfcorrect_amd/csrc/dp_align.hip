@@ -9,10 +9,11 @@
 // never-written cells read as 0.  Cells are stored with gap*(band row) already subtracted, and the columns run
 // in turns of four, each turn in the code of its class (outside the matrix / interior / cut by a matrix edge):
 // straight-line code under wave-uniform branches only (dp_column).
-// Traceback: which neighbour the traceback takes at a cell (:604-661) depends only on that cell (its
-// score, the three neighbour scores as _getBandedCellScore sees them, and the two homopolymer tests), so
-// the fill stores the decision itself -- 2 bits per cell, one 64-byte line per column -- and the traceback
-// just follows them, 16 columns per fetch.
+// Traceback: which neighbour the traceback takes at a cell (:604-661) depends only on that cell: its score against the three
+// neighbour scores as _getBandedCellScore sees them, the two homopolymer tests and the mismatch test.  The last three are functions of
+// the two sequences alone, so the fill stores only the two score comparisons the decision can need -- 2 bits per cell, one 64-byte line
+// per column -- and the traceback, which visits a few hundred of a matrix's tens of thousands of cells, finishes the decision at the
+// cells it walks: trace words 16 columns per fetch, sequence characters in windows across the lanes.
 #include <hip/hip_runtime.h>
 
 #include "dp_dev.h"
@@ -58,27 +59,39 @@ constexpr uint32_t dp_dir_tree(bool eq_diag, bool eq_up, bool eq_left, bool h1, 
     if(dir == 0u && mismatch) dir = 1u;
     return dir;
 }
-// The same function as two boolean expressions, one per bit of the code: on lane predicates these are scalar mask operations, where
-// the tree is a nest of exec-mask regions.
-// (a choice c ? a : b between predicates is written b ^ (c & (a ^ b)): as a select the compiler takes it through vector registers)
-constexpr bool dp_pick(bool c, bool a, bool b) { return b ^ (c & (a ^ b)); }
-constexpr bool dp_dir_bit1(bool eq_diag, bool eq_up, bool eq_left, bool h1, bool h2)
+// What the fill stores of it (dp_column): B = eq_left, and A = the one of eq_up / eq_diag the tree can ask for at this cell: eq_up where a
+// homopolymer test holds, eq_diag where neither does.  The traceback has h1, h2 and mismatch from the sequences and finishes the choice.
+constexpr uint32_t dp_dir_finish(bool A, bool B, bool h1, bool h2, bool mismatch)
 {
-    return dp_pick(h1 | h2, eq_up | eq_left, !eq_diag);
+    uint32_t dir = 0;
+    if(h2) dir = A ? 2u : B ? 3u : 0u;
+    else if(h1) dir = B ? 3u : A ? 2u : 0u;
+    else dir = A ? 0u : B ? 3u : 2u;
+    if(dir == 0u && mismatch) dir = 1u;
+    return dir;
 }
-constexpr bool dp_dir_bit0(bool eq_diag, bool eq_up, bool eq_left, bool h1, bool h2, bool mismatch)
-{
-    return dp_pick(h2, !eq_up & (eq_left | mismatch), dp_pick(h1, eq_left | (!eq_up & mismatch), dp_pick(eq_diag, mismatch, eq_left)));
-}
-constexpr bool dp_dir_bits_match_tree()
+constexpr bool dp_dir_finish_matches_tree()
 {
     for(uint32_t m = 0; m < 64; ++m) {
         const bool d = m & 1, u = m & 2, l = m & 4, h1 = m & 8, h2 = m & 16, x = m & 32;
-        if(dp_dir_tree(d, u, l, h1, h2, x) != ((uint32_t)dp_dir_bit1(d, u, l, h1, h2) << 1 | (uint32_t)dp_dir_bit0(d, u, l, h1, h2, x))) return false;
+        if(dp_dir_tree(d, u, l, h1, h2, x) != dp_dir_finish((h1 | h2) ? u : d, l, h1, h2, x)) return false;
     }
     return true;
 }
-static_assert(dp_dir_bits_match_tree(), "the two-bit form of the traceback decision differs from the reference's tree");
+static_assert(dp_dir_finish_matches_tree(), "the traceback's decision from the two stored comparisons differs from the reference's tree");
+// The traceback's step, dp_dir_finish without the mismatch (which only turns M into M over a mismatch), as a table of 16 two-bit
+// entries indexed by A | B << 1 | h1 << 2 | h2 << 3: bit 0 = ti steps back, bit 1 = tj steps back, so 3 = M, 2 = I, 1 = D.  One shift on
+// the traceback's serial chain.
+constexpr uint32_t dp_step_table()
+{
+    uint32_t tab = 0;
+    for(uint32_t m = 0; m < 16; ++m) {
+        const uint32_t dir = dp_dir_finish(m & 1, m & 2, m & 4, m & 8, false);
+        tab |= (dir == 0u ? 3u : dir == 2u ? 2u : 1u) << (2 * m);
+    }
+    return tab;
+}
+constexpr uint32_t kDpStepTable = dp_step_table();
 
 // What a lane knows about its four band rows r0 .. r0 + 3 for the whole launch.
 struct DpLane {
@@ -98,7 +111,12 @@ struct DpScores { int ms, mx, g, g2; };
 // the last of them unless it is also the first, else -1: the row that ignores "left" (overlapper.cpp:476,:506-512; the first computed
 // row never takes "up" because the rows below it are masked out of the scan).
 // c1 / h1: this column's s1 character and its homopolymer test (wave-uniform); e[K .. K + 4]: s2 characters of rows r0 .. r0 + 4;
-// h2[K + t]: e[K + t] == e[K + t + 1].  Returns the lane's four 2-bit traceback codes.
+// h2[K + t]: e[K + t] == e[K + t + 1].  Returns the lane's four 2-bit traceback codes, A | B << 1 of dp_dir_finish.
+// The codes of rows outside [rlo, rhi) (and of rows >= bw) are whatever the comparisons give: the traceback reads a code only at a cell
+// (ti, tj) with 1 <= tj <= L2 and band row 0 <= tj - jb < bw (it stops with `bad` outside the band), and [rlo, rhi) is exactly the band
+// rows r of the column with 1 <= jb + r <= L2.  For the same reason the zero line of a column whose band lies outside the matrix (the
+// first class of a turn) is never read: no row of such a column has 1 <= j <= L2.  That matters now: a code of 0 is no neutral "M"
+// any more, it reads as "I" where neither homopolymer test holds.
 template <bool EDGE, int K>
 __device__ __forceinline__ uint32_t dp_column(const DpLane& C, const DpScores& sc, const int (&Hp)[4], int (&Hc)[4], uint32_t c1, bool h1,
                                               const uint32_t (&e)[8], const bool (&h2)[7], int rlo, int rhi, int rlast)
@@ -131,13 +149,10 @@ __device__ __forceinline__ uint32_t dp_column(const DpLane& C, const DpScores& s
     uint32_t flags = 0;
 #pragma unroll
     for(int t = 0; t < 4; ++t) {
-        const bool eq_diag = Hc[t] == diag[t];
-        const bool eq_up = Hc[t] == (t > 0 ? Hc[t - 1] : below);
+        const int up = t > 0 ? Hc[t - 1] : below;
+        const bool eq_a = Hc[t] == ((h1 | h2[K + t]) ? up : diag[t]);
         const bool eq_left = Hc[t] == leftg[t];
-        bool b1 = dp_dir_bit1(eq_diag, eq_up, eq_left, h1, h2[K + t]);
-        bool b0 = dp_dir_bit0(eq_diag, eq_up, eq_left, h1, h2[K + t], mis[t]);
-        if(EDGE) { b1 = b1 & inr[t]; b0 = b0 & inr[t]; }        // interior: the codes of rows >= bw are never read
-        flags |= (b0 ? 1u << (2 * t) : 0u) | (b1 ? 2u << (2 * t) : 0u);
+        flags |= (eq_a ? 1u << (2 * t) : 0u) | (eq_left ? 2u << (2 * t) : 0u);
     }
     return flags;
 }
@@ -171,8 +186,10 @@ __device__ __forceinline__ void dp_copy(int (&dst)[4], const int (&src)[4])
 }
 } // namespace
 
+// amdgpu_waves_per_eu(8): the kernel is sized for eight wavefronts per SIMD, i.e. 64 VGPRs, and says so: left to itself the register
+// allocator took 66 in the global variant.  tests/test_align_kernel_build.py holds that the limit costs no scratch and no spills.
 template <bool GLOBAL>
-__global__ __launch_bounds__(64) void dp_align_kernel(DpAlignArgs a)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8))) void dp_align_kernel(DpAlignArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
     // the two sequences are staged in LDS, or -- for the few alignments beyond it -- in this wavefront's slice of a global workspace
@@ -257,6 +274,7 @@ __global__ __launch_bounds__(64) void dp_align_kernel(DpAlignArgs a)
             const int jb0 = origin + i;                             // first matrix row of the band in the first of the columns
             uint8_t* tr = trace + (uint64_t)i * kDpTraceStride + tid;
             if(n == 4 && (jb0 + 3 + bw <= 1 || jb0 >= num_rows)) {  // the band lies outside the matrix in all four: cells read as 0
+                                                                    // (codes the traceback never reads, see dp_column)
 #pragma unroll
                 for(int k = 0; k < 4; ++k) tr[k * kDpTraceStride] = 0;
 #pragma unroll
@@ -334,7 +352,7 @@ __global__ __launch_bounds__(64) void dp_align_kernel(DpAlignArgs a)
         ti = __builtin_amdgcn_readfirstlane(ti);
         tj = __builtin_amdgcn_readfirstlane(tj);
         o.m0e = ti - 1; o.m1e = tj - 1;
-        o.edit_distance = 0; o.total_columns = 0;
+        o.edit_distance = 0;
 
         // ---- traceback ----------------------------------------------------------------------------------------
         const uint64_t t_job1 = __builtin_readcyclecounter();
@@ -342,33 +360,57 @@ __global__ __launch_bounds__(64) void dp_align_kernel(DpAlignArgs a)
         __threadfence();
         uint32_t w0 = 0, w1 = 0, w2 = 0, w3 = 0;
         int wb = -1;                                                // first column of the 16-column window held in w0..w3
+        uint32_t wcur = 0, key = ~0u;                               // the one of w0..w3 that holds band rows 16 d ..: key = wb | d
+        // the sequence tests of a cell come from two windows across the lanes, one v_readlane each (the fill's indexing: h1 = c[k] == c[k + 1]
+        // with c[k] = S1[i - 1]; h2 = e == e' and mismatch = c[k] != e with e = S2[j - 1], e' = S2[j]; S1[L1] = 4, S2[j >= L2] = 4):
+        uint32_t v1 = 0;                                            // lane l, column i = wb + l: S1[i - 1] << 4 | h1 << 2; loaded with w0..w3
+        uint32_t v2 = 0;                                            // lane l, row j = s2_base + l + 1: S2[j - 1] << 4 | h2 << 3
+        int s2_base = 0x40000000;
         uint32_t acc = 0, n_ops = 0;
         uint8_t* ops = a.ops + J.ops_off;
         bool bad = false;
         while(ti > 0 && tj > 0) {
-            if((ti & ~15) != wb) {
-                wb = ti & ~15;
-                const uint32_t* src = reinterpret_cast<const uint32_t*>(trace + (uint64_t)(wb + (int)(lane >> 2)) * kDpTraceStride + (lane & 3u) * 16u);
-                w0 = __hip_atomic_load(src + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                w1 = __hip_atomic_load(src + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                w2 = __hip_atomic_load(src + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                w3 = __hip_atomic_load(src + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
             const int r = tj - origin - ti;
-            if(r < 0 || r >= bw) { bad = true; break; }
-            const uint32_t d = ((uint32_t)r >> 4) & 3u;
-            const uint32_t word = d == 0 ? w0 : d == 1 ? w1 : d == 2 ? w2 : w3;
-            const uint32_t src_lane = ((uint32_t)(ti - wb) << 2) | ((uint32_t)r >> 6);
-            const uint32_t code = ((uint32_t)__builtin_amdgcn_readlane((int)word, (int)src_lane) >> (2 * ((uint32_t)r & 15u))) & 3u;
-            uint32_t op;
-            if(code <= 1u) { op = 'M'; o.edit_distance += (int)code; --ti; --tj; }
-            else if(code == 2u) { op = 'I'; o.edit_distance += 1; --tj; }
-            else { op = 'D'; o.edit_distance += 1; --ti; }
-            o.total_columns += 1;
+            if((uint32_t)r >= (uint32_t)bw) { bad = true; break; }
+            const uint32_t k = (uint32_t)(ti & ~15) | (((uint32_t)r >> 4) & 3u);
+            if(k != key) {                                          // every few steps: another 16 columns, or another 16 rows of the band
+                key = k;
+                if((ti & ~15) != wb) {
+                    wb = ti & ~15;
+                    const uint32_t* src = reinterpret_cast<const uint32_t*>(trace + (uint64_t)(wb + (int)(lane >> 2)) * kDpTraceStride + (lane & 3u) * 16u);
+                    w0 = __hip_atomic_load(src + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    w1 = __hip_atomic_load(src + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    w2 = __hip_atomic_load(src + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    w3 = __hip_atomic_load(src + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    int x = wb + (int)lane;                         // lanes 0 .. 15 are read, at 1 <= i <= L1; the others stay inside S1[0 .. L1]
+                    x = x < 1 ? 1 : x > L1 ? L1 : x;
+                    const uint32_t c_prev = S1[x - 1], c_here = S1[x];
+                    v1 = c_prev << 4 | (c_prev == c_here ? 4u : 0u);
+                }
+                const uint32_t d = k & 3u;
+                wcur = d == 0 ? w0 : d == 1 ? w1 : d == 2 ? w2 : w3;
+            }
+            if((uint32_t)(tj - 1 - s2_base) > 63u) {                // every 64 rows
+                s2_base = tj - 64;                                  // S2[tj - 64 .. tj] lies in [-63, L2]: staged (pad before, 4 from S2[L2] on)
+                const uint8_t* p = S2 + (s2_base + (int)lane);
+                const uint32_t e_prev = p[0], e_here = p[1];
+                v2 = e_prev << 4 | (e_prev == e_here ? 8u : 0u);
+            }
+            const uint32_t col = (uint32_t)(ti - wb);
+            const uint32_t ab = ((uint32_t)__builtin_amdgcn_readlane((int)wcur, (int)(col << 2 | (uint32_t)r >> 6)) >> (2 * ((uint32_t)r & 15u))) & 3u;
+            // bits 2, 3: h1, h2; above them the two characters' difference
+            const uint32_t x = (uint32_t)__builtin_amdgcn_readlane((int)v1, (int)col) ^ (uint32_t)__builtin_amdgcn_readlane((int)v2, tj - 1 - s2_base);
+            const uint32_t step = (kDpStepTable >> (2 * (ab | (x & 12u)))) & 3u;                      // 3 = M, 2 = I, 1 = D
+            const uint32_t edit = (step ^ 3u) | x >> 4;             // not M, or M over a mismatch
+            o.edit_distance += (int)(edit < 1u ? edit : 1u);
+            ti -= (int)(step & 1u);
+            tj -= (int)(step >> 1);
+            const uint32_t op = (0x4D494400u >> (8 * step)) & 0xFFu;                                  // - 'D' 'I' 'M'
             acc = lane == (n_ops & 63u) ? op : acc;
             ++n_ops;
             if((n_ops & 63u) == 0) ops[n_ops - 64 + lane] = (uint8_t)acc;
         }
+        o.total_columns = (int)n_ops;
         if((n_ops & 63u) != 0 && lane < (n_ops & 63u)) ops[(n_ops & ~63u) + lane] = (uint8_t)acc;
         o.m0s = ti; o.m1s = tj;
         o.n_ops = bad ? 0xFFFFFFFFu : n_ops;
