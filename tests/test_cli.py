@@ -194,3 +194,95 @@ def test_stride_index_and_pbcorrect_end_to_end(stride, api, oracle, small_ds, tm
     assert (out / "threshold-table").read_text() == oracle.threshold_text(90)
     assert "Processed 180 sequences" in r.stderr
     want.close(); ob.close(); orb.close()
+
+
+# ---- every pbcorrect option that lands in lrsc_params ---------------------------------------------------------------------------
+# The oracle under the same params, in a process of its own: outside its domain the reference throws (std::string::substr with a
+# k-mer longer than a seed) and the oracle goes down with it, which must not take the test session along.
+_ORACLE_CHILD = r'''
+import json, sys
+from longreadselfcorrect_amd.capi import Params
+from oracle import oracle_py
+prefix, fasta, fields = sys.argv[1], sys.argv[2], json.loads(sys.argv[3])
+p = Params()
+for k, v in fields.items():
+    if k == "offset":
+        p.offset[0], p.offset[1], p.offset[2] = v
+    else:
+        setattr(p, k, v)
+reads = [l.strip() for l in open(fasta) if not l.startswith(">")]
+bases, off = oracle_py.pack_reads(reads)
+o = oracle_py.Oracle()
+ob, orb = o.bwt_load(prefix + ".bwt"), o.bwt_load(prefix + ".rbwt")
+run = o.correct_reads(ob, orb, p, bases, off)
+json.dump({"correct_fa": run.correct_fa, "discard_fa": run.discard_fa, "stats": run.stats}, sys.stdout)
+'''
+
+
+def _params_like_stride_main(api, opts):
+    """lrsc_params from pbcorrect's short options the way PacBioSelfCorrectionMain fills them (host/stride_main.cpp): the
+    defaults of (-g, -c); with any of -k / -u / -r the start k-mer and all three offsets from the options, the ones not given at
+    the option block's defaults; then -e -n -l -i -s -m, and `manual` with -m."""
+    import re
+
+    src = (REPO / "longreadselfcorrect_amd" / "host" / "stride_main.cpp").read_text()
+    block = src[src.index("namespace opt {"):]
+    block = block[: block.index("\n}")]
+    dflt = {m.group(1): m.group(2) for m in re.finditer(r"\b(\w+) = ([-\d.]+)[,;]", block)}
+    offset = [int(x) for x in re.search(r"offset = \{\{(-?\d+), (-?\d+), (-?\d+)\}\}", block).groups()]
+    get = lambda o, name, conv: conv(opts.get(o, dflt[name]))
+    p = api.params_default(get("g", "genome", int), get("c", "PBcoverage", int))
+    if any(o in opts for o in "kur"):
+        p.start_kmer_len = get("k", "startKmerLen", int)
+        p.offset[0], p.offset[1], p.offset[2] = offset[0], int(opts.get("u", offset[1])), int(opts.get("r", offset[2]))
+    p.error_rate, p.next_target, p.max_leaves = get("e", "ErrorRate", float), get("n", "nextTarget", int), get("l", "maxLeaves", int)
+    p.idmer_len, p.min_kmer_len, p.mode = get("i", "idmerLen", int), get("s", "minKmerLen", int), get("m", "mode", int)
+    p.manual, p.split, p.no_dp = int("m" in opts), 0, int("nodp" in opts)
+    return p
+
+
+def _oracle_in_child(prefix, fasta, p):
+    import json
+    import sys
+
+    fields = {n: (list(getattr(p, n)) if n == "offset" else getattr(p, n)) for n, _ in type(p)._fields_}
+    r = subprocess.run([sys.executable, "-c", _ORACLE_CHILD, str(prefix), str(fasta), json.dumps(fields)], cwd=REPO, capture_output=True,
+                       text=True)
+    return json.loads(r.stdout) if r.returncode == 0 else None, r
+
+
+PBCORRECT_OPTION_RUNS = {
+    "e-i-s-l-n": {"c": "90", "g": "5", "e": "0.25", "i": "7", "s": "15", "l": "4", "n": "2", "nodp": None},
+    "k-u-r-m": {"c": "90", "g": "5", "e": "0.25", "i": "7", "s": "15", "l": "4", "n": "2", "nodp": None,
+                "k": "21", "u": "2", "r": "-4", "m": "0"},
+}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("run", list(PBCORRECT_OPTION_RUNS))
+def test_stride_pbcorrect_options_reach_the_device(stride, api, small_ds, tmp_path, run):
+    """`stride pbcorrect -c 90 -g 5 -e 0.25 -i 7 -s 15 -l 4 -n 2 --nodp`, and the same with `-k 21 -u 2 -r -4 -m 0` on top (static
+    k-mers 21 / 23 / 17, manual mode 0): correct.fa, discard.fa and the integer statistics equal the oracle's under the params that
+    PacBioSelfCorrectionMain derives from these options.  Both combinations are used whole: the oracle, run first and in a child
+    process, completes on them (-s 15 does not exceed the smallest static k-mer, 15 here and 17 with -k 21), so no option had to
+    be dropped; each changes the oracle's output against `-c 90 -g 5 --nodp` alone."""
+    n = 40
+    fa = tmp_path / "reads.fa"
+    write_fasta(fa, small_ds.reads[:n])                          # the first reads, corrected against the index of them all
+    opts = PBCORRECT_OPTION_RUNS[run]
+    p = _params_like_stride_main(api, opts)
+    want, child = _oracle_in_child(small_ds.prefix, fa, p)
+    assert want is not None, f"the oracle does not complete on this combination:\n{child.stderr[-2000:]}"
+    dflt, _ = _oracle_in_child(small_ds.prefix, fa, _params_like_stride_main(api, {"c": "90", "g": "5", "nodp": None}))
+    assert (want["correct_fa"], want["stats"]) != (dflt["correct_fa"], dflt["stats"])
+    out = tmp_path / "out"
+    cmd = [stride, "pbcorrect", "-p", small_ds.prefix, "-o", str(out)]
+    for o, v in opts.items():
+        cmd += [("-" if len(o) == 1 else "--") + o] + ([v] if v is not None else [])
+    r = subprocess.run(cmd + [str(fa)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    assert (out / "correct.fa").read_text() == want["correct_fa"]
+    assert (out / "discard.fa").read_text() == want["discard_fa"]
+    got_ints = {l.split(":")[0]: l.split(":")[1].split(",")[0].strip() for l in r.stdout.strip().split("\n") if ":" in l and not l.startswith("Time")}
+    want_ints = {l.split(":")[0]: l.split(":")[1].strip() for l in want["stats"].strip().split("\n")}
+    assert got_ints == want_ints

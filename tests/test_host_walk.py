@@ -51,6 +51,13 @@ def _skip_descs(params, reads, count, seeds, skip):
     return descs
 
 
+def _in_domain(params, desc):
+    """The walks the reference itself can take with these params: source, target and start k-mer at least as long as the k-mers it
+    cuts from them (it throws from substr on shorter ones)."""
+    src, _, trg, _, initk = desc[:5]
+    return min(len(src), len(trg), initk) >= max(params.min_kmer_len, params.idmer_len)
+
+
 def _check(hw, api, oracle, small_ds, ds_units, genome, cov, tables, wide, n_reads, modes=(0, 1), skip=0):
     (u0, u1), n_sym = ds_units
     h = hw.index(u0, u1, n_sym, wide=wide, tables=tables)
@@ -95,3 +102,70 @@ def test_host_walk_repeat_dataset(hw, api, oracle, repeat_ds):
     """Repeat-rich reads: repeat-to-unique walks on the reverse strand, the isInsufficientFreqs / SelectFreqsOfrange branch."""
     n, codes, fast, steps = _check(hw, api, oracle, repeat_ds, _units(repeat_ds), 5, 90, (5, 9), False, 60)
     assert n > 100 and len(codes) >= 2
+
+
+# ---- -i / -s / -e / -c away from their defaults ---------------------------------------------------------------------------------
+# (idmer_len, min_kmer_len, error_rate, coverage); the default setting is the yardstick of the histogram check
+DEFAULT_SETTING = (9, 13, .15, 90)
+OPTION_SETTINGS = [(7, 13, .15, 90), (5, 13, .15, 90), (12, 13, .15, 90), (13, 13, .15, 90), (16, 17, .15, 90),
+                   (9, 11, .15, 90), (9, 9, .15, 90), (9, 17, .15, 90),
+                   (9, 13, .05, 90), (9, 13, .30, 90), (9, 13, .15, 30), (11, 15, .10, 60)]
+MUST_DIFFER = [(5, 13, .15, 90), (9, 13, .30, 90), (9, 13, .15, 30)]      # settings whose oracle code histogram must not be the default's
+OPTION_CASES = [(s, t) for s in OPTION_SETTINGS for t in ((5, 9, 11), ())] + [((7, 13, .15, 90), (5, 7, 13))]
+N_OPTION_READS = 15
+_OPTION_WANT = {}
+
+
+def _option_params(api, setting):
+    idmer, mink, err, cov = setting
+    p = api.params_default(5, cov)
+    p.idmer_len, p.min_kmer_len, p.error_rate = idmer, mink, err
+    return p
+
+
+def _option_want(api, oracle, ds, setting):
+    """The walks of a setting (consecutive seeds plus seed i to seed i + 3, inside the reference's domain) and what the oracle makes
+    of each, computed once per setting and shared by its table configurations."""
+    if setting not in _OPTION_WANT:
+        p = _option_params(api, setting)
+        ob, orb = oracle.bwt_load(ds.prefix + ".bwt"), oracle.bwt_load(ds.prefix + ".rbwt")
+        off = ds.off[: N_OPTION_READS + 1].copy()
+        count, seeds, _ = oracle.find_seeds(ob, orb, p, ds.bases[: int(off[-1])], off)
+        reads = ds.reads[:N_OPTION_READS]
+        descs = [d for d in _walk_descs(p, reads, count, seeds) + _skip_descs(p, reads, count, seeds, 3) if _in_domain(p, d)]
+        want = []
+        for d in descs:
+            wcode, wmerged, wst = oracle.extend_walk(ob, orb, p, *d)
+            want.append((wcode, wmerged, wst[0]))
+        ob.close(); orb.close()
+        _OPTION_WANT[setting] = (descs, want)
+    return _OPTION_WANT[setting]
+
+
+def _histogram(want):
+    h = {}
+    for code, _, _ in want:
+        h[code] = h.get(code, 0) + 1
+    return h
+
+
+@pytest.mark.parametrize("setting,tables", OPTION_CASES, ids=lambda v: "-".join(str(x) for x in v) or "notab")
+def test_host_walk_options(hw, api, oracle, small_ds, ds_units, setting, tables):
+    """Walk::run and the wp_extend_kernel loop under non-default idmer_len / min_kmer_len / error_rate / coverage: with tables of
+    5 / 9 / 11 (the fast table path only where the setting's sizes are among them), without tables (the generic path), and for
+    idmer_len 7 with tables of 5 / 7 / 13 (the fast table path with a 7-base seed)."""
+    descs, want = _option_want(api, oracle, small_ds, setting)
+    hist = _histogram(want)
+    assert len(descs) >= 100 and hist.get(1, 0) > 0 and hist.get(-1, 0) > 0, hist
+    if setting in MUST_DIFFER:
+        assert hist != _histogram(_option_want(api, oracle, small_ds, DEFAULT_SETTING)[1])
+    (u0, u1), n_sym = ds_units
+    h = hw.index(u0, u1, n_sym, wide=False, tables=tables)
+    p = _option_params(api, setting)
+    try:
+        for d, w in zip(descs, want):
+            for mode in (0, 1):
+                code, merged, st, _ = hw.extend_walk(h, p, *d, mode)
+                assert (code, merged, st) == w, (mode, d)
+    finally:
+        hw.index_free(h)

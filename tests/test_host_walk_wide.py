@@ -82,3 +82,30 @@ def test_wide_walk_at_32_is_the_narrow_walk(hww, api, oracle, repeat_ds, repeat_
     finally:
         hww.index_free(h)
         ob.close(); orb.close()
+
+
+@pytest.mark.parametrize("idmer,min_kmer", [(7, 13), (9, 15)], ids=["idmer7", "minkmer15"])
+def test_wide_walk_with_options(hww, api, oracle, repeat_ds, repeat_walks, idmer, min_kmer):
+    """-l 64 away from the default -i / -s: the wide walk builds its tables by the generic path (no k-mer table of 7; none of 15)."""
+    from tests.test_host_walk import _in_domain
+
+    p = _params(api, 64)
+    p.idmer_len, p.min_kmer_len = idmer, min_kmer
+    descs = [d for d in repeat_walks if _in_domain(p, d)]
+    assert len(descs) >= 100
+    (u0, u1), n_sym = _units(repeat_ds)
+    h = hww.index(u0, u1, n_sym, wide=False, tables=(5, 9, 11))
+    ob, orb = oracle.bwt_load(repeat_ds.prefix + ".bwt"), oracle.bwt_load(repeat_ds.prefix + ".rbwt")
+    codes, fronts = set(), 0
+    try:
+        for d in descs:
+            want = oracle.extend_walk(ob, orb, p, *d)
+            codes.add(want[0])
+            for mode in (0, 1):
+                code, merged, steps, front = hww.extend_walk_wide(h, p, *d, mode)
+                assert (code, merged, steps) == (want[0], want[1], want[2][0]), (mode, d[3:])
+                fronts = max(fronts, front)
+    finally:
+        hww.index_free(h)
+        ob.close(); orb.close()
+    assert {1, -1} <= codes and fronts > 32, (codes, fronts)
