@@ -153,6 +153,76 @@ struct alignas(16) Leaf {             // SAIOverlapNode3 + leafInfo, flattened; 
 
 template <class P> __host__ __device__ __forceinline__ int64_t isize(P lo, P hi) { return (int64_t)hi - (int64_t)lo + 1; }
 
+// ---- block moves between DISJOINT slots of a walk's workspace (rings, paths, leaves) --------------------------------------
+// Written as `dst[k] = src[k]` the compiler cannot tell that the slots are disjoint, so each store orders the next load behind
+// it: one memory round trip per element for a lane that has nothing else in flight.  Here a chunk of independent loads is
+// issued back to back into registers and stored after one wait.  The chunk sizes are small on purpose: the lane-per-walk
+// kernel is compiled at its register limit, and a chunk that spills gives back what it saves.
+// 16-byte units through a type that may alias any other (the slots are read as doubles / Leaf fields elsewhere)
+typedef uint32_t CopyU4 __attribute__((ext_vector_type(4), may_alias, aligned(16)));
+typedef uint32_t CopyU1 __attribute__((may_alias));
+constexpr uint32_t kCopyChunk16 = 5;      // 16-byte units per burst (20 registers): divides a ring row's 50
+constexpr uint32_t kCopyChunk4 = 8;       // dwords per burst where only 4-byte alignment holds (path rows)
+
+// nb bursts of kCopyChunk16 16-byte units each, both pointers 16-byte aligned
+__host__ __device__ __forceinline__ void burst_copy16(void* dst_, const void* src_, uint32_t nb)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    CopyU4* dst = reinterpret_cast<CopyU4*>(dst_);
+    const CopyU4* src = reinterpret_cast<const CopyU4*>(src_);
+    for(uint32_t k = 0; k < nb * kCopyChunk16; k += kCopyChunk16) {
+        CopyU4 t[kCopyChunk16];
+#pragma unroll
+        for(uint32_t j = 0; j < kCopyChunk16; ++j) t[j] = src[k + j];
+#pragma unroll
+        for(uint32_t j = 0; j < kCopyChunk16; ++j) dst[k + j] = t[j];
+    }
+#else
+    __builtin_memcpy(dst_, src_, (size_t)nb * kCopyChunk16 * 16);
+#endif
+}
+// n dwords, 4-byte alignment.  A tail shorter than a chunk loads its last dword again instead of branching around each load (a
+// guarded load would wait for itself alone), and guards the stores.
+__host__ __device__ __forceinline__ void burst_copy4(uint32_t* dst_, const uint32_t* src_, uint32_t n)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+    CopyU1* dst = reinterpret_cast<CopyU1*>(dst_);
+    const CopyU1* src = reinterpret_cast<const CopyU1*>(src_);
+    uint32_t k = 0;
+    for(; k + kCopyChunk4 <= n; k += kCopyChunk4) {
+        uint32_t t[kCopyChunk4];
+#pragma unroll
+        for(uint32_t j = 0; j < kCopyChunk4; ++j) t[j] = src[k + j];
+#pragma unroll
+        for(uint32_t j = 0; j < kCopyChunk4; ++j) dst[k + j] = t[j];
+    }
+    if(k < n) {
+        uint32_t t[kCopyChunk4 - 1];
+#pragma unroll
+        for(uint32_t j = 0; j < kCopyChunk4 - 1; ++j) t[j] = src[k + j < n ? k + j : n - 1];
+#pragma unroll
+        for(uint32_t j = 0; j < kCopyChunk4 - 1; ++j) if(k + j < n) dst[k + j] = t[j];
+    }
+#else
+    __builtin_memcpy(dst_, src_, (size_t)n * 4);
+#endif
+}
+// one leaf to another slot (dst != src): the whole leaf in, then out
+template <class P> __host__ __device__ __forceinline__ void leaf_move(Leaf<P>* dst, const Leaf<P>* src)
+{
+    static_assert(sizeof(Leaf<P>) % 16 == 0 && alignof(Leaf<P>) == 16, "a leaf moves as 16-byte units");
+#if defined(__HIP_DEVICE_COMPILE__)
+    constexpr uint32_t N = (uint32_t)(sizeof(Leaf<P>) / 16);
+    CopyU4 t[N];
+#pragma unroll
+    for(uint32_t j = 0; j < N; ++j) t[j] = reinterpret_cast<const CopyU4*>(src)[j];
+#pragma unroll
+    for(uint32_t j = 0; j < N; ++j) reinterpret_cast<CopyU4*>(dst)[j] = t[j];
+#else
+    __builtin_memcpy(static_cast<void*>(dst), static_cast<const void*>(src), sizeof(Leaf<P>));
+#endif
+}
+
 // character `t` (0 = oldest) of the suffix of length l of a leaf's path
 template <class P> __host__ __device__ __forceinline__ uint32_t suf_char(const Leaf<P>& lf, uint32_t l, uint32_t t)
 {
@@ -523,7 +593,7 @@ struct Walk : WalkCap<BIG> {
                 free_leaf_slots(cur[i]);
                 continue;
             }
-            if(w != i) cur[w] = cur[i];
+            if(w != i) leaf_move(&cur[w], &cur[i]);
             ++w;
         }
         n_cur = w;
@@ -769,7 +839,7 @@ struct Walk : WalkCap<BIG> {
         r.match_i = (uint32_t)hit;
         uint32_t* dst = rpaths + (uint64_t)(lf.res_first - 1) * pathw;
         const uint32_t nw = (plen + 15) >> 4;
-        for(uint32_t k = 0; k < nw; ++k) dst[k] = pw[k];
+        burst_copy4(dst, pw, nw);
         uint32_t len = plen;
         if(extra >= 0) { path_set(dst, len, (uint32_t)extra); ++len; }
         r.path_len = len;
@@ -1110,14 +1180,18 @@ struct Walk : WalkCap<BIG> {
                         ch.ring = (uint16_t)__builtin_ctz(ring_free); ring_free &= ring_free - 1u;     // survivors <= 32 slots: never empty here
                         ch.path = (uint16_t)__builtin_ctz(path_free); path_free &= path_free - 1u;
                     }
-                    const double* src = rings + (uint64_t)pr * 100;
-                    double* dst = rings + (uint64_t)ch.ring * 100;
-                    const uint32_t own = (ch.hist_size - 1) % 100;                 // the slot this child overwrites anyway
-                    for(uint32_t k = 0; k < 100; ++k) if(k != own) dst[k] = src[k];
-                    const uint32_t* ps = paths + (uint64_t)pp * pathw;
-                    uint32_t* pd = paths + (uint64_t)ch.path * pathw;
-                    const uint32_t nw = (ch.path_len + 16) >> 4;
-                    for(uint32_t k = 0; k < nw; ++k) pd[k] = ps[k];
+                    // The ring: only the slots the lineage has pushed so far.  The parent has made hist_size - 1 pushes (its
+                    // hist_size is this child's minus the push of this step), into slots 0, 1, ... in turn, wrapping at 100.
+                    // computeErrorRate is the only reader of a slot: it reads (totalsize - localK) % 100 once totalsize >=
+                    // localK = 100, the slot written 100 pushes earlier on the same lineage.  So a slot at or beyond the
+                    // number of pushes is never read before it has been written, and need not be copied.  The count is
+                    // rounded up to whole bursts (a row is 10 of them): what that copies beyond the live slots is the
+                    // child's own slot -- as the parent's in-place child may already have written it -- which the push
+                    // below overwrites, and slots of the never-read kind.
+                    const uint32_t live = ch.hist_size - 1 < 100 ? ch.hist_size - 1 : 100;
+                    const uint32_t nburst = (live * 8 + kCopyChunk16 * 16 - 1) / (kCopyChunk16 * 16);
+                    burst_copy16(rings + (uint64_t)ch.ring * 100, rings + (uint64_t)pr * 100, nburst);
+                    burst_copy4(paths + (uint64_t)ch.path * pathw, paths + (uint64_t)pp * pathw, (ch.path_len + 16) >> 4);
                 }
                 if constexpr(BIG) bits_set(this->seen_bits, ch.parent); else seen |= 1u << ch.parent;
                 rings[(uint64_t)ch.ring * 100 + (ch.hist_size - 1) % 100] = ch.globalErr;     // GlobalErrorRateRecord.push_back
@@ -1130,7 +1204,7 @@ struct Walk : WalkCap<BIG> {
             // m_leaves = newLeaves: the two leaf buffers trade places when the old `cur` region (32 or kMaxChildren slots) can take
             // the next step's children (4 per survivor); otherwise the survivors are copied down as before
             if(4u * w <= (cur == leaf_small ? small_cap() : max_children())) { Leaf<P>* t2 = cur; cur = nxt; nxt = t2; }
-            else for(uint32_t i = 0; i < w; ++i) cur[i] = nxt[i];
+            else for(uint32_t i = 0; i < w; ++i) leaf_move(&cur[i], &nxt[i]);
             n_cur = w;
             tock(5, t);
             t = tick();
@@ -1159,7 +1233,7 @@ struct Walk : WalkCap<BIG> {
             *out_match_i = results[best].match_i;
             const uint32_t* src = rpaths + (uint64_t)best * pathw;
             const uint32_t nw = (results[best].path_len + 15) >> 4;
-            for(uint32_t k = 0; k < nw; ++k) out_words[k] = src[k];
+            burst_copy4(out_words, src, nw);
             return 1;
         }
         if(n_cur == 0) return -1;                    // high error
