@@ -26,7 +26,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/lrsc.h"
+#include "fm_launch.h"
 
 namespace lrsc {
 
@@ -237,11 +237,7 @@ struct Dev {
 
 static inline unsigned nblk(uint64_t n) { return (unsigned)((n + 255) / 256); }
 
-#define BB_TRY(expr)                                                                 \
-    do {                                                                             \
-        hipError_t _e = (expr);                                                      \
-        if(_e != hipSuccess) { err = std::string(#expr) + ": " + hipGetErrorString(_e); return LRSC_ERR_DEVICE; } \
-    } while(0)
+constexpr int kOomStatus = LRSC_ERR_DEVICE;                      // what DEV_TRY answers when device memory runs out
 
 // Scratch of the sorting jobs, sized once for the largest job.
 template <class P>
@@ -275,73 +271,73 @@ static int sort_job(Dev& d, SortSpace<P>& sp, const uint8_t* d_T, uint64_t N, ui
         return e;
     };
     hipLaunchKernelGGL(init_keys_kernel<P>, dim3(nblk(n)), dim3(256), 0, st, d_T, N, n, sp.sa[0], sp.key[0]);
-    BB_TRY(hipGetLastError());
+    DEV_TRY(hipGetLastError());
     // 1. one big stable sort on the first 21 symbols
     hipcub::DoubleBuffer<uint64_t> kb(sp.key[0], sp.key[1]);
     hipcub::DoubleBuffer<P> vb(sp.sa[0], sp.sa[1]);
     size_t need = 0;
-    BB_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, need, kb, vb, (int)n, 0, 63, st));
-    BB_TRY(ensure_tmp(need));
-    BB_TRY(hipcub::DeviceRadixSort::SortPairs(sp.tmp, need, kb, vb, (int)n, 0, 63, st));
+    DEV_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, need, kb, vb, (int)n, 0, 63, st));
+    DEV_TRY(ensure_tmp(need));
+    DEV_TRY(hipcub::DeviceRadixSort::SortPairs(sp.tmp, need, kb, vb, (int)n, 0, 63, st));
     uint64_t* key = kb.Current();
     P* sa = vb.Current();
-    BB_TRY(hipMemsetAsync(sp.bnd, 0, n, st));
+    DEV_TRY(hipMemsetAsync(sp.bnd, 0, n, st));
 
     for(uint64_t depth = kSymsPerKey;; depth += kSymsPerKey) {
         hipLaunchKernelGGL(mark_kernel, dim3(nblk(n)), dim3(256), 0, st, key, n, sp.bnd);
         hipLaunchKernelGGL(unresolved_kernel, dim3(nblk(n)), dim3(256), 0, st, key, sp.bnd, n, sp.flag, sp.head);
-        BB_TRY(hipGetLastError());
+        DEV_TRY(hipGetLastError());
         // compact the unresolved SA positions
         hipcub::CountingInputIterator<uint32_t> iota(0);
-        BB_TRY(hipcub::DeviceSelect::Flagged(nullptr, need, iota, sp.flag, sp.U, sp.nsel, (int)n, st));
-        BB_TRY(ensure_tmp(need));
-        BB_TRY(hipcub::DeviceSelect::Flagged(sp.tmp, need, iota, sp.flag, sp.U, sp.nsel, (int)n, st));
+        DEV_TRY(hipcub::DeviceSelect::Flagged(nullptr, need, iota, sp.flag, sp.U, sp.nsel, (int)n, st));
+        DEV_TRY(ensure_tmp(need));
+        DEV_TRY(hipcub::DeviceSelect::Flagged(sp.tmp, need, iota, sp.flag, sp.U, sp.nsel, (int)n, st));
         uint32_t n_u = 0;
-        BB_TRY(hipMemcpy(&n_u, sp.nsel, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        DEV_TRY(hipMemcpy(&n_u, sp.nsel, sizeof(uint32_t), hipMemcpyDeviceToHost));
         if(n_u == 0) break;
         ++rounds;
         if(depth > (1ull << 22)) { err = "BWT refinement did not converge"; return LRSC_ERR_UNSUPPORTED; }
         // group id of every position = position of the closest boundary at or before it
-        BB_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, need, sp.head, sp.headscan, MaxOp(), (int)n, st));
-        BB_TRY(ensure_tmp(need));
-        BB_TRY(hipcub::DeviceScan::InclusiveScan(sp.tmp, need, sp.head, sp.headscan, MaxOp(), (int)n, st));
+        DEV_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, need, sp.head, sp.headscan, MaxOp(), (int)n, st));
+        DEV_TRY(ensure_tmp(need));
+        DEV_TRY(hipcub::DeviceScan::InclusiveScan(sp.tmp, need, sp.head, sp.headscan, MaxOp(), (int)n, st));
         if(n_u > sp.u_cap) {
             sp.u_cap = n_u;
             for(int b = 0; b < 2; ++b) {
-                BB_TRY(d.alloc(&sp.u_key[b], sp.u_cap));
-                BB_TRY(d.alloc(&sp.u_gid[b], sp.u_cap));
-                BB_TRY(d.alloc(&sp.u_perm[b], sp.u_cap));
-                BB_TRY(d.alloc(&sp.u_p2[b], sp.u_cap));
+                DEV_TRY(d.alloc(&sp.u_key[b], sp.u_cap));
+                DEV_TRY(d.alloc(&sp.u_gid[b], sp.u_cap));
+                DEV_TRY(d.alloc(&sp.u_perm[b], sp.u_cap));
+                DEV_TRY(d.alloc(&sp.u_p2[b], sp.u_cap));
             }
-            BB_TRY(d.alloc(&sp.u_val, sp.u_cap));
+            DEV_TRY(d.alloc(&sp.u_val, sp.u_cap));
         }
         hipLaunchKernelGGL(gather_kernel<P>, dim3(nblk(n_u)), dim3(256), 0, st, d_T, N, depth, sp.U, n_u, sa, sp.headscan,
                            sp.u_key[0], sp.u_gid[0], sp.u_val, sp.u_perm[0]);
-        BB_TRY(hipGetLastError());
+        DEV_TRY(hipGetLastError());
         // sort 1 (stable): by the next 21 symbols.  p1[k] = gathered index of the k-th smallest key.
         hipcub::DoubleBuffer<uint64_t> k2(sp.u_key[0], sp.u_key[1]);
         hipcub::DoubleBuffer<uint32_t> p1(sp.u_perm[0], sp.u_perm[1]);
-        BB_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, need, k2, p1, (int)n_u, 0, 63, st));
-        BB_TRY(ensure_tmp(need));
-        BB_TRY(hipcub::DeviceRadixSort::SortPairs(sp.tmp, need, k2, p1, (int)n_u, 0, 63, st));
+        DEV_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, need, k2, p1, (int)n_u, 0, 63, st));
+        DEV_TRY(ensure_tmp(need));
+        DEV_TRY(hipcub::DeviceRadixSort::SortPairs(sp.tmp, need, k2, p1, (int)n_u, 0, 63, st));
         // sort 2 (stable): by group id, payload = rank in sort-1 order; inside a group the
         // sort-1 order (next 21 symbols, then text position) is preserved.
         hipLaunchKernelGGL(permute_u32_kernel, dim3(nblk(n_u)), dim3(256), 0, st, sp.u_gid[0], p1.Current(), n_u, sp.u_gid[1]);
         hipLaunchKernelGGL(iota_kernel, dim3(nblk(n_u)), dim3(256), 0, st, sp.u_p2[0], n_u);
-        BB_TRY(hipGetLastError());
+        DEV_TRY(hipGetLastError());
         hipcub::DoubleBuffer<uint32_t> gd(sp.u_gid[1], sp.u_gid[0]);
         hipcub::DoubleBuffer<uint32_t> p2(sp.u_p2[0], sp.u_p2[1]);
-        BB_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, need, gd, p2, (int)n_u, 0, 32, st));
-        BB_TRY(ensure_tmp(need));
-        BB_TRY(hipcub::DeviceRadixSort::SortPairs(sp.tmp, need, gd, p2, (int)n_u, 0, 32, st));
+        DEV_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, need, gd, p2, (int)n_u, 0, 32, st));
+        DEV_TRY(ensure_tmp(need));
+        DEV_TRY(hipcub::DeviceRadixSort::SortPairs(sp.tmp, need, gd, p2, (int)n_u, 0, 32, st));
         // U is ascending and groups are contiguous, so the k-th element of the (group, key2) order
         // belongs at SA position U[k].
         hipLaunchKernelGGL(scatter_kernel<P>, dim3(nblk(n_u)), dim3(256), 0, st, sp.U, n_u, p2.Current(), p1.Current(), sp.u_val,
                            k2.Current(), sa, key);
-        BB_TRY(hipGetLastError());
+        DEV_TRY(hipGetLastError());
     }
     hipLaunchKernelGGL(bwt_kernel<P>, dim3(nblk(n)), dim3(256), 0, st, d_T, sa, N, n, d_bwt);
-    BB_TRY(hipGetLastError());
+    DEV_TRY(hipGetLastError());
     return LRSC_OK;
 }
 
@@ -349,9 +345,9 @@ template <class P>
 static int alloc_space(Dev& d, SortSpace<P>& sp, uint32_t cap, std::string& err)
 {
     sp.cap = cap;
-    for(int b = 0; b < 2; ++b) { BB_TRY(d.alloc(&sp.key[b], cap)); BB_TRY(d.alloc(&sp.sa[b], cap)); }
-    BB_TRY(d.alloc(&sp.bnd, cap)); BB_TRY(d.alloc(&sp.flag, cap)); BB_TRY(d.alloc(&sp.head, cap));
-    BB_TRY(d.alloc(&sp.U, cap)); BB_TRY(d.alloc(&sp.nsel, 1)); BB_TRY(d.alloc(&sp.headscan, cap));
+    for(int b = 0; b < 2; ++b) { DEV_TRY(d.alloc(&sp.key[b], cap)); DEV_TRY(d.alloc(&sp.sa[b], cap)); }
+    DEV_TRY(d.alloc(&sp.bnd, cap)); DEV_TRY(d.alloc(&sp.flag, cap)); DEV_TRY(d.alloc(&sp.head, cap));
+    DEV_TRY(d.alloc(&sp.U, cap)); DEV_TRY(d.alloc(&sp.nsel, 1)); DEV_TRY(d.alloc(&sp.headscan, cap));
     return LRSC_OK;
 }
 
@@ -365,14 +361,14 @@ static int build_grouped(Dev& d, const uint8_t* d_T, uint64_t N, uint64_t limit,
     uint32_t len = 0;
     std::vector<unsigned long long> hist;
     unsigned long long* d_hist = nullptr;
-    BB_TRY(d.alloc(&d_hist, 1u << 15));
+    DEV_TRY(d.alloc(&d_hist, 1u << 15));
     for(len = 1; len <= 4; ++len) {
         const uint32_t bins = 1u << (3 * len);
-        BB_TRY(hipMemset(d_hist, 0, bins * sizeof(unsigned long long)));
+        DEV_TRY(hipMemset(d_hist, 0, bins * sizeof(unsigned long long)));
         hipLaunchKernelGGL(prefix_hist_kernel, dim3(4096), dim3(256), bins * sizeof(uint32_t), st, d_T, N, len, d_hist);
-        BB_TRY(hipGetLastError());
+        DEV_TRY(hipGetLastError());
         hist.resize(bins);
-        BB_TRY(hipMemcpy(hist.data(), d_hist, bins * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        DEV_TRY(hipMemcpy(hist.data(), d_hist, bins * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         unsigned long long mx = 0;
         for(unsigned long long h : hist) mx = std::max(mx, h);
         if(mx <= limit) break;
@@ -392,7 +388,7 @@ static int build_grouped(Dev& d, const uint8_t* d_T, uint64_t N, uint64_t limit,
     int rc = alloc_space(d, sp, (uint32_t)largest, err);
     if(rc != LRSC_OK) return rc;
     uint32_t* d_nsel = nullptr;
-    BB_TRY(d.alloc(&d_nsel, 1));
+    DEV_TRY(d.alloc(&d_nsel, 1));
     uint8_t* d_sel_tmp = nullptr;
     size_t sel_cap = 0;
     const uint64_t chunk = 1ull << 30;
@@ -405,16 +401,16 @@ static int build_grouped(Dev& d, const uint8_t* d_T, uint64_t N, uint64_t limit,
             const uint64_t cnt = std::min<uint64_t>(chunk, N - base);
             hipcub::CountingInputIterator<P> first((P)base);
             size_t need = 0;
-            BB_TRY(hipcub::DeviceSelect::If(nullptr, need, first, sp.sa[0] + got, d_nsel, (int)cnt, pred, st));
+            DEV_TRY(hipcub::DeviceSelect::If(nullptr, need, first, sp.sa[0] + got, d_nsel, (int)cnt, pred, st));
             if(need > sel_cap) {
                 if(d_sel_tmp) d.release(d_sel_tmp);
                 d_sel_tmp = nullptr;
-                BB_TRY(d.alloc(&d_sel_tmp, need));
+                DEV_TRY(d.alloc(&d_sel_tmp, need));
                 sel_cap = need;
             }
-            BB_TRY(hipcub::DeviceSelect::If(d_sel_tmp, need, first, sp.sa[0] + got, d_nsel, (int)cnt, pred, st));
+            DEV_TRY(hipcub::DeviceSelect::If(d_sel_tmp, need, first, sp.sa[0] + got, d_nsel, (int)cnt, pred, st));
             uint32_t n_sel = 0;
-            BB_TRY(hipMemcpy(&n_sel, d_nsel, sizeof(uint32_t), hipMemcpyDeviceToHost));
+            DEV_TRY(hipMemcpy(&n_sel, d_nsel, sizeof(uint32_t), hipMemcpyDeviceToHost));
             got += n_sel;
         }
         if(got != g.count) { err = "BWT builder: group size mismatch"; return LRSC_ERR_DEVICE; }
@@ -437,22 +433,22 @@ int build_bwt_resident(const char* reads, const uint64_t* off, uint32_t n_reads,
 {
     const uint64_t total = off[n_reads];
     const uint64_t N = total + n_reads;
-    BB_TRY(hipSetDevice(device));
+    DEV_TRY(hipSetDevice(device));
     hipStream_t st = nullptr;   // default stream: this is a one-off setup step
     Dev d;
     char* d_ascii; uint64_t* d_off; uint8_t* d_T; int* d_bad;
-    BB_TRY(d.alloc(&d_ascii, total));
-    BB_TRY(d.alloc(&d_off, (size_t)n_reads + 1));
-    BB_TRY(d.alloc(&d_T, N + 64));
-    BB_TRY(d.alloc(&d_bad, 1));
-    BB_TRY(hipMemset(d_bad, 0, sizeof(int)));
-    BB_TRY(hipMemset(d_T + N, 0, 64));
-    BB_TRY(hipMemcpy(d_ascii, reads, total, hipMemcpyHostToDevice));
-    BB_TRY(hipMemcpy(d_off, off, ((size_t)n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
+    DEV_TRY(d.alloc(&d_ascii, total));
+    DEV_TRY(d.alloc(&d_off, (size_t)n_reads + 1));
+    DEV_TRY(d.alloc(&d_T, N + 64));
+    DEV_TRY(d.alloc(&d_bad, 1));
+    DEV_TRY(hipMemset(d_bad, 0, sizeof(int)));
+    DEV_TRY(hipMemset(d_T + N, 0, 64));
+    DEV_TRY(hipMemcpy(d_ascii, reads, total, hipMemcpyHostToDevice));
+    DEV_TRY(hipMemcpy(d_off, off, ((size_t)n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(text_kernel, dim3((unsigned)std::min<uint64_t>((N + 255) / 256, 1u << 22)), dim3(256), 0, st, d_ascii, d_off, n_reads, N, reverse_reads, d_T, d_bad);
-    BB_TRY(hipGetLastError());
+    DEV_TRY(hipGetLastError());
     int bad = 0;
-    BB_TRY(hipMemcpy(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost));
+    DEV_TRY(hipMemcpy(&bad, d_bad, sizeof(int), hipMemcpyDeviceToHost));
     if(bad) { err = "sequence contains a base other than A,C,G,T"; return LRSC_ERR_ARG; }
     d.release(d_ascii);
 
@@ -461,7 +457,7 @@ int build_bwt_resident(const char* reads, const uint64_t* off, uint32_t n_reads,
     const char* wp = std::getenv("LRSC_BWT_WIDE_POS");
     const bool wide_pos = N >= (1ull << 32) || (wp && std::atoi(wp) != 0);
     uint8_t* d_bwt;
-    BB_TRY(d.alloc(&d_bwt, N));
+    DEV_TRY(d.alloc(&d_bwt, N));
     uint32_t rounds = 0, n_groups = 1;
     int rc;
     if(N <= limit) {
@@ -485,7 +481,7 @@ int build_bwt_resident(const char* reads, const uint64_t* off, uint32_t n_reads,
     if(std::getenv("LRSC_BWT_PROFILE"))
         std::fprintf(stderr, "[lrsc] BWT of %llu symbols: %u job(s), %u refinement rounds, %d-bit positions\n", (unsigned long long)N, n_groups,
                      rounds, wide_pos ? 64 : 32);
-    BB_TRY(hipDeviceSynchronize());
+    DEV_TRY(hipDeviceSynchronize());
     d.keep(d_bwt);
     *d_bwt_out = d_bwt;
     if(rounds_out) *rounds_out = rounds;

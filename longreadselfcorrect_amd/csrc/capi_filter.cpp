@@ -1,7 +1,5 @@
 // capi_filter.cpp -- what `stride filter` needs of the library: the duplicate check of a batch of reads against a context's
 // index (fm_dup.hip) and the index without some of its reads (fm_remove.hip).
-#include <chrono>
-
 #include "capi_internal.h"
 #include "fm_dup.h"
 #include "fm_remove.h"
@@ -91,7 +89,7 @@ extern "C" int lrsc_dupcheck_reads(lrsc_dupcheck* dc, const char* reads, const u
 // an index without some of its reads (fm_remove.hip)
 // ---------------------------------------------------------------------------------------
 // One strand of lrsc_index_remove: mark + compact -> BWT of the kept reads on the device -> packed image on the device (dc.*[s])
-// -> host image, as the merge does after its interleave.  The first strand's walks tell the result's length and with it its
+// -> host image (adopt_packed).  The first strand's walks tell the result's length and with it its
 // layout; the second strand's must come to the same.  ms: walk, compact, pack.
 static int remove_strand(const FmStrand& fs, bool wide_in, const std::vector<uint32_t>& ids, int s, lrsc_index* res, DeviceCopy& dc, double ms[3],
                          std::string& err)
@@ -102,22 +100,13 @@ static int remove_strand(const FmStrand& fs, bool wide_in, const std::vector<uin
     if(st != LRSC_OK) return st;
     if(s == 0) {
         res->num_symbols = N;
-        res->wide = N >= (1ull << 31) || std::getenv("LRSC_FORCE_WIDE") != nullptr;   // as index_from_units_impl
+        res->wide = index_is_wide(N);
     } else if(N != res->num_symbols) {
         (void)hipFree(d_bwt);
         err = "index remove: .bwt and .rbwt disagree on the lengths of the dropped reads";
         return LRSC_ERR_FORMAT;
     }
-    const auto t0 = std::chrono::steady_clock::now();
-    PackedStrand ps;
-    st = pack_strand_device(d_bwt, N, res->wide, ps, err);
-    (void)hipFree(d_bwt);
-    if(st != LRSC_OK) return st;
-    dc.blocks[s] = ps.blocks;
-    dc.dollars[s] = ps.dollars;
-    dc.dollar_dir[s] = ps.dollar_dir;
-    ms[2] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return image_from_device(ps, N, 0, res->image[s], err);
+    return adopt_packed(d_bwt, N, res->wide, s, dc, res->image[s], ms[2], err);
 }
 
 extern "C" int lrsc_index_remove(lrsc_index* idx, const uint8_t* drop, uint64_t n_reads, int device, lrsc_index** out)
@@ -146,17 +135,9 @@ extern "C" int lrsc_index_remove(lrsc_index* idx, const uint8_t* drop, uint64_t 
         st = remove_strand(fs[s], wide_in, ids, s, res, dc, ms, err);
         if(st != LRSC_OK) st = fail(st, err);
     }
-    if(st == LRSC_OK && (res->image[0].dollars.size() != n_kept || res->image[1].dollars.size() != n_kept))
-        st = fail(LRSC_ERR_FORMAT, "index remove: the '$' rows of the result are not those of the kept reads");
-    if(st == LRSC_OK) {
-        const auto t0 = std::chrono::steady_clock::now();
-        std::lock_guard<std::mutex> lock(res->mu);
-        st = register_copy(res, device, dc);
-        ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    if(st != LRSC_OK) { free_device_copy(dc); delete res; return st; }
-    if(std::getenv("LRSC_BWT_PROFILE"))
-        std::fprintf(stderr, "[lrsc] index remove: walk %.3f ms, compact %.3f ms, pack %.3f ms, tables %.3f ms\n", ms[0], ms[1], ms[2], ms[3]);
+    st = finish_index(res, device, dc, st, n_kept, LRSC_ERR_FORMAT, "index remove: the '$' rows of the result are not those of the kept reads", ms, 3,
+                      "[lrsc] index remove: walk %.3f ms, compact %.3f ms, pack %.3f ms, tables %.3f ms\n");
+    if(st != LRSC_OK) return st;
     *out = res;
     return LRSC_OK;
 }

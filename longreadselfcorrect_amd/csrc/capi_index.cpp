@@ -13,6 +13,8 @@
 
 using namespace lrsc;
 
+bool lrsc::index_is_wide(uint64_t num_symbols) { return num_symbols >= (1ull << 31) || std::getenv("LRSC_FORCE_WIDE") != nullptr; }
+
 static int index_from_units_impl(const uint8_t* u0, uint64_t n0, const uint8_t* u1, uint64_t n1,
                                  uint64_t num_strings, uint64_t num_symbols, lrsc_index** out)
 {
@@ -20,9 +22,7 @@ static int index_from_units_impl(const uint8_t* u0, uint64_t n0, const uint8_t* 
     if(!idx) return fail(LRSC_ERR_NOMEM, "lrsc_index");
     idx->num_strings = num_strings;
     idx->num_symbols = num_symbols;
-    // Block64 (64-bit counters, 128 symbols per block) from 2^31 symbols per strand; LRSC_FORCE_WIDE=1 selects it for any
-    // index so that the wide code path can be tested on small data
-    idx->wide = num_symbols >= (1ull << 31) || std::getenv("LRSC_FORCE_WIDE") != nullptr;
+    idx->wide = index_is_wide(num_symbols);
     int st[2] = {LRSC_OK, LRSC_OK};
     std::string err[2];
     const uint8_t* us[2] = {u0, u1};
@@ -286,28 +286,53 @@ int lrsc::image_from_device(const PackedStrand& ps, uint64_t N, uint64_t n_runs,
     return LRSC_OK;
 }
 
-// One strand of lrsc_index_build: BWT on the device -> packed image on the device (dc.*[s]) -> host image by a copy of the
-// packed arrays (a third of a byte per symbol).  d_bwt is gone before the next strand starts.
-static int build_strand(const char* reads, const uint64_t* off, uint32_t n_reads, int s, int device, bool wide, StrandImage& im,
-                        DeviceCopy& dc, double ms[2], std::string& err)
+int lrsc::adopt_packed(const PackedStrand& ps, uint64_t N, uint64_t n_runs, int s, DeviceCopy& dc, StrandImage& im, std::string& err)
 {
-    using clk = std::chrono::steady_clock;
-    const auto t0 = clk::now();
-    uint8_t* d_bwt = nullptr;
-    int st = build_bwt_resident(reads, off, n_reads, s, device, &d_bwt, nullptr, err);
-    if(st != LRSC_OK) return st;
-    const auto t1 = clk::now();
-    const uint64_t N = off[n_reads] + n_reads;
-    PackedStrand ps;
-    st = pack_strand_device(d_bwt, N, wide, ps, err);
-    (void)hipFree(d_bwt);
-    if(st != LRSC_OK) return st;
     dc.blocks[s] = ps.blocks;
     dc.dollars[s] = ps.dollars;
     dc.dollar_dir[s] = ps.dollar_dir;
-    ms[0] += std::chrono::duration<double, std::milli>(t1 - t0).count();
-    ms[1] += std::chrono::duration<double, std::milli>(clk::now() - t1).count();
-    return image_from_device(ps, N, 0, im, err);
+    return image_from_device(ps, N, n_runs, im, err);
+}
+
+int lrsc::adopt_packed(uint8_t* d_bwt, uint64_t N, bool wide, int s, DeviceCopy& dc, StrandImage& im, double& pack_ms, std::string& err)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    PackedStrand ps;
+    const int st = pack_strand_device(d_bwt, N, wide, ps, err);
+    (void)hipFree(d_bwt);
+    if(st != LRSC_OK) return st;
+    pack_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return adopt_packed(ps, N, 0, s, dc, im, err);
+}
+
+// profile_fmt is applied to ms[0], ms[1], ms[2], ms[3]: it may consume at most those four doubles, in that order, and nothing else
+int lrsc::finish_index(lrsc_index* idx, int device, DeviceCopy& dc, int st, uint64_t n_dollars, int bad_status, const char* bad_msg, double ms[4],
+                       int tables_slot, const char* profile_fmt)
+{
+    if(st == LRSC_OK && bad_msg && (idx->image[0].dollars.size() != n_dollars || idx->image[1].dollars.size() != n_dollars))
+        st = fail(bad_status, bad_msg);
+    if(st == LRSC_OK) {
+        const auto t0 = std::chrono::steady_clock::now();
+        std::lock_guard<std::mutex> lock(idx->mu);
+        st = register_copy(idx, device, dc);
+        ms[tables_slot] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    if(st != LRSC_OK) { free_device_copy(dc); delete idx; return st; }
+    if(std::getenv("LRSC_BWT_PROFILE")) std::fprintf(stderr, profile_fmt, ms[0], ms[1], ms[2], ms[3]);
+    return LRSC_OK;
+}
+
+// One strand of lrsc_index_build: BWT on the device -> packed image on the device (dc.*[s]) -> host image.  d_bwt is gone before
+// the next strand starts.
+static int build_strand(const char* reads, const uint64_t* off, uint32_t n_reads, int s, int device, bool wide, StrandImage& im,
+                        DeviceCopy& dc, double ms[2], std::string& err)
+{
+    const auto t0 = std::chrono::steady_clock::now();
+    uint8_t* d_bwt = nullptr;
+    const int st = build_bwt_resident(reads, off, n_reads, s, device, &d_bwt, nullptr, err);
+    if(st != LRSC_OK) return st;
+    ms[0] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return adopt_packed(d_bwt, off[n_reads] + n_reads, wide, s, dc, im, ms[1], err);
 }
 
 extern "C" int lrsc_index_build(const char* reads, const uint64_t* read_off, uint32_t n_reads, int device, lrsc_index** out)
@@ -319,23 +344,16 @@ extern "C" int lrsc_index_build(const char* reads, const uint64_t* read_off, uin
     if(!idx) return fail(LRSC_ERR_NOMEM, "lrsc_index");
     idx->num_strings = n_reads;
     idx->num_symbols = read_off[n_reads] + n_reads;
-    idx->wide = idx->num_symbols >= (1ull << 31) || std::getenv("LRSC_FORCE_WIDE") != nullptr;   // as index_from_units_impl
+    idx->wide = index_is_wide(idx->num_symbols);
     DeviceCopy dc;
-    double ms[3] = {0., 0., 0.};
+    double ms[4] = {0., 0., 0., 0.};
     std::string err;
     for(int s = 0; s < 2 && st == LRSC_OK; ++s) {
         st = build_strand(reads, read_off, n_reads, s, device, idx->wide, idx->image[s], dc, ms, err);
         if(st != LRSC_OK) st = fail(st, err);
     }
-    if(st == LRSC_OK) {
-        const auto t0 = std::chrono::steady_clock::now();
-        std::lock_guard<std::mutex> lock(idx->mu);
-        st = register_copy(idx, device, dc);
-        ms[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    if(st != LRSC_OK) { free_device_copy(dc); delete idx; return st; }
-    if(std::getenv("LRSC_BWT_PROFILE"))
-        std::fprintf(stderr, "[lrsc] index build: bwt %.3f ms, pack %.3f ms, tables %.3f ms\n", ms[0], ms[1], ms[2]);
+    st = finish_index(idx, device, dc, st, n_reads, LRSC_OK, nullptr, ms, 2, "[lrsc] index build: bwt %.3f ms, pack %.3f ms, tables %.3f ms\n");
+    if(st != LRSC_OK) return st;
     *out = idx;
     return LRSC_OK;
 }
@@ -344,7 +362,7 @@ extern "C" int lrsc_index_build(const char* reads, const uint64_t* read_off, uin
 // two resident indexes merged on the device (fm_merge.hip)
 // ---------------------------------------------------------------------------------------
 // One strand of lrsc_index_merge: walk + interleave -> BWT of the union on the device -> packed image on the device (dc.*[s]) ->
-// host image, as build_strand does after its sort.  rank[] goes once the origin is read from it, the BWT once it is packed.
+// host image (adopt_packed).  rank[] goes once the origin is read from it, the BWT once it is packed.
 // ms: walk, interleave, pack.
 static int merge_strand(const FmStrand& a, bool wide_a, const FmStrand& b, bool wide_b, int s, bool wide, uint8_t* origin, StrandImage& im,
                         DeviceCopy& dc, double ms[3], std::string& err)
@@ -356,17 +374,7 @@ static int merge_strand(const FmStrand& a, bool wide_a, const FmStrand& b, bool 
     if(origin) st = merge_origin_device(a, b, d_rank, origin, err);
     (void)hipFree(d_rank);
     if(st != LRSC_OK) { (void)hipFree(d_bwt); return st; }
-    const auto t0 = std::chrono::steady_clock::now();
-    const uint64_t N = a.n_symbols + b.n_symbols;
-    PackedStrand ps;
-    st = pack_strand_device(d_bwt, N, wide, ps, err);
-    (void)hipFree(d_bwt);
-    if(st != LRSC_OK) return st;
-    dc.blocks[s] = ps.blocks;
-    dc.dollars[s] = ps.dollars;
-    dc.dollar_dir[s] = ps.dollar_dir;
-    ms[2] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return image_from_device(ps, N, 0, im, err);
+    return adopt_packed(d_bwt, a.n_symbols + b.n_symbols, wide, s, dc, im, ms[2], err);
 }
 
 // the strands of idx's copy on `device`
@@ -396,7 +404,7 @@ extern "C" int lrsc_index_merge(lrsc_index* a, lrsc_index* b, int device, lrsc_i
     if(!idx) return fail(LRSC_ERR_NOMEM, "lrsc_index");
     idx->num_strings = n_reads;
     idx->num_symbols = a->num_symbols + b->num_symbols;
-    idx->wide = idx->num_symbols >= (1ull << 31) || std::getenv("LRSC_FORCE_WIDE") != nullptr;   // as index_from_units_impl
+    idx->wide = index_is_wide(idx->num_symbols);
     std::vector<uint8_t> origin(dollar_origin ? 2 * n_reads : 0);
     DeviceCopy dc;
     double ms[4] = {0., 0., 0., 0.};
@@ -405,17 +413,9 @@ extern "C" int lrsc_index_merge(lrsc_index* a, lrsc_index* b, int device, lrsc_i
         st = merge_strand(fa[s], wide_a, fb[s], wide_b, s, idx->wide, dollar_origin ? origin.data() + s * n_reads : nullptr, idx->image[s], dc, ms, err);
         if(st != LRSC_OK) st = fail(st, err);
     }
-    if(st == LRSC_OK && (idx->image[0].dollars.size() != n_reads || idx->image[1].dollars.size() != n_reads))
-        st = fail(LRSC_ERR_DEVICE, "index merge: the '$' rows of the result are not those of its inputs");
-    if(st == LRSC_OK) {
-        const auto t0 = std::chrono::steady_clock::now();
-        std::lock_guard<std::mutex> lock(idx->mu);
-        st = register_copy(idx, device, dc);
-        ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    if(st != LRSC_OK) { free_device_copy(dc); delete idx; return st; }
-    if(std::getenv("LRSC_BWT_PROFILE"))
-        std::fprintf(stderr, "[lrsc] index merge: walk %.3f ms, interleave %.3f ms, pack %.3f ms, tables %.3f ms\n", ms[0], ms[1], ms[2], ms[3]);
+    st = finish_index(idx, device, dc, st, n_reads, LRSC_ERR_DEVICE, "index merge: the '$' rows of the result are not those of its inputs", ms, 3,
+                      "[lrsc] index merge: walk %.3f ms, interleave %.3f ms, pack %.3f ms, tables %.3f ms\n");
+    if(st != LRSC_OK) return st;
     if(dollar_origin) std::memcpy(dollar_origin, origin.data(), origin.size());
     *out = idx;
     return LRSC_OK;
@@ -444,12 +444,9 @@ static int unrle_strand(const uint8_t* units, uint64_t n_units, uint64_t N, int 
     const int st = pack_units_device(d_units, n_units, N, wide, ps, nullptr, err);
     (void)hipFree(d_units);
     if(st != LRSC_OK) return st;
-    dc.blocks[s] = ps.blocks;
-    dc.dollars[s] = ps.dollars;
-    dc.dollar_dir[s] = ps.dollar_dir;
     ms[0] += std::chrono::duration<double, std::milli>(t1 - t0).count();
     ms[1] += std::chrono::duration<double, std::milli>(clk::now() - t1).count();
-    return image_from_device(ps, N, n_units, im, err);
+    return adopt_packed(ps, N, n_units, s, dc, im, err);
 }
 
 static int index_from_units_device_impl(const uint8_t* u0, uint64_t n0, const uint8_t* u1, uint64_t n1, uint64_t num_strings,
@@ -460,7 +457,7 @@ static int index_from_units_device_impl(const uint8_t* u0, uint64_t n0, const ui
     if(!idx) return fail(LRSC_ERR_NOMEM, "lrsc_index");
     idx->num_strings = num_strings;
     idx->num_symbols = num_symbols;
-    idx->wide = num_symbols >= (1ull << 31) || std::getenv("LRSC_FORCE_WIDE") != nullptr;   // as index_from_units_impl
+    idx->wide = index_is_wide(num_symbols);
     const uint8_t* us[2] = {u0, u1};
     const uint64_t ns[2] = {n0, n1};
     DeviceCopy dc;
@@ -473,18 +470,10 @@ static int index_from_units_device_impl(const uint8_t* u0, uint64_t n0, const ui
         if(st != LRSC_OK) st = fail(st, err);
         ms[2] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     }
-    if(st == LRSC_OK && (idx->image[0].dollars.size() != num_strings || idx->image[1].dollars.size() != num_strings))
-        st = fail(LRSC_ERR_FORMAT, "number of '$' rows differs from the number of strings in the header");
-    if(st == LRSC_OK) {
-        const auto t0 = std::chrono::steady_clock::now();
-        std::lock_guard<std::mutex> lock(idx->mu);
-        st = register_copy(idx, device, dc);
-        ms[3] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    if(st != LRSC_OK) { free_device_copy(dc); delete idx; return st; }
-    if(std::getenv("LRSC_BWT_PROFILE"))
-        std::fprintf(stderr, "[lrsc] index open on the device: units to the device %.3f ms, decode + pack %.3f ms, image to the host %.3f ms, tables %.3f ms\n",
-                     ms[0], ms[1], ms[2] - ms[0] - ms[1], ms[3]);
+    ms[2] -= ms[0] + ms[1];                                       // what the strands took beyond the copy and the pack
+    st = finish_index(idx, device, dc, st, num_strings, LRSC_ERR_FORMAT, "number of '$' rows differs from the number of strings in the header", ms, 3,
+                      "[lrsc] index open on the device: units to the device %.3f ms, decode + pack %.3f ms, image to the host %.3f ms, tables %.3f ms\n");
+    if(st != LRSC_OK) return st;
     *out = idx;
     return LRSC_OK;
 }

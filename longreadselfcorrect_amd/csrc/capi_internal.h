@@ -241,6 +241,19 @@ void free_device_copy(DeviceCopy& dc);
 int register_copy(lrsc_index* idx, int device, DeviceCopy& dc);
 // the host image of a strand that was packed on the device
 int image_from_device(const PackedStrand& ps, uint64_t N, uint64_t n_runs, StrandImage& im, std::string& err);
+// Block64 (64-bit counters, 128 symbols per block) from 2^31 symbols per strand; LRSC_FORCE_WIDE=1 selects it for any index so
+// that the wide code path can be tested on small data
+bool index_is_wide(uint64_t num_symbols);
+// One strand of an index that is made on the device: ps, packed there from N symbols (n_runs RL units, 0 when it never had any),
+// becomes strand s of dc, and im its host image, a copy of the packed arrays (a third of a byte per symbol).
+int adopt_packed(const PackedStrand& ps, uint64_t N, uint64_t n_runs, int s, DeviceCopy& dc, StrandImage& im, std::string& err);
+// The same from the byte-per-symbol BWT d_bwt, which is packed first and released either way; pack_ms += the pack.
+int adopt_packed(uint8_t* d_bwt, uint64_t N, bool wide, int s, DeviceCopy& dc, StrandImage& im, double& pack_ms, std::string& err);
+// How such an entry ends, st being what its strands left.  Both strands must hold n_dollars '$' rows, else bad_status with
+// bad_msg (nullptr: not checked).  Then dc becomes idx's copy on `device`, ms[tables_slot] = that, and with LRSC_BWT_PROFILE set
+// profile_fmt is printed with ms[0..3].  On any failure dc and idx are released.
+int finish_index(lrsc_index* idx, int device, DeviceCopy& dc, int st, uint64_t n_dollars, int bad_status, const char* bad_msg, double ms[4],
+                 int tables_slot, const char* profile_fmt);
 // the strands of idx's copy on `device` (LRSC_ERR_DEVICE without one)
 int resident_strands(lrsc_index* idx, int device, FmStrand fs[2], bool& wide);
 

@@ -30,7 +30,7 @@
 #pragma once
 #include <stdint.h>
 
-#include "fm_merge.h"
+#include "fm_strand.h"
 
 namespace lrsc {
 
@@ -76,17 +76,17 @@ LRSC_HD uint32_t dup_code(const uint32_t* words, uint64_t pos, DupReader& r)
 
 // Occ over the first `off` symbols of block g, held in b, plus the block's base count ('$' rows are stored as A and taken out)
 template <class Block>
-LRSC_HD uint64_t dup_occ(const MergeStrand<Block>& S, const Block& b, uint64_t g, uint32_t off, uint32_t code, const uint32_t* mtab)
+LRSC_HD uint64_t dup_occ(const StrandView<Block>& S, const Block& b, uint64_t g, uint32_t off, uint32_t code, const uint32_t* mtab)
 {
-    uint64_t c = block_base_count(b, code) + block_prefix_count(b, code, mtab + off * MergeLay<Block>::kRow);
+    uint64_t c = block_base_count(b, code) + block_prefix_count(b, code, mtab + off * BlockLay<Block>::kRow);
     if(code == 0 && off != 0 && has_dollar_flag(b)) {
         bool at = false;
-        c -= block_dollars_before(S, g, g * Block::kSyms, g * Block::kSyms + off, at);
+        uint64_t j = 0;
+        c -= dollars_before(S, g, g * Block::kSyms, g * Block::kSyms + off, at, j);
     }
     return c;
 }
-// D(pos): '$' rows of the strand before row pos <= N, from the directory entry of pos's group and the list entries of the group
-// before pos.  The '$' list of a strand without its rank blocks.
+// The '$' list of a strand without its rank blocks.
 struct DupDollars {
     const uint64_t* dollars;
     const uint32_t* dollar_dir;
@@ -94,20 +94,16 @@ struct DupDollars {
     uint32_t block_syms;
 };
 template <class Block>
-LRSC_HD DupDollars dup_dollars(const MergeStrand<Block>& S) { return DupDollars{S.dollars, S.dollar_dir, S.n_dollars, Block::kSyms}; }
-LRSC_HD uint64_t dup_dollar_rank(const DupDollars& d, uint64_t pos)
-{
-    uint64_t j = d.dollar_dir[(pos / d.block_syms) >> kDollarDirShift];
-    while(j < d.n_dollars && d.dollars[j] < pos) ++j;
-    return j;
-}
+LRSC_HD DupDollars dup_dollars(const StrandView<Block>& S) { return DupDollars{S.dollars, S.dollar_dir, S.n_dollars, Block::kSyms}; }
+// D(pos): '$' rows of the strand before row pos <= N
+LRSC_HD uint64_t dup_d(const DupDollars& d, uint64_t pos) { return dollar_rank(d.dollars, d.n_dollars, d.dollar_dir, pos / d.block_syms, pos); }
 
 // The chain of `kind` for the read at words[begin .. begin + len), len >= 1.  n_rank += the Occ queries, n_blk += the block loads.
 template <class Block>
-LRSC_HD DupChainOut dup_chain(const MergeStrand<Block>& S, const uint32_t* mtab, const uint32_t* words, uint64_t begin, uint32_t len, uint32_t kind,
+LRSC_HD DupChainOut dup_chain(const StrandView<Block>& S, const uint32_t* mtab, const uint32_t* words, uint64_t begin, uint32_t len, uint32_t kind,
                               uint32_t& n_rank, uint32_t& n_blk)
 {
-    using P = typename MergeLay<Block>::pos_t;
+    using P = typename BlockLay<Block>::pos_t;
     const bool forward = dup_kind_forward(kind);
     const uint32_t flip = dup_kind_flip(kind);
     DupChainOut out{0, 0, 0, kDupDead, 0};
@@ -115,12 +111,12 @@ LRSC_HD DupChainOut dup_chain(const MergeStrand<Block>& S, const uint32_t* mtab,
     P lo = 0, hi1 = 0;                                            // the interval's rows are [lo, hi1)
     for(uint32_t t = 0; t < len; ++t) {
         const uint32_t code = dup_code(words, forward ? begin + t : begin + (len - 1 - t), rd) ^ flip;
-        const P pred = merge_pred(S, code);
+        const P pred = strand_pred(S, code);
         if(t == 0) {
             lo = pred;
-            hi1 = code == 3u ? (P)S.N : merge_pred(S, code + 1);
+            hi1 = code == 3u ? (P)S.N : strand_pred(S, code + 1);
         } else {
-            const uint64_t gl = merge_block_of<Block>(lo), gu = merge_block_of<Block>(hi1);
+            const uint64_t gl = block_of<Block>(lo), gu = block_of<Block>(hi1);
             const Block bl = S.blocks[gl];
             const uint64_t ca = dup_occ(S, bl, gl, (uint32_t)(lo - (P)(gl * Block::kSyms)), code, mtab);
             uint64_t cb;
@@ -140,8 +136,8 @@ LRSC_HD DupChainOut dup_chain(const MergeStrand<Block>& S, const uint32_t* mtab,
     out.state = kDupLive;
     const DupDollars dd = dup_dollars(S);
     out.lo = (uint64_t)lo;
-    out.d_lo = dup_dollar_rank(dd, (uint64_t)lo);
-    out.d_hi1 = dup_dollar_rank(dd, (uint64_t)hi1);
+    out.d_lo = dup_d(dd, (uint64_t)lo);
+    out.d_hi1 = dup_d(dd, (uint64_t)hi1);
     out.extended = (uint64_t)(hi1 - lo) > out.d_hi1 - out.d_lo ? 1u : 0u;
     return out;
 }
@@ -153,7 +149,7 @@ LRSC_HD bool dup_equal_reads(const DupDollars& bwt, uint64_t n_rows, const DupCh
     if(in_bwt.state != kDupLive || in_rbwt.state != kDupLive) return false;
     const uint64_t at_end = in_rbwt.d_hi1 - in_rbwt.d_lo;         // E
     if(at_end == 0 || at_end > n_rows || in_bwt.lo > n_rows - at_end) return false;
-    const uint64_t d_end = dup_dollar_rank(bwt, in_bwt.lo + at_end);
+    const uint64_t d_end = dup_d(bwt, in_bwt.lo + at_end);
     if(d_end <= in_bwt.d_lo) return false;
     lower = (int64_t)in_bwt.d_lo;
     upper = (int64_t)d_end - 1;

@@ -12,11 +12,8 @@
 //   3. dup_classify_kernel      one lane per read: UNIQUE when the slot's bit is clear and the read won the slot, else FULL_LENGTH
 //   4. dup_commit_kernel        one lane per read: sets the slot's bit (32-bit atomic OR), winner[] back to kDupNoWinner
 // The outcome is that of the reads taken one after the other in input order, whatever the order the lanes run in.
-#include <hip/hip_runtime.h>
-
-#include "../../include/lrsc.h"
 #include "fm_dup.h"
-#include "kernels.h"
+#include "fm_launch.h"
 
 namespace lrsc {
 
@@ -25,26 +22,21 @@ static_assert(sizeof(DupResult) == sizeof(lrsc_dup_result) && offsetof(DupResult
 static_assert(kDupUnique == LRSC_DUP_UNIQUE && kDupSubstring == LRSC_DUP_SUBSTRING && kDupFullLength == LRSC_DUP_FULL_LENGTH &&
               kDupAbsent == LRSC_DUP_ABSENT, "the classes are lrsc_dup_class");
 
-template <bool WIDE> struct DupBlock { using type = Block32; };
-template <> struct DupBlock<true> { using type = Block64; };
-
 template <bool WIDE>
 __global__ __launch_bounds__(kDupThreads) __attribute__((amdgpu_waves_per_eu(kDupWavesPerSimd, kDupWavesPerSimd)))
-void dup_chain_kernel(MergeStrand<typename DupBlock<WIDE>::type> S0, MergeStrand<typename DupBlock<WIDE>::type> S1, const uint32_t* __restrict__ words,
+void dup_chain_kernel(StrandView<typename BlockOf<WIDE>::type> S0, StrandView<typename BlockOf<WIDE>::type> S1, const uint32_t* __restrict__ words,
                       const uint64_t* __restrict__ read_off, uint32_t n, uint32_t groups_per_kind, DupChainOut* __restrict__ chains, DevCounters* ctr)
 {
-    using B = typename DupBlock<WIDE>::type;
-    __shared__ __attribute__((aligned(16))) uint32_t mtab[MergeMaskTab<B>::kWords];
-    for(uint32_t i = threadIdx.x; i < MergeMaskTab<B>::kWords; i += blockDim.x) mtab[i] = merge_mask_word<B>(i);
+    using B = typename BlockOf<WIDE>::type;
+    __shared__ __attribute__((aligned(16))) uint32_t mtab[MaskTab<B>::kWords];
+    // The table's fill and the wavefront sums below are written in place, not with fm_launch.h's fill_mask_table and wave_sum:
+    // with the helpers the kernel came to 930 (Block64) and 939 (Block32) instructions against 935 and 938, at the same 61 and 52
+    // VGPRs, and measured 0.4 to 1.1 % slower.
+    for(uint32_t i = threadIdx.x; i < MaskTab<B>::kWords; i += blockDim.x) mtab[i] = mask_word<B>(i);
     __syncthreads();
     const uint32_t kind = blockIdx.x / groups_per_kind;           // uniform in the workgroup
     const uint64_t read = (uint64_t)(blockIdx.x - kind * groups_per_kind) * kDupThreads + threadIdx.x;
-    // the kind's strand, member by member: a by-value argument picked by a run-time index would be copied to scratch
-    const bool rev = dup_kind_strand(kind) != 0;
-    MergeStrand<B> S;
-    S.blocks = rev ? S1.blocks : S0.blocks; S.dollars = rev ? S1.dollars : S0.dollars; S.dollar_dir = rev ? S1.dollar_dir : S0.dollar_dir;
-    S.n_dollars = rev ? S1.n_dollars : S0.n_dollars; S.n_blocks = rev ? S1.n_blocks : S0.n_blocks; S.N = rev ? S1.N : S0.N;
-    S.c1 = rev ? S1.c1 : S0.c1; S.c2 = rev ? S1.c2 : S0.c2; S.c3 = rev ? S1.c3 : S0.c3; S.c4 = rev ? S1.c4 : S0.c4;
+    const StrandView<B> S = select_view(dup_kind_strand(kind) != 0, S0, S1);       // the kind's strand
     uint32_t n_rank = 0, n_blk = 0;
     if(read < n) {
         const uint64_t begin = read_off[read];
@@ -58,11 +50,7 @@ void dup_chain_kernel(MergeStrand<typename DupBlock<WIDE>::type> S0, MergeStrand
         a += __shfl_down(a, o, 64);
         b += __shfl_down(b, o, 64);
     }
-    if(ctr != nullptr && (threadIdx.x & 63) == 0 && a) {
-        DevCounters* shard = ctr + (blockIdx.x & (kCtrShards - 1));
-        atomicAdd(&shard->rank_queries, a);
-        atomicAdd(&shard->block_loads, b);
-    }
+    wave_count(ctr, a, b);
 }
 
 __global__ __launch_bounds__(256) void dup_combine_kernel(DupDollars bwt, uint64_t n_rows, const DupChainOut* __restrict__ chains, uint32_t n, uint64_t n_slots,
@@ -106,11 +94,11 @@ hipError_t launch_dup_chains(const FmIndexDev& fm, const uint32_t* words, const 
     const uint64_t gpk = ((uint64_t)n + kDupThreads - 1) / kDupThreads;
     if(n == 0 || gpk * kDupKinds >= (1ull << 31)) return hipErrorInvalidValue;
     if(fm.wide)
-        hipLaunchKernelGGL((dup_chain_kernel<true>), dim3((unsigned)(gpk * kDupKinds)), dim3(kDupThreads), 0, stream, merge_strand<Block64>(fm.strand[0]),
-                           merge_strand<Block64>(fm.strand[1]), words, read_off, n, (uint32_t)gpk, chains, ctr);
+        hipLaunchKernelGGL((dup_chain_kernel<true>), dim3((unsigned)(gpk * kDupKinds)), dim3(kDupThreads), 0, stream, strand_view<Block64>(fm.strand[0]),
+                           strand_view<Block64>(fm.strand[1]), words, read_off, n, (uint32_t)gpk, chains, ctr);
     else
-        hipLaunchKernelGGL((dup_chain_kernel<false>), dim3((unsigned)(gpk * kDupKinds)), dim3(kDupThreads), 0, stream, merge_strand<Block32>(fm.strand[0]),
-                           merge_strand<Block32>(fm.strand[1]), words, read_off, n, (uint32_t)gpk, chains, ctr);
+        hipLaunchKernelGGL((dup_chain_kernel<false>), dim3((unsigned)(gpk * kDupKinds)), dim3(kDupThreads), 0, stream, strand_view<Block32>(fm.strand[0]),
+                           strand_view<Block32>(fm.strand[1]), words, read_off, n, (uint32_t)gpk, chains, ctr);
     return hipGetLastError();
 }
 

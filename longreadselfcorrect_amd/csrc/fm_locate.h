@@ -4,7 +4,7 @@
 // A strand of an index is the BWT of a string set whose sentinels sort in input order: row i < n is the suffix that is read
 // i's sentinel alone.  One LF step, i <- C[c] + Occ(c, i) with c = BWT[i], leads from the suffix of a read at position p to
 // the one at p - 1, and the row whose symbol is '$' is the whole read.  Both c and Occ(c, i) come from the one rank block of
-// row i (locate_lf_step, the step of fm_merge.h's walk on B's side).
+// row i (fm_strand.h's lf_step).
 //
 //   prepare  One lane per read i walks it backwards from row i, counting its steps t.  Every visited row r that is a multiple
 //            of the sample rate gets samples[r / rate] = (i, t).  At the '$' row, whose rank among the '$' rows is k (the
@@ -16,7 +16,7 @@
 //            the answer is (sample.read, sample.pos + offset), on a '$' row (order[k], offset).  The sample is looked at before
 //            the symbol, as in the reference.
 //
-// Every walk ends on any input: after num_symbols steps, or when a position leaves the index, the lane reports kLocateBroken
+// Every walk ends on any input: after num_symbols steps, or when a position leaves the index, the lane reports kWalkBroken
 // and the call fails.  All functions here are LRSC_HD and free of HIP types: the kernels call them, and
 // tests/host_tools/locate_driver.cpp compiles the same source for the CPU and holds it against a suffix sort.
 #pragma once
@@ -24,7 +24,7 @@
 
 #include <string>
 
-#include "fm_merge.h"
+#include "fm_strand.h"
 
 namespace lrsc {
 
@@ -36,9 +36,6 @@ constexpr uint32_t kLocateUnset = 0xFFFFFFFFu;                    // an entry no
 
 struct SaElem { uint32_t read, pos; };                            // lrsc_sa_elem: SA[row] = the suffix of `read` that starts at `pos`
 
-// What a lane reports: 0, or why its walk was cut short.  An index made by this library never gives the latter.
-enum : uint32_t { kLocateOk = 0, kLocateBroken = 1 };
-
 // the locate tables of one strand, on the device
 struct LocateTables {
     SaElem* samples = nullptr;                                    // n_samples entries: SA of the rows that are multiples of rate
@@ -49,65 +46,20 @@ struct LocateTables {
 };
 LRSC_HD uint64_t locate_sample_count(uint64_t n_symbols, uint32_t rate) { return rate ? n_symbols / rate + 1 : 0; }
 
-// '$' rows of the list before position pos that lie in block g (which starts at symbol base), as block_dollars_before; j is
-// the number of '$' rows of the whole strand before pos, the rank of pos among them when it is one itself (at_pos)
-template <class Block>
-LRSC_HD uint32_t locate_dollars_before(const MergeStrand<Block>& s, uint64_t g, uint64_t base, uint64_t pos, bool& at_pos, uint64_t& j)
-{
-    j = s.dollar_dir[g >> kDollarDirShift];
-    uint32_t n = 0;
-    uint64_t d = ~0ull;
-    for(; j < s.n_dollars; ++j) {
-        d = s.dollars[j];
-        if(d >= pos) break;
-        n += d >= base ? 1u : 0u;
-    }
-    at_pos = j < s.n_dollars && d == pos;
-    return n;
-}
-
-// One LF step from row i < S.N, b being its block i / kSyms.  Returns false, i unchanged, when BWT[i] is '$': k is then the
-// rank of the row among the strand's '$' rows.
-template <class Block>
-LRSC_HD bool locate_lf_step(const MergeStrand<Block>& S, const Block& b, const uint32_t* mtab, typename MergeLay<Block>::pos_t& i, uint64_t& k)
-{
-    using P = typename MergeLay<Block>::pos_t;
-    const P g = i / Block::kSyms;
-    const uint32_t o = (uint32_t)(i - g * Block::kSyms);
-    const uint32_t code = block_symbol(b, o);
-    uint64_t c = block_base_count(b, code) + block_prefix_count(b, code, mtab + o * MergeLay<Block>::kRow);
-    if(code == 0 && has_dollar_flag(b)) {                         // '$' is stored as A: only flagged blocks pay for the list
-        bool at = false;
-        const uint32_t n = locate_dollars_before(S, (uint64_t)g, (uint64_t)g * Block::kSyms, (uint64_t)i, at, k);
-        if(at) return false;
-        c -= n;
-    }
-    i = merge_pred(S, code) + (P)c;
-    return true;
-}
-
 // ---- prepare: the walk of one read ----
-// Returns kLocateOk after writing the read's samples, order[] entry and length.  n_reads = S.n_dollars.
+// Returns kWalkOk after writing the read's samples, order[] entry and length.  n_reads = S.n_dollars.
 template <class Block>
-LRSC_HD uint32_t locate_prepare_read(const MergeStrand<Block>& S, const uint32_t* mtab, uint32_t read, uint32_t rate, SaElem* samples,
+LRSC_HD uint32_t locate_prepare_read(const StrandView<Block>& S, const uint32_t* mtab, uint32_t read, uint32_t rate, SaElem* samples,
                                      uint32_t* order, uint32_t* read_len)
 {
-    using P = typename MergeLay<Block>::pos_t;
-    P i = (P)read;
-    // a read has fewer symbols than the strand has rows and never leaves it: the bound and the range check only end the walk
-    // through an index that is no BWT of a string set
-    for(uint64_t t = 0; t < S.N; ++t) {
-        if(i >= S.N) return kLocateBroken;
-        if(rate != 0 && i % rate == 0) samples[i / rate] = SaElem{read, (uint32_t)t};
-        const Block b = S.blocks[merge_block_of<Block>(i)];
-        uint64_t k = 0;
-        if(!locate_lf_step(S, b, mtab, i, k)) {
-            order[k] = read;                                      // k < n_dollars: locate_dollars_before found the row in the list
-            read_len[read] = (uint32_t)t;
-            return kLocateOk;
-        }
-    }
-    return kLocateBroken;
+    uint64_t k = 0, t = 0;
+    const uint32_t st = walk_read_back(S, mtab, read, [&](typename BlockLay<Block>::pos_t i, uint64_t steps) {
+        if(rate != 0 && i % rate == 0) samples[i / rate] = SaElem{read, (uint32_t)steps};
+    }, k, t);
+    if(st != kWalkOk) return st;
+    order[k] = read;
+    read_len[read] = (uint32_t)t;
+    return kWalkOk;
 }
 
 // ---- fix-up: steps from the sentinel row -> position in the read ----
@@ -115,40 +67,40 @@ LRSC_HD uint32_t locate_prepare_read(const MergeStrand<Block>& S, const uint32_t
 // exist, and stays unset (the reference's empty SAElem)
 LRSC_HD uint32_t locate_fix_sample(SaElem& s, uint64_t slot, uint32_t rate, uint64_t n_symbols, const uint32_t* read_len, uint64_t n_reads)
 {
-    if(slot * rate >= n_symbols) return kLocateOk;
-    if(s.read == kLocateUnset || s.read >= n_reads) return kLocateBroken;     // a row that no walk came through
+    if(slot * rate >= n_symbols) return kWalkOk;
+    if(s.read == kLocateUnset || s.read >= n_reads) return kWalkBroken;     // a row that no walk came through
     const uint32_t len = read_len[s.read];
-    if(s.pos > len) return kLocateBroken;
+    if(s.pos > len) return kWalkBroken;
     s.pos = len - s.pos;
-    return kLocateOk;
+    return kWalkOk;
 }
 
 // ---- locate: calcSA of one row ----
 // steps += the LF steps taken
 template <class Block>
-LRSC_HD uint32_t locate_row(const MergeStrand<Block>& S, const uint32_t* mtab, uint64_t row, uint32_t rate, const SaElem* samples,
+LRSC_HD uint32_t locate_row(const StrandView<Block>& S, const uint32_t* mtab, uint64_t row, uint32_t rate, const SaElem* samples,
                             const uint32_t* order, SaElem& out, uint32_t& steps)
 {
-    using P = typename MergeLay<Block>::pos_t;
+    using P = typename BlockLay<Block>::pos_t;
     out = SaElem{kLocateUnset, kLocateUnset};
-    if(row >= S.N) return kLocateBroken;
+    if(row >= S.N) return kWalkBroken;
     P i = (P)row;
     for(uint64_t offset = 0; offset < S.N; ++offset) {
-        if(i >= S.N) return kLocateBroken;
+        if(i >= S.N) return kWalkBroken;
         if(rate != 0 && i % rate == 0) {
             const SaElem s = samples[i / rate];
             out = SaElem{s.read, s.pos + (uint32_t)offset};
-            return kLocateOk;
+            return kWalkOk;
         }
-        const Block b = S.blocks[merge_block_of<Block>(i)];
+        const Block b = S.blocks[block_of<Block>(i)];
         uint64_t k = 0;
-        if(!locate_lf_step(S, b, mtab, i, k)) {
+        if(!lf_step(S, b, mtab, i, k)) {
             out = SaElem{order[k], (uint32_t)offset};
-            return kLocateOk;
+            return kWalkOk;
         }
         ++steps;
     }
-    return kLocateBroken;
+    return kWalkBroken;
 }
 
 // ---- the device side (fm_locate.hip) ----

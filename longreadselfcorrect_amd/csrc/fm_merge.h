@@ -10,11 +10,11 @@
 //               c = BWT_B[i] is no '$' steps i <- C_B[c] + Occ_B(c, i), r <- C_A[c] + Occ_A(c, r).  Every row visited, the first
 //               and the one that holds the '$' included, gets rank[i] = r.  The walks of all reads visit every row of B once.
 //               BWT_B[i] and Occ_B(c, i) come from one rank block of B and Occ_A(c, r) from one of A, whichever c is: the caller
-//               loads both before merge_walk_step looks at either.
+//               loads both before merge_walk_step looks at either.  B's side of the step is fm_strand.h's lf_step.
 //   interleave  rank[] is non-decreasing in the row, so B row j lands at merged position j + rank[j], strictly increasing, and
 //               A's rows fill the gaps in order.  A tile of merged positions [p0, p1) finds its first B row by a binary search
 //               of p0 in j + rank[j] (merge_tile_search): rows [j0, j1) of B and [p0 - j0, p1 - j1) of A make the tile.  Both
-//               are decoded from their rank blocks with unpack_block, and every lane fills 16 consecutive positions
+//               are decoded from their rank blocks with decode_block, and every lane fills 16 consecutive positions
 //               (merge_fill16) from the two decoded stretches and the tile's list of B positions.
 //   origin      B's k-th '$' row, row d of B, is preceded in the union by B's k earlier ones and by the '$' rows of A that lie
 //               among A's first rank[d] rows (merge_origin_slot).
@@ -26,9 +26,7 @@
 
 #include <string>
 
-#include "fm_device.h"
-#include "fm_pack.h"
-#include "fm_rle.h"
+#include "fm_strand.h"
 
 namespace lrsc {
 
@@ -40,137 +38,46 @@ constexpr uint32_t kMergeLanes = 256;                             // threads per
 constexpr uint32_t kMergeTile = kMergeLanes * 16;                 // merged positions per tile
 static_assert(kMergeTile <= 65536, "a tile's B positions are kept as 16-bit offsets");
 
-// position type and mask-table row of a layout (rank_device.h's Lay<WIDE>, without HIP types)
-template <class Block> struct MergeLay;
-template <> struct MergeLay<Block32> { using pos_t = uint32_t; static constexpr uint32_t kRow = 8; };
-template <> struct MergeLay<Block64> { using pos_t = uint64_t; static constexpr uint32_t kRow = 4; };
-// Row `off` of the table holds the kWords partial-word masks of "the first off symbols of a block".
-template <class Block> struct MergeMaskTab { static constexpr uint32_t kWords = (Block::kSyms + 1) * MergeLay<Block>::kRow; };
-template <class Block>
-LRSC_HD uint32_t merge_mask_word(uint32_t i)
-{
-    const uint32_t off = i / MergeLay<Block>::kRow, w = i % MergeLay<Block>::kRow;
-    return w < Block::kWords ? low_mask((int32_t)off - 32 * (int32_t)w) : 0u;
-}
-
-// One strand as the merge reads it.  C[] as four scalars: indexing a by-value kernel argument dynamically would put it in scratch.
-template <class Block>
-struct MergeStrand {
-    using pos_t = typename MergeLay<Block>::pos_t;
-    const Block* blocks;
-    const uint64_t* dollars;
-    const uint32_t* dollar_dir;
-    uint64_t n_dollars, n_blocks, N;
-    pos_t c1, c2, c3, c4;                                         // C[A], C[C], C[G], C[T]
-};
-template <class Block>
-LRSC_HD MergeStrand<Block> merge_strand(const FmStrand& s)
-{
-    using P = typename MergeLay<Block>::pos_t;
-    MergeStrand<Block> m;
-    m.blocks = static_cast<const Block*>(s.blocks); m.dollars = s.dollars; m.dollar_dir = s.dollar_dir;
-    m.n_dollars = s.n_dollars; m.n_blocks = s.n_blocks; m.N = s.n_symbols;
-    m.c1 = (P)s.pred[1]; m.c2 = (P)s.pred[2]; m.c3 = (P)s.pred[3]; m.c4 = (P)s.pred[4];
-    return m;
-}
-template <class Block>
-LRSC_HD typename MergeLay<Block>::pos_t merge_pred(const MergeStrand<Block>& s, uint32_t code)
-{
-    typename MergeLay<Block>::pos_t v = s.c1;
-    v += code >= 1 ? (s.c2 - s.c1) : 0;
-    v += code >= 2 ? (s.c3 - s.c2) : 0;
-    v += code >= 3 ? (s.c4 - s.c3) : 0;
-    return v;
-}
-
-// ---- one rank block, held in registers: every index into it is a constant after unrolling ----
-LRSC_HD uint64_t merge_pick4(uint32_t code, uint64_t a, uint64_t b, uint64_t c, uint64_t d)
-{
-    return (code & 2u) ? ((code & 1u) ? d : c) : ((code & 1u) ? b : a);       // by the code's bits, never an equality chain (rank_device.h)
-}
-LRSC_HD uint64_t block_base_count(const Block32& b, uint32_t code) { return merge_pick4(code, b.cnt[0] & ~kFlag32, b.cnt[1], b.cnt[2], b.cnt[3]); }
-LRSC_HD uint64_t block_base_count(const Block64& b, uint32_t code) { return merge_pick4(code, b.cnt[0] & ~kFlag64, b.cnt[1], b.cnt[2], b.cnt[3]); }
-
-// code (A=0 .. T=3, '$' reads as A) of symbol `off` of the block
-template <class Block>
-LRSC_HD uint32_t block_symbol(const Block& b, uint32_t off)
-{
-    uint32_t l = 0, h = 0;
-    LRSC_UNROLL
-    for(uint32_t wi = 0; wi < Block::kWords; ++wi) {
-        l = (off >> 5) == wi ? plane_lo(b, wi) : l;
-        h = (off >> 5) == wi ? plane_hi(b, wi) : h;
-    }
-    return ((l >> (off & 31u)) & 1u) | (((h >> (off & 31u)) & 1u) << 1);
-}
-// symbols with that code among the first symbols of the block, mrow being their row of the mask table ('$' rows count as A)
-template <class Block>
-LRSC_HD uint32_t block_prefix_count(const Block& b, uint32_t code, const uint32_t* mrow)
-{
-    const uint32_t L = (code & 1u) ? 0u : 0xFFFFFFFFu;
-    const uint32_t H = (code & 2u) ? 0u : 0xFFFFFFFFu;
-    uint32_t c = 0;
-    LRSC_UNROLL
-    for(uint32_t wi = 0; wi < Block::kWords; ++wi) c += (uint32_t)__builtin_popcount((plane_lo(b, wi) ^ L) & (plane_hi(b, wi) ^ H) & mrow[wi]);
-    return c;
-}
-// '$' rows of block g (which starts at symbol base) before position pos, and whether pos itself is one: the directory entry of
-// the block's group, then the few list entries of the group
-template <class Block>
-LRSC_HD uint32_t block_dollars_before(const MergeStrand<Block>& s, uint64_t g, uint64_t base, uint64_t pos, bool& at_pos)
-{
-    uint64_t j = s.dollar_dir[g >> kDollarDirShift];
-    uint32_t n = 0;
-    uint64_t d = ~0ull;
-    for(; j < s.n_dollars; ++j) {
-        d = s.dollars[j];
-        if(d >= pos) break;
-        n += d >= base ? 1u : 0u;
-    }
-    at_pos = j < s.n_dollars && d == pos;
-    return n;
-}
-
 // ---- the walk ----
 template <class BlockA, class BlockB>
 struct MergeWalk {
-    typename MergeLay<BlockB>::pos_t i;                           // row of B
-    typename MergeLay<BlockA>::pos_t r;                           // suffixes of A smaller than that row's
+    typename BlockLay<BlockB>::pos_t i;                           // row of B
+    typename BlockLay<BlockA>::pos_t r;                           // suffixes of A smaller than that row's
 };
 template <class BlockA, class BlockB>
 LRSC_HD MergeWalk<BlockA, BlockB> merge_walk_start(uint64_t read_of_b, uint64_t n_reads_a)
 {
     MergeWalk<BlockA, BlockB> w;
-    w.i = (typename MergeLay<BlockB>::pos_t)read_of_b;
-    w.r = (typename MergeLay<BlockA>::pos_t)n_reads_a;
+    w.i = (typename BlockLay<BlockB>::pos_t)read_of_b;
+    w.r = (typename BlockLay<BlockA>::pos_t)n_reads_a;
     return w;
 }
-template <class Block> LRSC_HD uint64_t merge_block_of(typename MergeLay<Block>::pos_t p) { return (uint64_t)(p / Block::kSyms); }
 
-// One step.  bb is B's block merge_block_of(w.i), ba is A's block merge_block_of(w.r).  Returns false, w unchanged, when
-// BWT_B[w.i] is '$': the read is done.
+// One step.  bb is B's block block_of(w.i), ba is A's block block_of(w.r).  Returns false, w unchanged, when BWT_B[w.i] is
+// '$': the read is done.
 template <class BlockA, class BlockB>
-LRSC_HD bool merge_walk_step(const MergeStrand<BlockA>& A, const MergeStrand<BlockB>& B, const BlockA& ba, const BlockB& bb,
+LRSC_HD bool merge_walk_step(const StrandView<BlockA>& A, const StrandView<BlockB>& B, const BlockA& ba, const BlockB& bb,
                              const uint32_t* mtab_a, const uint32_t* mtab_b, MergeWalk<BlockA, BlockB>& w)
 {
-    using PA = typename MergeLay<BlockA>::pos_t;
-    using PB = typename MergeLay<BlockB>::pos_t;
+    using PA = typename BlockLay<BlockA>::pos_t;
+    using PB = typename BlockLay<BlockB>::pos_t;
     const PB gb = w.i / BlockB::kSyms;
     const PA ga = w.r / BlockA::kSyms;
     const uint32_t ob = (uint32_t)(w.i - gb * BlockB::kSyms), oa = (uint32_t)(w.r - ga * BlockA::kSyms);
     const uint32_t code = block_symbol(bb, ob);
-    uint64_t cb = block_base_count(bb, code) + block_prefix_count(bb, code, mtab_b + ob * MergeLay<BlockB>::kRow);
-    uint64_t ca = block_base_count(ba, code) + block_prefix_count(ba, code, mtab_a + oa * MergeLay<BlockA>::kRow);
+    uint64_t cb = block_base_count(bb, code) + block_prefix_count(bb, code, mtab_b + ob * BlockLay<BlockB>::kRow);
+    uint64_t ca = block_base_count(ba, code) + block_prefix_count(ba, code, mtab_a + oa * BlockLay<BlockA>::kRow);
     if(code == 0) {                                               // '$' is stored as A: only flagged blocks pay for the list
         bool at = false;
+        uint64_t j = 0;                                           // the rows' ranks among the '$' rows: not needed here
         if(has_dollar_flag(bb)) {
-            cb -= block_dollars_before(B, (uint64_t)gb, (uint64_t)gb * BlockB::kSyms, (uint64_t)w.i, at);
+            cb -= dollars_before(B, (uint64_t)gb, (uint64_t)gb * BlockB::kSyms, (uint64_t)w.i, at, j);
             if(at) return false;
         }
-        if(oa != 0 && has_dollar_flag(ba)) ca -= block_dollars_before(A, (uint64_t)ga, (uint64_t)ga * BlockA::kSyms, (uint64_t)w.r, at);
+        if(oa != 0 && has_dollar_flag(ba)) ca -= dollars_before(A, (uint64_t)ga, (uint64_t)ga * BlockA::kSyms, (uint64_t)w.r, at, j);
     }
-    w.i = merge_pred(B, code) + (PB)cb;
-    w.r = merge_pred(A, code) + (PA)ca;
+    w.i = strand_pred(B, code) + (PB)cb;
+    w.r = strand_pred(A, code) + (PA)ca;
     return true;
 }
 
@@ -208,18 +115,6 @@ LRSC_HD MergeSpan merge_span(uint64_t row0, uint64_t row1)
     s.n_blocks = row1 > row0 ? (uint32_t)((row1 - 1) / Block::kSyms - s.first_block + 1) : 0u;
     return s;
 }
-// block first_block + u of a span -> its codes ($ACGT = 0..4) at out[u * kSyms/16 ...]
-template <class Block>
-LRSC_HD void merge_decode_block(const MergeStrand<Block>& s, uint64_t g, Sym16* out)
-{
-    const Block b = s.blocks[g];
-    const uint64_t base = g * Block::kSyms;
-    const uint64_t left = s.N - base;                             // n_blocks = N / kSyms + 1: base <= N
-    uint64_t j = s.n_dollars;
-    if(has_dollar_flag(b)) j = first_dollar_of_block(s.dollars, s.n_dollars, s.dollar_dir, g, base);
-    unpack_block<Block>(b, base, s.dollars + j, s.n_dollars - j, (uint32_t)(left < Block::kSyms ? left : Block::kSyms), out);
-}
-
 // Merged positions [q, q + 16) of a tile, of which those below n_valid exist (the others read 0).  pos_b[0 .. n_bt) are the
 // tile's B rows as positions in the tile, ascending; sym_a / sym_b the decoded stretches, the tile's first row at skip_a / skip_b.
 LRSC_HD Sym16 merge_fill16(const uint16_t* pos_b, uint32_t n_bt, const Sym16* sym_a, uint32_t skip_a, const Sym16* sym_b, uint32_t skip_b,
@@ -237,7 +132,7 @@ LRSC_HD Sym16 merge_fill16(const uint16_t* pos_b, uint32_t n_bt, const Sym16* sy
         const uint32_t p = q + t;
         if(p < n_valid) {
             const bool from_b = k < n_bt && pos_b[k] == p;
-            const uint32_t c = from_b ? rle_sym(sym_b, skip_b + k) : rle_sym(sym_a, skip_a + p - k);
+            const uint32_t c = from_b ? sym_at(sym_b, skip_b + k) : sym_at(sym_a, skip_a + p - k);
             k += from_b ? 1u : 0u;
             v.w[t >> 2] |= c << (8 * (t & 3));
         }

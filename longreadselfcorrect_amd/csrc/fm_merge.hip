@@ -12,36 +12,23 @@
 //                                          decoding one block; then every lane fills 16 positions and stores them with one
 //                                          16-byte access.  No atomics anywhere.
 //   4. merge_origin_kernel                 one lane per '$' row of B: where it falls among the union's
-#include <hip/hip_runtime.h>
-
-#include <algorithm>
 #include <chrono>
-#include <vector>
 
-#include "../../include/lrsc.h"
+#include "fm_launch.h"
 #include "fm_merge.h"
 
 namespace lrsc {
 
-template <bool WIDE> struct BlockOf { using type = Block32; };
-template <> struct BlockOf<true> { using type = Block64; };
-
-template <class Block>
-__device__ __forceinline__ void fill_mask_table(uint32_t* tab)
-{
-    for(uint32_t i = threadIdx.x; i < MergeMaskTab<Block>::kWords; i += blockDim.x) tab[i] = merge_mask_word<Block>(i);
-}
-
 template <bool WIDE_A, bool WIDE_B>
 __global__ __launch_bounds__(kMergeWalkThreads) __attribute__((amdgpu_waves_per_eu(kMergeWalkWavesPerSimd, kMergeWalkWavesPerSimd)))
-void merge_rank_kernel(MergeStrand<typename BlockOf<WIDE_A>::type> A, MergeStrand<typename BlockOf<WIDE_B>::type> B, uint64_t n_reads_a,
+void merge_rank_kernel(StrandView<typename BlockOf<WIDE_A>::type> A, StrandView<typename BlockOf<WIDE_B>::type> B, uint64_t n_reads_a,
                        uint64_t n_reads_b, uint64_t* __restrict__ rank)
 {
     using BA = typename BlockOf<WIDE_A>::type;
     using BB = typename BlockOf<WIDE_B>::type;
     // one table serves both inputs when their layouts agree
-    __shared__ __attribute__((aligned(16))) uint32_t mtab_b[MergeMaskTab<BB>::kWords];
-    __shared__ __attribute__((aligned(16))) uint32_t mtab_other[WIDE_A == WIDE_B ? 1 : MergeMaskTab<BA>::kWords];
+    __shared__ __attribute__((aligned(16))) uint32_t mtab_b[MaskTab<BB>::kWords];
+    __shared__ __attribute__((aligned(16))) uint32_t mtab_other[WIDE_A == WIDE_B ? 1 : MaskTab<BA>::kWords];
     fill_mask_table<BB>(mtab_b);
     if(WIDE_A != WIDE_B) fill_mask_table<BA>(mtab_other);
     __syncthreads();
@@ -54,8 +41,8 @@ void merge_rank_kernel(MergeStrand<typename BlockOf<WIDE_A>::type> A, MergeStran
     for(uint64_t step = 0; step < B.N; ++step) {
         if(w.i >= B.N || w.r > A.N) break;
         rank[w.i] = w.r;
-        const BB bb = B.blocks[merge_block_of<BB>(w.i)];
-        const BA ba = A.blocks[merge_block_of<BA>(w.r)];
+        const BB bb = B.blocks[block_of<BB>(w.i)];
+        const BA ba = A.blocks[block_of<BA>(w.r)];
         if(!merge_walk_step(A, B, ba, bb, mtab_a, mtab_b, w)) break;
     }
 }
@@ -70,8 +57,8 @@ __global__ __launch_bounds__(256) void merge_tile_kernel(const uint64_t* __restr
 }
 
 template <bool WIDE_A, bool WIDE_B>
-__global__ __launch_bounds__(kMergeLanes) void merge_interleave_kernel(MergeStrand<typename BlockOf<WIDE_A>::type> A,
-                                                                       MergeStrand<typename BlockOf<WIDE_B>::type> B,
+__global__ __launch_bounds__(kMergeLanes) void merge_interleave_kernel(StrandView<typename BlockOf<WIDE_A>::type> A,
+                                                                       StrandView<typename BlockOf<WIDE_B>::type> B,
                                                                        const uint64_t* __restrict__ rank, const uint64_t* __restrict__ tile_row,
                                                                        uint8_t* __restrict__ out)
 {
@@ -92,8 +79,8 @@ __global__ __launch_bounds__(kMergeLanes) void merge_interleave_kernel(MergeStra
     const MergeSpan span_b = merge_span<BB>(j0, j1);
     for(uint32_t k = threadIdx.x; k < n_bt; k += kMergeLanes) pos_b[k] = (uint16_t)(j0 + k + rank[j0 + k] - p0);
     for(uint32_t u = threadIdx.x; u < span_a.n_blocks + span_b.n_blocks; u += kMergeLanes) {
-        if(u < span_a.n_blocks) merge_decode_block<BA>(A, span_a.first_block + u, sym_a + u * SA::kChunks);
-        else merge_decode_block<BB>(B, span_b.first_block + (u - span_a.n_blocks), sym_b + (u - span_a.n_blocks) * SB::kChunks);
+        if(u < span_a.n_blocks) decode_block<BA>(A, span_a.first_block + u, sym_a + u * SA::kChunks);
+        else decode_block<BB>(B, span_b.first_block + (u - span_a.n_blocks), sym_b + (u - span_a.n_blocks) * SB::kChunks);
     }
     __syncthreads();
     const uint32_t q = threadIdx.x * 16;
@@ -111,26 +98,7 @@ __global__ __launch_bounds__(256) void merge_origin_kernel(const uint64_t* __res
     if(d < rows_b) origin[merge_origin_slot(dollars_a, n_a, rank[d], k)] = 1;
 }
 
-namespace {
-struct Owned {
-    std::vector<void*> ptrs;
-    ~Owned() { for(void* p : ptrs) (void)hipFree(p); }
-    template <class T> hipError_t alloc(T** p, size_t n)
-    {
-        void* q = nullptr;
-        hipError_t e = hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T));
-        if(e == hipSuccess) { ptrs.push_back(q); *p = static_cast<T*>(q); }
-        return e;
-    }
-    void keep(void* p) { ptrs.erase(std::remove(ptrs.begin(), ptrs.end(), p), ptrs.end()); }
-};
-}
-
-#define MG_TRY(expr)                                                                 \
-    do {                                                                             \
-        hipError_t _e = (expr);                                                      \
-        if(_e != hipSuccess) { err = std::string(#expr) + ": " + hipGetErrorString(_e); return LRSC_ERR_DEVICE; } \
-    } while(0)
+constexpr int kOomStatus = LRSC_ERR_DEVICE;                      // what DEV_TRY answers when device memory runs out
 
 template <bool WIDE_A, bool WIDE_B>
 static int merge_strand_t(const FmStrand& a, const FmStrand& b, uint8_t** d_bwt_out, uint64_t** d_rank_out, double ms[2], std::string& err)
@@ -148,25 +116,25 @@ static int merge_strand_t(const FmStrand& a, const FmStrand& b, uint8_t** d_bwt_
     const uint64_t n_tiles = (N + kMergeTile - 1) / kMergeTile;
     const uint64_t walk_groups = (b.n_dollars + kMergeWalkThreads - 1) / kMergeWalkThreads;
     if(n_tiles >= (1ull << 31) || walk_groups >= (1ull << 31)) { err = "index merge: more than 2^31 tiles"; return LRSC_ERR_UNSUPPORTED; }
-    const MergeStrand<BA> A = merge_strand<BA>(a);
-    const MergeStrand<BB> B = merge_strand<BB>(b);
+    const StrandView<BA> A = strand_view<BA>(a);
+    const StrandView<BB> B = strand_view<BB>(b);
     Owned d;
     uint64_t *d_rank = nullptr, *d_tile = nullptr;
     uint8_t* d_bwt = nullptr;
-    MG_TRY(d.alloc(&d_rank, b.n_symbols));
+    DEV_TRY(d.alloc(&d_rank, b.n_symbols));
     const auto t0 = clk::now();
     hipLaunchKernelGGL((merge_rank_kernel<WIDE_A, WIDE_B>), dim3((unsigned)walk_groups), dim3(kMergeWalkThreads), 0, st, A, B, a.n_dollars,
                        b.n_dollars, d_rank);
-    MG_TRY(hipGetLastError());
-    MG_TRY(hipDeviceSynchronize());
+    DEV_TRY(hipGetLastError());
+    DEV_TRY(hipDeviceSynchronize());
     const auto t1 = clk::now();
-    MG_TRY(d.alloc(&d_tile, n_tiles + 1));
-    MG_TRY(d.alloc(&d_bwt, (N + 15) / 16 * 16));
+    DEV_TRY(d.alloc(&d_tile, n_tiles + 1));
+    DEV_TRY(d.alloc(&d_bwt, (N + 15) / 16 * 16));
     hipLaunchKernelGGL(merge_tile_kernel, dim3((unsigned)((n_tiles + 256) / 256)), dim3(256), 0, st, d_rank, b.n_symbols, N, n_tiles, d_tile);
-    MG_TRY(hipGetLastError());
+    DEV_TRY(hipGetLastError());
     hipLaunchKernelGGL((merge_interleave_kernel<WIDE_A, WIDE_B>), dim3((unsigned)n_tiles), dim3(kMergeLanes), 0, st, A, B, d_rank, d_tile, d_bwt);
-    MG_TRY(hipGetLastError());
-    MG_TRY(hipDeviceSynchronize());
+    DEV_TRY(hipGetLastError());
+    DEV_TRY(hipDeviceSynchronize());
     ms[0] += std::chrono::duration<double, std::milli>(t1 - t0).count();
     ms[1] += std::chrono::duration<double, std::milli>(clk::now() - t1).count();
     d.keep(d_rank); d.keep(d_bwt);
@@ -190,12 +158,12 @@ int merge_origin_device(const FmStrand& a, const FmStrand& b, const uint64_t* d_
     const uint64_t n = a.n_dollars + b.n_dollars;
     Owned d;
     uint8_t* d_origin = nullptr;
-    MG_TRY(d.alloc(&d_origin, n));
-    MG_TRY(hipMemsetAsync(d_origin, 0, n, st));
+    DEV_TRY(d.alloc(&d_origin, n));
+    DEV_TRY(hipMemsetAsync(d_origin, 0, n, st));
     hipLaunchKernelGGL(merge_origin_kernel, dim3((unsigned)((b.n_dollars + 255) / 256)), dim3(256), 0, st, a.dollars, a.n_dollars, b.dollars, b.n_dollars,
                        b.n_symbols, d_rank, d_origin);
-    MG_TRY(hipGetLastError());
-    MG_TRY(hipMemcpy(origin, d_origin, n, hipMemcpyDeviceToHost));
+    DEV_TRY(hipGetLastError());
+    DEV_TRY(hipMemcpy(origin, d_origin, n, hipMemcpyDeviceToHost));
     return LRSC_OK;
 }
 

@@ -24,6 +24,8 @@ namespace lrsc {
 struct alignas(16) Sym16 {
     uint32_t w[4];
 };
+// symbol i of the stretch at s
+LRSC_HD uint32_t sym_at(const Sym16* s, uint32_t i) { return (s[i >> 4].w[(i >> 2) & 3] >> (8 * (i & 3))) & 0xFFu; }
 
 // 32 symbols of a block as bit masks (bit i = symbol i): the two code planes (A=0 C=1 G=2 T=3; '$' is stored as A),
 // the '$' rows and the positions that exist (< n_valid).  All four are zero at positions >= n_valid.

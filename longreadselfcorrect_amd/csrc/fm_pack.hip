@@ -12,13 +12,9 @@
 // lane (consecutive lanes, consecutive addresses), then every thread packs the block of its own LDS row with the functions
 // of fm_pack.h.  pack_blocks_kernel sends the finished blocks back through LDS so that they leave as full 16-byte-per-lane
 // stores as well, every 64-byte block written once.  No atomics anywhere.
-#include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
-#include <algorithm>
-#include <vector>
-
-#include "../../include/lrsc.h"
+#include "fm_launch.h"
 #include "fm_pack.h"
 
 namespace lrsc {
@@ -100,26 +96,7 @@ struct IsDollar {
     __host__ __device__ __forceinline__ bool operator()(const uint64_t& pos) const { return bwt[pos] == 0; }
 };
 
-namespace {
-struct Owned {
-    std::vector<void*> ptrs;
-    ~Owned() { for(void* p : ptrs) (void)hipFree(p); }
-    template <class T> hipError_t alloc(T** p, size_t n)
-    {
-        void* q = nullptr;
-        hipError_t e = hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T));
-        if(e == hipSuccess) { ptrs.push_back(q); *p = static_cast<T*>(q); }
-        return e;
-    }
-    void keep(void* p) { ptrs.erase(std::remove(ptrs.begin(), ptrs.end(), p), ptrs.end()); }
-};
-}
-
-#define PK_TRY(expr)                                                                 \
-    do {                                                                             \
-        hipError_t _e = (expr);                                                      \
-        if(_e != hipSuccess) { err = std::string(#expr) + ": " + hipGetErrorString(_e); return LRSC_ERR_DEVICE; } \
-    } while(0)
+constexpr int kOomStatus = LRSC_ERR_DEVICE;                      // what DEV_TRY answers when device memory runs out
 
 template <class Block>
 static int pack_strand_t(const uint8_t* d_bwt, uint64_t N, PackedStrand& out, std::string& err)
@@ -131,40 +108,40 @@ static int pack_strand_t(const uint8_t* d_bwt, uint64_t N, PackedStrand& out, st
     const unsigned tiles = (unsigned)((n1 + kPackThreads - 1) / kPackThreads);
     Owned d;
     uint64_t* d_cnt = nullptr;
-    PK_TRY(d.alloc(&d_cnt, 5 * n1));
+    DEV_TRY(d.alloc(&d_cnt, 5 * n1));
     hipLaunchKernelGGL(pack_hist_kernel<Block>, dim3(tiles), dim3(kPackThreads), 0, st, d_bwt, N, n_blocks, d_cnt);
-    PK_TRY(hipGetLastError());
+    DEV_TRY(hipGetLastError());
     size_t need = 0;
-    PK_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, d_cnt, d_cnt, (int)n1, st));
+    DEV_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, d_cnt, d_cnt, (int)n1, st));
     uint8_t* d_tmp = nullptr;
-    PK_TRY(d.alloc(&d_tmp, need));
-    for(uint32_t k = 0; k < 5; ++k) PK_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, need, d_cnt + k * n1, d_cnt + k * n1, (int)n1, st));
+    DEV_TRY(d.alloc(&d_tmp, need));
+    for(uint32_t k = 0; k < 5; ++k) DEV_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, need, d_cnt + k * n1, d_cnt + k * n1, (int)n1, st));
     uint64_t tot[5];
-    for(uint32_t k = 0; k < 5; ++k) PK_TRY(hipMemcpy(&tot[k], d_cnt + k * n1 + n_blocks, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    for(uint32_t k = 0; k < 5; ++k) DEV_TRY(hipMemcpy(&tot[k], d_cnt + k * n1 + n_blocks, sizeof(uint64_t), hipMemcpyDeviceToHost));
     if(tot[4] >= (1ull << 32)) { err = "more than 2^32 reads"; return LRSC_ERR_UNSUPPORTED; }
     if(tot[0] + tot[1] + tot[2] + tot[3] + tot[4] != N) { err = "index packer: a BWT code outside $ACGT"; return LRSC_ERR_DEVICE; }
 
     Block* d_blocks = nullptr;
-    PK_TRY(d.alloc(&d_blocks, n_blocks));
+    DEV_TRY(d.alloc(&d_blocks, n_blocks));
     hipLaunchKernelGGL(pack_blocks_kernel<Block>, dim3(tiles), dim3(kPackThreads), 0, st, d_bwt, N, n_blocks, d_cnt, d_blocks);
-    PK_TRY(hipGetLastError());
+    DEV_TRY(hipGetLastError());
 
     // the '$' rows in position order, 2^30 positions per call (hipCUB counts in int)
     uint64_t* d_dollars = nullptr;
     uint64_t* d_nsel = nullptr;
-    PK_TRY(d.alloc(&d_dollars, tot[4]));
-    PK_TRY(d.alloc(&d_nsel, 1));
+    DEV_TRY(d.alloc(&d_dollars, tot[4]));
+    DEV_TRY(d.alloc(&d_nsel, 1));
     const uint64_t chunk = 1ull << 30;
     uint8_t* d_sel_tmp = nullptr;
-    PK_TRY(hipcub::DeviceSelect::If(nullptr, need, hipcub::CountingInputIterator<uint64_t>(0), d_dollars, d_nsel, (int)std::min(chunk, N), IsDollar{d_bwt}, st));
-    PK_TRY(d.alloc(&d_sel_tmp, need));
+    DEV_TRY(hipcub::DeviceSelect::If(nullptr, need, hipcub::CountingInputIterator<uint64_t>(0), d_dollars, d_nsel, (int)std::min(chunk, N), IsDollar{d_bwt}, st));
+    DEV_TRY(d.alloc(&d_sel_tmp, need));
     uint64_t got = 0;
     for(uint64_t base = 0; base < N; base += chunk) {
         size_t n2 = need;
-        PK_TRY(hipcub::DeviceSelect::If(d_sel_tmp, n2, hipcub::CountingInputIterator<uint64_t>(base), d_dollars + got, d_nsel,
+        DEV_TRY(hipcub::DeviceSelect::If(d_sel_tmp, n2, hipcub::CountingInputIterator<uint64_t>(base), d_dollars + got, d_nsel,
                                         (int)std::min(chunk, N - base), IsDollar{d_bwt}, st));
         uint64_t n_sel = 0;
-        PK_TRY(hipMemcpy(&n_sel, d_nsel, sizeof(uint64_t), hipMemcpyDeviceToHost));
+        DEV_TRY(hipMemcpy(&n_sel, d_nsel, sizeof(uint64_t), hipMemcpyDeviceToHost));
         got += n_sel;
         if(got > tot[4]) break;
     }
@@ -172,10 +149,10 @@ static int pack_strand_t(const uint8_t* d_bwt, uint64_t N, PackedStrand& out, st
 
     const uint64_t n_dir = (n_blocks >> kDollarDirShift) + 2;
     uint32_t* d_dir = nullptr;
-    PK_TRY(d.alloc(&d_dir, n_dir));
+    DEV_TRY(d.alloc(&d_dir, n_dir));
     hipLaunchKernelGGL(dollar_dir_kernel, dim3((unsigned)((n_dir + 255) / 256)), dim3(256), 0, st, d_cnt + 4 * n1, n_blocks, n_dir, d_dir);
-    PK_TRY(hipGetLastError());
-    PK_TRY(hipDeviceSynchronize());
+    DEV_TRY(hipGetLastError());
+    DEV_TRY(hipDeviceSynchronize());
 
     d.keep(d_blocks); d.keep(d_dollars); d.keep(d_dir);
     out.blocks = d_blocks;

@@ -5,17 +5,17 @@
 // symbols as they were: what is left is the BWT of the remaining reads, the mirror image of fm_merge.h's union.
 //
 //   mark     One lane per dropped read i walks it backwards from row i (the suffix that is the read's sentinel alone) with
-//            fm_locate.h's LF step until the row's symbol is '$', and sets the bit of every row it visits, the first and the
+//            fm_strand.h's LF step until the row's symbol is '$', and sets the bit of every row it visits, the first and the
 //            '$' row included.  The walks of different reads visit different rows; the bits of 32 rows share a word, so a bit is
 //            set with a 32-bit atomic OR.  The bitmap takes num_symbols / 8 bytes.
 //   count    rows of a tile of kRemoveTile whose bit is clear (remove_tile_kept); an exclusive scan gives every tile's offset
 //            in the output.
-//   compact  Per tile: its rank blocks are decoded (merge_decode_block), every lane takes 16 rows and copies the kept ones
+//   compact  Per tile: its rank blocks are decoded (decode_block), every lane takes 16 rows and copies the kept ones
 //            (remove_keep16, remove_scatter16) to a stage at the lane's offset, the sum of the kept rows of the lanes before
 //            it.  The stage is laid out congruent to the output modulo 16, so the tile leaves with 16-byte stores except for
 //            the bytes of the two 16-byte chunks it shares with its neighbours (remove_store_chunk).
 //
-// Every walk ends on any input (remove_mark_read: the bound of locate_prepare_read).  All functions here are LRSC_HD and free of
+// Every walk ends on any input (remove_mark_read is fm_strand.h's walk_read_back).  All functions here are LRSC_HD and free of
 // HIP types: the kernels call them, and tests/host_tools/remove_driver.cpp compiles the same source for the CPU and holds it
 // against a suffix sort of the kept reads.
 #pragma once
@@ -23,7 +23,7 @@
 
 #include <string>
 
-#include "fm_locate.h"
+#include "fm_strand.h"
 
 namespace lrsc {
 
@@ -38,23 +38,15 @@ static_assert(kRemoveTile % 32 == 0, "a tile is whole bitmap words");
 LRSC_HD uint64_t remove_bitmap_words(uint64_t n_symbols, uint32_t tile) { return (n_symbols + tile - 1) / tile * (tile / 32); }
 
 // ---- mark: the walk of one dropped read ----
-// mark(row) is called for every row of the read; rows += their number.  Returns kLocateOk when the walk ended at a '$' row.
+// mark(row) is called for every row of the read; rows += their number.  Returns kWalkOk when the walk ended at a '$' row.
 template <class Block, class Mark>
-LRSC_HD uint32_t remove_mark_read(const MergeStrand<Block>& S, const uint32_t* mtab, uint32_t read, Mark&& mark, uint64_t& rows)
+LRSC_HD uint32_t remove_mark_read(const StrandView<Block>& S, const uint32_t* mtab, uint32_t read, Mark&& mark, uint64_t& rows)
 {
-    using P = typename MergeLay<Block>::pos_t;
-    P i = (P)read;
-    // a read has fewer symbols than the strand has rows and never leaves it: the bound and the range check only end the walk
-    // through an index that is no BWT of a string set
-    for(uint64_t t = 0; t < S.N; ++t) {
-        if(i >= S.N) return kLocateBroken;
+    uint64_t k = 0, t = 0;
+    return walk_read_back(S, mtab, read, [&](typename BlockLay<Block>::pos_t i, uint64_t) {
         mark((uint64_t)i);
         ++rows;
-        const Block b = S.blocks[merge_block_of<Block>(i)];
-        uint64_t k = 0;
-        if(!locate_lf_step(S, b, mtab, i, k)) return kLocateOk;
-    }
-    return kLocateBroken;
+    }, k, t);
 }
 
 // ---- count: kept rows of a tile, from words [w0, w0 + n_words) of the bitmap that one lane looks at ----
@@ -97,7 +89,7 @@ LRSC_HD void remove_store_chunk(const Sym16* stage, uint32_t shift, uint32_t n_k
         *reinterpret_cast<Sym16*>(out16 + lo) = stage[c];
         return;
     }
-    for(uint32_t i = lo < shift ? shift : lo; i < (hi < end ? hi : end); ++i) out16[i] = (uint8_t)rle_sym(stage, i);
+    for(uint32_t i = lo < shift ? shift : lo; i < (hi < end ? hi : end); ++i) out16[i] = (uint8_t)sym_at(stage, i);
 }
 template <uint32_t kTile> struct RemoveStage { static constexpr uint32_t kRows = kTile / 16 + 1; };   // Sym16 rows: a tile shifted by up to 15 bytes
 

@@ -11,20 +11,14 @@
 //   3. remove_compact_kernel<WIDE>   per tile: its rank blocks go to LDS decoded, one lane per block; every lane copies the kept
 //                                    ones of its 16 rows to the stage at the workgroup prefix sum of the kept counts; the stage
 //                                    leaves with 16-byte stores where the tile owns the whole chunk
-#include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
-#include <algorithm>
 #include <chrono>
-#include <vector>
 
-#include "../../include/lrsc.h"
+#include "fm_launch.h"
 #include "fm_remove.h"
 
 namespace lrsc {
-
-template <bool WIDE> struct RemBlock { using type = Block32; };
-template <> struct RemBlock<true> { using type = Block64; };
 
 struct RemoveAtomicMark {
     uint32_t* bitmap;
@@ -33,18 +27,20 @@ struct RemoveAtomicMark {
 
 template <bool WIDE>
 __global__ __launch_bounds__(kRemoveWalkThreads) __attribute__((amdgpu_waves_per_eu(kRemoveWalkWavesPerSimd, kRemoveWalkWavesPerSimd)))
-void remove_mark_kernel(MergeStrand<typename RemBlock<WIDE>::type> S, const uint32_t* __restrict__ ids, uint64_t n_drop, uint32_t* __restrict__ bitmap,
+void remove_mark_kernel(StrandView<typename BlockOf<WIDE>::type> S, const uint32_t* __restrict__ ids, uint64_t n_drop, uint32_t* __restrict__ bitmap,
                         unsigned long long* __restrict__ rows_total, uint32_t* __restrict__ broken)
 {
-    using B = typename RemBlock<WIDE>::type;
-    __shared__ __attribute__((aligned(16))) uint32_t mtab[MergeMaskTab<B>::kWords];
-    for(uint32_t i = threadIdx.x; i < MergeMaskTab<B>::kWords; i += blockDim.x) mtab[i] = merge_mask_word<B>(i);
+    using B = typename BlockOf<WIDE>::type;
+    __shared__ __attribute__((aligned(16))) uint32_t mtab[MaskTab<B>::kWords];
+    // The table's fill and the wavefront sum below are written in place, not with fm_launch.h's fill_mask_table and wave_sum: with
+    // the helpers the kernel's instruction stream was not the one measured before (other register names, one operand order).
+    for(uint32_t i = threadIdx.x; i < MaskTab<B>::kWords; i += blockDim.x) mtab[i] = mask_word<B>(i);
     __syncthreads();
     const uint64_t k = (uint64_t)blockIdx.x * kRemoveWalkThreads + threadIdx.x;
     uint64_t rows = 0;
     if(k < n_drop) {
         const uint32_t read = ids[k];
-        if(read >= S.n_dollars || remove_mark_read<B>(S, mtab, read, RemoveAtomicMark{bitmap}, rows) != kLocateOk) *broken = 1u;
+        if(read >= S.n_dollars || remove_mark_read<B>(S, mtab, read, RemoveAtomicMark{bitmap}, rows) != kWalkOk) *broken = 1u;
     }
     // rows of the wavefront's walks -> one atomic (every lane of the wavefront is here)
     unsigned long long total = rows;
@@ -70,10 +66,10 @@ __global__ __launch_bounds__(256) void remove_count_kernel(const uint32_t* __res
 }
 
 template <bool WIDE>
-__global__ __launch_bounds__(kRemoveLanes) void remove_compact_kernel(MergeStrand<typename RemBlock<WIDE>::type> S, const uint32_t* __restrict__ bitmap,
+__global__ __launch_bounds__(kRemoveLanes) void remove_compact_kernel(StrandView<typename BlockOf<WIDE>::type> S, const uint32_t* __restrict__ bitmap,
                                                                       const uint64_t* __restrict__ tile_off, uint8_t* __restrict__ out)
 {
-    using B = typename RemBlock<WIDE>::type;
+    using B = typename BlockOf<WIDE>::type;
     constexpr uint32_t kChunks = B::kSyms / 16, kWaves = kRemoveLanes / 64;
     __shared__ Sym16 sym[kRemoveTile / 16];
     __shared__ Sym16 stage[RemoveStage<kRemoveTile>::kRows];
@@ -87,7 +83,7 @@ __global__ __launch_bounds__(kRemoveLanes) void remove_compact_kernel(MergeStran
     if(n_kept == 0) return;
     const uint64_t first_block = p0 / B::kSyms;
     const uint32_t n_blk = (n_valid + B::kSyms - 1) / B::kSyms;
-    for(uint32_t u = threadIdx.x; u < n_blk; u += kRemoveLanes) merge_decode_block<B>(S, first_block + u, sym + u * kChunks);
+    for(uint32_t u = threadIdx.x; u < n_blk; u += kRemoveLanes) decode_block<B>(S, first_block + u, sym + u * kChunks);
     const uint32_t keep = remove_keep16(bitmap, p0, threadIdx.x, n_valid);
     const uint32_t cnt = (uint32_t)__builtin_popcount(keep);
     uint32_t incl = cnt;
@@ -110,34 +106,12 @@ __global__ __launch_bounds__(kRemoveLanes) void remove_compact_kernel(MergeStran
     for(uint32_t c = threadIdx.x; 16 * c < shift + n_kept; c += kRemoveLanes) remove_store_chunk(stage, shift, n_kept, c, out16);
 }
 
-namespace {
-struct Owned {
-    std::vector<void*> ptrs;
-    ~Owned() { for(void* p : ptrs) (void)hipFree(p); }
-    template <class T> hipError_t alloc(T** p, size_t n)
-    {
-        void* q = nullptr;
-        hipError_t e = hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T));
-        if(e == hipSuccess) { ptrs.push_back(q); *p = static_cast<T*>(q); }
-        return e;
-    }
-    void keep(void* p) { ptrs.erase(std::remove(ptrs.begin(), ptrs.end(), p), ptrs.end()); }
-};
-}
-
-#define RM_TRY(expr)                                                                 \
-    do {                                                                             \
-        hipError_t _e = (expr);                                                      \
-        if(_e != hipSuccess) {                                                       \
-            err = std::string(#expr) + ": " + hipGetErrorString(_e);                 \
-            return _e == hipErrorOutOfMemory ? LRSC_ERR_NOMEM : LRSC_ERR_DEVICE;     \
-        }                                                                            \
-    } while(0)
+constexpr int kOomStatus = LRSC_ERR_NOMEM;                       // what DEV_TRY answers when device memory runs out
 
 template <bool WIDE>
 static int remove_strand_t(const FmStrand& s, const uint32_t* ids, uint64_t n_drop, uint8_t** d_bwt_out, uint64_t* n_out, double ms[2], std::string& err)
 {
-    using B = typename RemBlock<WIDE>::type;
+    using B = typename BlockOf<WIDE>::type;
     using clk = std::chrono::steady_clock;
     hipStream_t st = nullptr;
     const uint64_t N = s.n_symbols;
@@ -146,53 +120,53 @@ static int remove_strand_t(const FmStrand& s, const uint32_t* ids, uint64_t n_dr
     const uint64_t n_tiles = (N + kRemoveTile - 1) / kRemoveTile;
     const uint64_t walk_groups = (n_drop + kRemoveWalkThreads - 1) / kRemoveWalkThreads;
     if(n_tiles >= (1ull << 31) - 1 || walk_groups >= (1ull << 31)) { err = "index remove: more than 2^31 tiles"; return LRSC_ERR_UNSUPPORTED; }
-    const MergeStrand<B> S = merge_strand<B>(s);
+    const StrandView<B> S = strand_view<B>(s);
     const uint64_t n_words = remove_bitmap_words(N, kRemoveTile);
     Owned d;
     uint32_t *d_bitmap = nullptr, *d_ids = nullptr, *d_broken = nullptr;
     unsigned long long* d_rows = nullptr;
     uint64_t* d_kept = nullptr;
     uint8_t *d_tmp = nullptr, *d_bwt = nullptr;
-    RM_TRY(d.alloc(&d_bitmap, n_words));
-    RM_TRY(d.alloc(&d_ids, n_drop));
-    RM_TRY(d.alloc(&d_broken, 1));
-    RM_TRY(d.alloc(&d_rows, 1));
-    RM_TRY(d.alloc(&d_kept, n_tiles + 1));
-    RM_TRY(hipMemsetAsync(d_bitmap, 0, n_words * sizeof(uint32_t), st));
-    RM_TRY(hipMemsetAsync(d_broken, 0, sizeof(uint32_t), st));
-    RM_TRY(hipMemsetAsync(d_rows, 0, sizeof(unsigned long long), st));
-    if(n_drop) RM_TRY(hipMemcpyAsync(d_ids, ids, n_drop * sizeof(uint32_t), hipMemcpyHostToDevice, st));
-    RM_TRY(hipDeviceSynchronize());
+    DEV_TRY(d.alloc(&d_bitmap, n_words));
+    DEV_TRY(d.alloc(&d_ids, n_drop));
+    DEV_TRY(d.alloc(&d_broken, 1));
+    DEV_TRY(d.alloc(&d_rows, 1));
+    DEV_TRY(d.alloc(&d_kept, n_tiles + 1));
+    DEV_TRY(hipMemsetAsync(d_bitmap, 0, n_words * sizeof(uint32_t), st));
+    DEV_TRY(hipMemsetAsync(d_broken, 0, sizeof(uint32_t), st));
+    DEV_TRY(hipMemsetAsync(d_rows, 0, sizeof(unsigned long long), st));
+    if(n_drop) DEV_TRY(hipMemcpyAsync(d_ids, ids, n_drop * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    DEV_TRY(hipDeviceSynchronize());
     const auto t0 = clk::now();
     if(n_drop) {
         hipLaunchKernelGGL((remove_mark_kernel<WIDE>), dim3((unsigned)walk_groups), dim3(kRemoveWalkThreads), 0, st, S, d_ids, n_drop, d_bitmap, d_rows, d_broken);
-        RM_TRY(hipGetLastError());
+        DEV_TRY(hipGetLastError());
     }
     uint32_t broken = 0;
     unsigned long long rows = 0;
-    RM_TRY(hipMemcpy(&broken, d_broken, sizeof(uint32_t), hipMemcpyDeviceToHost));
-    RM_TRY(hipMemcpy(&rows, d_rows, sizeof(rows), hipMemcpyDeviceToHost));
+    DEV_TRY(hipMemcpy(&broken, d_broken, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    DEV_TRY(hipMemcpy(&rows, d_rows, sizeof(rows), hipMemcpyDeviceToHost));
     const auto t1 = clk::now();
     if(broken) { err = "index remove: a backward walk from a sentinel row does not end at a '$' row (the index is no BWT of a string set)"; return LRSC_ERR_FORMAT; }
     hipLaunchKernelGGL(remove_count_kernel, dim3((unsigned)((n_tiles + 1 + 3) / 4)), dim3(256), 0, st, d_bitmap, N, n_tiles, d_kept);
-    RM_TRY(hipGetLastError());
+    DEV_TRY(hipGetLastError());
     size_t need = 0;
-    RM_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, d_kept, d_kept, (int)(n_tiles + 1), st));
-    RM_TRY(d.alloc(&d_tmp, need));
-    RM_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, need, d_kept, d_kept, (int)(n_tiles + 1), st));
+    DEV_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need, d_kept, d_kept, (int)(n_tiles + 1), st));
+    DEV_TRY(d.alloc(&d_tmp, need));
+    DEV_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, need, d_kept, d_kept, (int)(n_tiles + 1), st));
     uint64_t total = 0;
-    RM_TRY(hipMemcpy(&total, d_kept + n_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    DEV_TRY(hipMemcpy(&total, d_kept + n_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost));
     if(total > N || N - total != rows) {
         err = "index remove: the marked rows are not the rows of the dropped reads (walks of two reads met: the index is no BWT of a string set)";
         return LRSC_ERR_FORMAT;
     }
     if(total == 0) { err = "index remove: nothing is kept"; return LRSC_ERR_ARG; }
     const uint64_t cap = (total + 15) / 16 * 16;
-    RM_TRY(d.alloc(&d_bwt, cap));
-    RM_TRY(hipMemsetAsync(d_bwt + cap - 16, 0, 16, st));           // the packer reads whole 16-byte rows
+    DEV_TRY(d.alloc(&d_bwt, cap));
+    DEV_TRY(hipMemsetAsync(d_bwt + cap - 16, 0, 16, st));           // the packer reads whole 16-byte rows
     hipLaunchKernelGGL((remove_compact_kernel<WIDE>), dim3((unsigned)n_tiles), dim3(kRemoveLanes), 0, st, S, d_bitmap, d_kept, d_bwt);
-    RM_TRY(hipGetLastError());
-    RM_TRY(hipDeviceSynchronize());
+    DEV_TRY(hipGetLastError());
+    DEV_TRY(hipDeviceSynchronize());
     ms[0] += std::chrono::duration<double, std::milli>(t1 - t0).count();
     ms[1] += std::chrono::duration<double, std::milli>(clk::now() - t1).count();
     d.keep(d_bwt);

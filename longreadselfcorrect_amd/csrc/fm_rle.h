@@ -9,15 +9,15 @@
 //
 // The encoder works on tiles of kRleTile symbols; a tile is kRleLanes stretches of kRleChunks x 16 symbols, one per lane, in
 // the Sym16 form of fm_pack.h.  The symbols come from the byte-per-symbol BWT, or from the rank blocks of a resident index
-// copy through unpack_block, the inverse of pack_block.  All functions here are LRSC_HD and free of HIP types: the kernels call
-// them, and tests/host_tools/rle_driver.cpp compiles the same source for the CPU and holds it against the sequential rule.
+// copy through fm_strand.h's decode_block, the inverse of pack_block.  All functions here are LRSC_HD and free of HIP types:
+// the kernels call them, and tests/host_tools/rle_driver.cpp compiles the same source for the CPU and holds it against the
+// sequential rule.
 #pragma once
 #include <stdint.h>
 
 #include <string>
 
-#include "fm_device.h"
-#include "fm_pack.h"
+#include "fm_strand.h"
 
 #ifdef __HIPCC__
 #define LRSC_ROLLED _Pragma("unroll 1")
@@ -66,9 +66,6 @@ struct RleCombine {
     LRSC_HD RunSummary operator()(const RunSummary& a, const RunSummary& b) const { return rle_combine(a, b); }
 };
 
-// symbol i of the stretch at s
-LRSC_HD uint32_t rle_sym(const Sym16* s, uint32_t i) { return (s[i >> 4].w[(i >> 2) & 3] >> (8 * (i & 3))) & 0xFFu; }
-
 // The walk over a stretch that all three phases share.  `in` summarises everything before the stretch (empty at the start of
 // the BWT); f(i, c, opens) sees symbol c at i and whether it opens a unit.
 template <uint32_t kChunks, class F>
@@ -109,7 +106,7 @@ LRSC_HD RunSummary stretch_summary(const Sym16* s, uint32_t n_valid)
         last = c;
     });
     r.tail = (uint8_t)(run % kRleMaxRun);
-    r.first = (uint8_t)rle_sym(s, 0);
+    r.first = (uint8_t)sym_at(s, 0);
     r.last = (uint8_t)last;
     r.flags = (uint8_t)(kRleSome | (changes == 0 ? kRleSingle : 0));
     return r;
@@ -138,47 +135,8 @@ LRSC_HD void stretch_emit(const Sym16* s, uint32_t n_valid, const RunSummary& in
         } else if(len) ++len;
     });
     if(!len) return;
-    for(uint32_t i = kChunks * 16; len < kRleMaxRun && i < kChunks * 16 + n_after && rle_sym(s, i) == code; ++i) ++len;
+    for(uint32_t i = kChunks * 16; len < kRleMaxRun && i < kChunks * 16 + n_after && sym_at(s, i) == code; ++i) ++len;
     out[n] = (uint8_t)((code << 5) | len);
-}
-
-// ---- rank block -> codes: the inverse of pack_block ----
-// bits 0..3 of x -> bit 0 of each of four bytes
-LRSC_HD uint32_t spread_byte_bits(uint32_t x) { return ((x & 0xFu) * 0x00204081u) & 0x01010101u; }
-
-LRSC_HD uint32_t plane_lo(const Block32& b, uint32_t wi) { return b.w[Block32::lo_index(wi)]; }
-LRSC_HD uint32_t plane_hi(const Block32& b, uint32_t wi) { return b.w[Block32::hi_index(wi)]; }
-LRSC_HD uint32_t plane_lo(const Block64& b, uint32_t wi) { return b.lo[wi]; }
-LRSC_HD uint32_t plane_hi(const Block64& b, uint32_t wi) { return b.hi[wi]; }
-LRSC_HD bool has_dollar_flag(const Block32& b) { return (b.cnt[0] & kFlag32) != 0; }
-LRSC_HD bool has_dollar_flag(const Block64& b) { return (b.cnt[0] & kFlag64) != 0; }
-
-// index of the first entry >= base of the sorted '$' list, for the block that starts at symbol `base`: one directory entry,
-// then the few list entries of the block's group that lie before the block
-LRSC_HD uint64_t first_dollar_of_block(const uint64_t* dollars, uint64_t n_dollars, const uint32_t* dollar_dir, uint64_t block, uint64_t base)
-{
-    uint64_t j = dollar_dir[block >> kDollarDirShift];
-    while(j < n_dollars && dollars[j] < base) ++j;
-    return j;
-}
-
-// The kSyms codes ($ACGT = 0..4) of block b, which starts at symbol `base` and of which the first n_valid symbols exist, to
-// out[0 .. kSyms/16); codes at and beyond n_valid are 0.  d[0..n_d) are the sorted '$' positions from the block's first one
-// on (first_dollar_of_block; entries beyond the block are ignored, and an unflagged block is given none).
-template <class Block>
-LRSC_HD void unpack_block(const Block& b, uint64_t base, const uint64_t* d, uint64_t n_d, uint32_t n_valid, Sym16* out)
-{
-    uint64_t j = 0;
-    LRSC_UNROLL
-    for(uint32_t wi = 0; wi < Block::kWords; ++wi) {
-        uint32_t dollar = 0;
-        for(; j < n_d && d[j] - base < 32ull * (wi + 1); ++j) dollar |= 1u << ((uint32_t)(d[j] - base) & 31u);
-        const uint32_t v = low_mask((int32_t)n_valid - (int32_t)(32 * wi)) & ~dollar;
-        const uint32_t lo = plane_lo(b, wi) & v, hi = plane_hi(b, wi) & v;
-        LRSC_UNROLL
-        for(uint32_t q = 0; q < 8; ++q)
-            out[2 * wi + (q >> 2)].w[q & 3] = spread_byte_bits(v >> (4 * q)) + spread_byte_bits(lo >> (4 * q)) + (spread_byte_bits(hi >> (4 * q)) << 1);
-    }
 }
 
 // ---- the device encoder (fm_rle.hip) ----

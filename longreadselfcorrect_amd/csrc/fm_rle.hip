@@ -9,16 +9,12 @@
 //
 // A tile is kRleTile symbols in LDS, one stretch of kRleChunks x 16 per lane (fm_rle.h).  The symbols come from the
 // byte-per-symbol BWT of build_bwt_resident (SrcBytes: 16-byte coalesced loads) or from the rank blocks of an index copy
-// (SrcBlocks: one lane unpacks one 64-byte block, looking its '$' rows up once through the directory).  Within a tile the lanes'
+// (SrcBlocks: one lane unpacks one 64-byte block with decode_block, looking its '$' rows up once through the directory).  Within a tile the lanes'
 // summaries are joined by a block scan with the same operator; the unit that a tile's last symbols open may run on for at most
 // 30 symbols, so the emit kernel loads a halo past the tile's end and no tile waits for another.  No atomics anywhere.
-#include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
-#include <algorithm>
-#include <vector>
-
-#include "../../include/lrsc.h"
+#include "fm_launch.h"
 #include "fm_rle.h"
 
 namespace lrsc {
@@ -63,15 +59,7 @@ __device__ __forceinline__ void load_tile(const SrcBlocks<Block>& src, uint64_t 
     constexpr uint32_t kBlocks = kRleTile / Block::kSyms;
     static_assert(kBlocks + 1 <= kRleLanes, "one lane per block, and one for the halo");
     const uint64_t g = tile * kBlocks + threadIdx.x;
-    if(threadIdx.x < kBlocks + (halo ? 1u : 0u) && g < src.n_blocks) {
-        const Block b = src.blocks[g];
-        const uint64_t base = g * Block::kSyms;
-        const uint64_t left = src.N - base;                       // n_blocks = N / kSyms + 1: base <= N
-        uint64_t j = src.n_dollars;
-        if(has_dollar_flag(b)) j = first_dollar_of_block(src.dollars, src.n_dollars, src.dollar_dir, g, base);
-        unpack_block<Block>(b, base, src.dollars + j, src.n_dollars - j, (uint32_t)(left < Block::kSyms ? left : Block::kSyms),
-                            syms + threadIdx.x * (Block::kSyms / 16));
-    }
+    if(threadIdx.x < kBlocks + (halo ? 1u : 0u) && g < src.n_blocks) decode_block<Block>(src, g, syms + threadIdx.x * (Block::kSyms / 16));
     __syncthreads();
 }
 
@@ -162,26 +150,7 @@ __global__ __launch_bounds__(kRleLanes) void rle_emit_kernel(Src src, const RunS
     }
 }
 
-namespace {
-struct Owned {
-    std::vector<void*> ptrs;
-    ~Owned() { for(void* p : ptrs) (void)hipFree(p); }
-    template <class T> hipError_t alloc(T** p, size_t n)
-    {
-        void* q = nullptr;
-        hipError_t e = hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T));
-        if(e == hipSuccess) { ptrs.push_back(q); *p = static_cast<T*>(q); }
-        return e;
-    }
-    void keep(void* p) { ptrs.erase(std::remove(ptrs.begin(), ptrs.end(), p), ptrs.end()); }
-};
-}
-
-#define RL_TRY(expr)                                                                 \
-    do {                                                                             \
-        hipError_t _e = (expr);                                                      \
-        if(_e != hipSuccess) { err = std::string(#expr) + ": " + hipGetErrorString(_e); return LRSC_ERR_DEVICE; } \
-    } while(0)
+constexpr int kOomStatus = LRSC_ERR_DEVICE;                      // what DEV_TRY answers when device memory runs out
 
 template <class Src>
 static int rle_t(const Src& src, uint8_t** d_units, uint64_t* n_units, std::string& err)
@@ -196,32 +165,32 @@ static int rle_t(const Src& src, uint8_t** d_units, uint64_t* n_units, std::stri
     Owned d;
     RunSummary *d_sum = nullptr, *d_incl = nullptr;
     uint64_t* d_cnt = nullptr;
-    RL_TRY(d.alloc(&d_sum, n_tiles));
-    RL_TRY(d.alloc(&d_incl, n_tiles));
-    RL_TRY(d.alloc(&d_cnt, n_tiles + 1));
+    DEV_TRY(d.alloc(&d_sum, n_tiles));
+    DEV_TRY(d.alloc(&d_incl, n_tiles));
+    DEV_TRY(d.alloc(&d_cnt, n_tiles + 1));
     hipLaunchKernelGGL(rle_summary_kernel<Src>, dim3(grid), dim3(kRleLanes), 0, st, src, d_sum);
-    RL_TRY(hipGetLastError());
+    DEV_TRY(hipGetLastError());
     size_t need_a = 0, need_b = 0;
-    RL_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, need_a, d_sum, d_incl, RleCombine{}, (int)n_tiles, st));
-    RL_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need_b, d_cnt, d_cnt, (int)(n_tiles + 1), st));
+    DEV_TRY(hipcub::DeviceScan::InclusiveScan(nullptr, need_a, d_sum, d_incl, RleCombine{}, (int)n_tiles, st));
+    DEV_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need_b, d_cnt, d_cnt, (int)(n_tiles + 1), st));
     uint8_t* d_tmp = nullptr;
     size_t need = std::max(need_a, need_b);
-    RL_TRY(d.alloc(&d_tmp, need));
-    RL_TRY(hipcub::DeviceScan::InclusiveScan(d_tmp, need, d_sum, d_incl, RleCombine{}, (int)n_tiles, st));
+    DEV_TRY(d.alloc(&d_tmp, need));
+    DEV_TRY(hipcub::DeviceScan::InclusiveScan(d_tmp, need, d_sum, d_incl, RleCombine{}, (int)n_tiles, st));
     // entry n_tiles is 0 and becomes the total in the scan
-    RL_TRY(hipMemsetAsync(d_cnt + n_tiles, 0, sizeof(uint64_t), st));
+    DEV_TRY(hipMemsetAsync(d_cnt + n_tiles, 0, sizeof(uint64_t), st));
     hipLaunchKernelGGL(rle_count_kernel<Src>, dim3(grid), dim3(kRleLanes), 0, st, src, d_incl, d_cnt);
-    RL_TRY(hipGetLastError());
+    DEV_TRY(hipGetLastError());
     need = std::max(need_a, need_b);
-    RL_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, need, d_cnt, d_cnt, (int)(n_tiles + 1), st));
+    DEV_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, need, d_cnt, d_cnt, (int)(n_tiles + 1), st));
     uint64_t total = 0;
-    RL_TRY(hipMemcpy(&total, d_cnt + n_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    DEV_TRY(hipMemcpy(&total, d_cnt + n_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost));
     if(total == 0 || total > src.N) { err = "RL encoder: unit count out of range"; return LRSC_ERR_DEVICE; }
     uint8_t* d_out = nullptr;
-    RL_TRY(d.alloc(&d_out, total));
+    DEV_TRY(d.alloc(&d_out, total));
     hipLaunchKernelGGL(rle_emit_kernel<Src>, dim3(grid), dim3(kRleLanes), 0, st, src, d_incl, d_cnt, d_out);
-    RL_TRY(hipGetLastError());
-    RL_TRY(hipDeviceSynchronize());
+    DEV_TRY(hipGetLastError());
+    DEV_TRY(hipDeviceSynchronize());
     d.keep(d_out);
     *d_units = d_out;
     *n_units = total;

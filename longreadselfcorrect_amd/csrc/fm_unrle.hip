@@ -17,13 +17,9 @@
 // written, so a piece never has to be put together from two chunks.  With the rows filled the kernel is the packer's
 // (block_hist, a workgroup scan, pack_block, the blocks out through LDS); the thread of a block also writes that block's '$'
 // positions and, for the first block of a group, the directory entry.  No atomics anywhere.
-#include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
-#include <algorithm>
-#include <vector>
-
-#include "../../include/lrsc.h"
+#include "fm_launch.h"
 #include "fm_unrle.h"
 
 namespace lrsc {
@@ -232,26 +228,7 @@ __global__ __launch_bounds__(kUnrleLanes, UnrleOcc<Block>::kWaves) void unrle_pa
         if(first + (q >> 2) < n_blocks) dst[q] = rows[(q >> 2) * Tile::kOutRow + (q & 3)];
 }
 
-namespace {
-struct Owned {
-    std::vector<void*> ptrs;
-    ~Owned() { for(void* p : ptrs) (void)hipFree(p); }
-    template <class T> hipError_t alloc(T** p, size_t n)
-    {
-        void* q = nullptr;
-        hipError_t e = hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T));
-        if(e == hipSuccess) { ptrs.push_back(q); *p = static_cast<T*>(q); }
-        return e;
-    }
-    void keep(void* p) { ptrs.erase(std::remove(ptrs.begin(), ptrs.end(), p), ptrs.end()); }
-};
-}
-
-#define UN_TRY(expr)                                                                 \
-    do {                                                                             \
-        hipError_t _e = (expr);                                                      \
-        if(_e != hipSuccess) { err = std::string(#expr) + ": " + hipGetErrorString(_e); return LRSC_ERR_DEVICE; } \
-    } while(0)
+constexpr int kOomStatus = LRSC_ERR_DEVICE;                      // what DEV_TRY answers when device memory runs out
 
 template <class Block>
 static int unrle_t(const uint8_t* d_units, uint64_t n_units, uint64_t N, PackedStrand& out, uint64_t* first_bad, std::string& err)
@@ -267,25 +244,25 @@ static int unrle_t(const uint8_t* d_units, uint64_t n_units, uint64_t N, PackedS
     if(n1 >= (1ull << 31)) { err = "RL decoder: more than 2^31 unit tiles"; return LRSC_ERR_UNSUPPORTED; }
     Owned d;
     uint64_t *d_scan = nullptr, *d_bad = nullptr, *d_first = nullptr;
-    UN_TRY(d.alloc(&d_scan, 6 * n1));
-    UN_TRY(d.alloc(&d_bad, n_tiles));
-    UN_TRY(d.alloc(&d_first, 1));
-    for(uint32_t k = 0; k < 6; ++k) UN_TRY(hipMemsetAsync(d_scan + k * n1 + n_tiles, 0, sizeof(uint64_t), st));
+    DEV_TRY(d.alloc(&d_scan, 6 * n1));
+    DEV_TRY(d.alloc(&d_bad, n_tiles));
+    DEV_TRY(d.alloc(&d_first, 1));
+    for(uint32_t k = 0; k < 6; ++k) DEV_TRY(hipMemsetAsync(d_scan + k * n1 + n_tiles, 0, sizeof(uint64_t), st));
     hipLaunchKernelGGL(unrle_tile_kernel, dim3((unsigned)n_tiles), dim3(kUnrleLanes), 0, st, d_units, n_units, n_tiles, d_scan, d_bad);
-    UN_TRY(hipGetLastError());
+    DEV_TRY(hipGetLastError());
     size_t need_a = 0, need_b = 0;
-    UN_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need_a, d_scan, d_scan, (int)n1, st));
-    UN_TRY(hipcub::DeviceReduce::Min(nullptr, need_b, d_bad, d_first, (int)n_tiles, st));
+    DEV_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, need_a, d_scan, d_scan, (int)n1, st));
+    DEV_TRY(hipcub::DeviceReduce::Min(nullptr, need_b, d_bad, d_first, (int)n_tiles, st));
     uint8_t* d_tmp = nullptr;
-    UN_TRY(d.alloc(&d_tmp, std::max(need_a, need_b)));
+    DEV_TRY(d.alloc(&d_tmp, std::max(need_a, need_b)));
     for(uint32_t k = 0; k < 6; ++k) {
         size_t need = need_a;
-        UN_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, need, d_scan + k * n1, d_scan + k * n1, (int)n1, st));
+        DEV_TRY(hipcub::DeviceScan::ExclusiveSum(d_tmp, need, d_scan + k * n1, d_scan + k * n1, (int)n1, st));
     }
-    UN_TRY(hipcub::DeviceReduce::Min(d_tmp, need_b, d_bad, d_first, (int)n_tiles, st));
+    DEV_TRY(hipcub::DeviceReduce::Min(d_tmp, need_b, d_bad, d_first, (int)n_tiles, st));
     uint64_t tot[6], bad = kNoBad64;
-    for(uint32_t k = 0; k < 6; ++k) UN_TRY(hipMemcpy(&tot[k], d_scan + k * n1 + n_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost));
-    UN_TRY(hipMemcpy(&bad, d_first, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    for(uint32_t k = 0; k < 6; ++k) DEV_TRY(hipMemcpy(&tot[k], d_scan + k * n1 + n_tiles, sizeof(uint64_t), hipMemcpyDeviceToHost));
+    DEV_TRY(hipMemcpy(&bad, d_first, sizeof(uint64_t), hipMemcpyDeviceToHost));
     // build_strand_image's checks and texts; past them every position that the pack kernel forms lies inside its array
     if(first_bad) *first_bad = bad;
     if(bad != kNoBad64) { err = "corrupt RL unit in BWT"; return LRSC_ERR_FORMAT; }
@@ -297,14 +274,14 @@ static int unrle_t(const uint8_t* d_units, uint64_t n_units, uint64_t N, PackedS
     Block* d_blocks = nullptr;
     uint64_t* d_dollars = nullptr;
     uint32_t* d_dir = nullptr;
-    UN_TRY(d.alloc(&d_blocks, n_blocks));
-    UN_TRY(d.alloc(&d_dollars, tot[4]));
-    UN_TRY(d.alloc(&d_dir, n_dir));
+    DEV_TRY(d.alloc(&d_blocks, n_blocks));
+    DEV_TRY(d.alloc(&d_dollars, tot[4]));
+    DEV_TRY(d.alloc(&d_dir, n_dir));
     const unsigned grid = (unsigned)((n_blocks + kUnrleBlocks - 1) / kUnrleBlocks);
     hipLaunchKernelGGL(unrle_pack_kernel<Block>, dim3(grid), dim3(kUnrleLanes), 0, st, d_units, n_units, N, n_blocks, n_tiles, d_scan, tot[4],
                        d_blocks, d_dollars, d_dir, n_dir);
-    UN_TRY(hipGetLastError());
-    UN_TRY(hipDeviceSynchronize());
+    DEV_TRY(hipGetLastError());
+    DEV_TRY(hipDeviceSynchronize());
 
     d.keep(d_blocks); d.keep(d_dollars); d.keep(d_dir);
     out.blocks = d_blocks;

@@ -60,9 +60,9 @@ static void run(const StrandImage& i0, const StrandImage& i1, bool wide)
 {
     static_assert(sizeof(DupResult) == 40, "lrsc_dup_result");
     const FmStrand f0 = strand_of(i0, wide), f1 = strand_of(i1, wide);
-    const MergeStrand<Block> S[2] = {merge_strand<Block>(f0), merge_strand<Block>(f1)};
-    std::vector<uint32_t> mtab(MergeMaskTab<Block>::kWords);
-    for(uint32_t i = 0; i < mtab.size(); ++i) mtab[i] = merge_mask_word<Block>(i);
+    const StrandView<Block> S[2] = {strand_view<Block>(f0), strand_view<Block>(f1)};
+    std::vector<uint32_t> mtab(MaskTab<Block>::kWords);
+    for(uint32_t i = 0; i < mtab.size(); ++i) mtab[i] = mask_word<Block>(i);
     const uint64_t n_slots = S[0].n_dollars;
     if(n_slots == 0 || S[1].n_dollars != n_slots) die("the strands hold no reads, or not the same number");
     std::vector<uint32_t> bits((n_slots + 31) / 32, 0u), winner(n_slots, kDupNoWinner);

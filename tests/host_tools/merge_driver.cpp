@@ -5,7 +5,7 @@
 // input:  for A, then for B: u64 N, u64 n_units, the RL units of the strand's BWT.
 // The two images come from build_strand_image (fm_layout.cpp), Block64 where wide, as lrsc_index_upload would hold them.  Then,
 // as fm_merge.hip does: merge_walk_step for every read of B until its '$' (rank[]), merge_tile_search for every tile edge,
-// per tile the B positions, merge_decode_block for the blocks of either span and merge_fill16 for every lane, and
+// per tile the B positions, decode_block for the blocks of either span and merge_fill16 for every lane, and
 // merge_origin_slot for every '$' row of B; with the kernels' tile (small = 0) or one of 384 positions, two Block32 or three
 // Block64 (small = 1).  What the kernels leave unwritten in LDS is 0xA5 here.
 // output: u64 N_A + N_B, the merged codes ($ACGT = 0..4); u64 N_B, rank[] as u64; u64 n_A + n_B, the origin bytes.
@@ -43,8 +43,8 @@ static FmStrand strand_of(const StrandImage& im, bool wide)
 template <class Block>
 static std::vector<uint32_t> mask_table()
 {
-    std::vector<uint32_t> t(MergeMaskTab<Block>::kWords);
-    for(uint32_t i = 0; i < t.size(); ++i) t[i] = merge_mask_word<Block>(i);
+    std::vector<uint32_t> t(MaskTab<Block>::kWords);
+    for(uint32_t i = 0; i < t.size(); ++i) t[i] = mask_word<Block>(i);
     return t;
 }
 
@@ -63,8 +63,8 @@ static void merge(const StrandImage& ia, const StrandImage& ib, bool wide_a, boo
     using SA = MergeStage<BA, kTile>;
     using SB = MergeStage<BB, kTile>;
     const FmStrand fa = strand_of(ia, wide_a), fb = strand_of(ib, wide_b);
-    const MergeStrand<BA> A = merge_strand<BA>(fa);
-    const MergeStrand<BB> B = merge_strand<BB>(fb);
+    const StrandView<BA> A = strand_view<BA>(fa);
+    const StrandView<BB> B = strand_view<BB>(fb);
     const std::vector<uint32_t> mtab_a = mask_table<BA>(), mtab_b = mask_table<BB>();
     const uint64_t N = A.N + B.N, n_a = A.n_dollars, n_b = B.n_dollars;
     if(n_b == 0) die("B holds no read");
@@ -79,8 +79,8 @@ static void merge(const StrandImage& ia, const StrandImage& ib, bool wide_a, boo
             if(w.i >= B.N || w.r > A.N) die("a walk left its index");
             if(rank[w.i] != unset) die("a row of B visited twice");
             rank[w.i] = w.r;
-            const BB bb = B.blocks[merge_block_of<BB>(w.i)];
-            const BA ba = A.blocks[merge_block_of<BA>(w.r)];
+            const BB bb = B.blocks[block_of<BB>(w.i)];
+            const BA ba = A.blocks[block_of<BA>(w.r)];
             if(!merge_walk_step(A, B, ba, bb, mtab_a.data(), mtab_b.data(), w)) break;
         }
         if(step == B.N) die("a walk met no '$'");
@@ -108,8 +108,8 @@ static void merge(const StrandImage& ia, const StrandImage& ib, bool wide_a, boo
         const MergeSpan span_b = merge_span<BB>(j0, j1);
         if(span_a.n_blocks > SA::kBlocks || span_b.n_blocks > SB::kBlocks) die("a span beyond its stage");
         for(uint32_t k = 0; k < n_bt; ++k) pos_b[k] = (uint16_t)(j0 + k + rank[j0 + k] - p0);
-        for(uint32_t u = 0; u < span_a.n_blocks; ++u) merge_decode_block<BA>(A, span_a.first_block + u, &sym_a[u * SA::kChunks]);
-        for(uint32_t u = 0; u < span_b.n_blocks; ++u) merge_decode_block<BB>(B, span_b.first_block + u, &sym_b[u * SB::kChunks]);
+        for(uint32_t u = 0; u < span_a.n_blocks; ++u) decode_block<BA>(A, span_a.first_block + u, &sym_a[u * SA::kChunks]);
+        for(uint32_t u = 0; u < span_b.n_blocks; ++u) decode_block<BB>(B, span_b.first_block + u, &sym_b[u * SB::kChunks]);
         const uint32_t n_valid = (uint32_t)(p1 - p0);
         for(uint32_t lane = 0; lane < kLanes; ++lane) {
             const uint32_t q = lane * 16;

@@ -6,7 +6,7 @@
 //         n_units', the RL units of the BWT that is expected of the kept reads.
 // The image comes from build_strand_image (fm_layout.cpp), Block64 where wide, as lrsc_index_upload would hold it.  Then, as
 // fm_remove.hip does: remove_mark_read for every dropped read, the kept rows of every tile lane by lane and their exclusive scan,
-// and per tile merge_decode_block for its blocks, remove_keep16 / remove_scatter16 for every lane at the prefix sum of the lanes
+// and per tile decode_block for its blocks, remove_keep16 / remove_scatter16 for every lane at the prefix sum of the lanes
 // before it and remove_store_chunk for every chunk; with the kernels' tile (small = 0) or one of 384 rows, two Block32 or three
 // Block64 (small = 1).  What the kernels leave unwritten in LDS is 0xA5 here.  The compacted codes are then packed with
 // fm_pack.h's functions in fm_pack.hip's order and held against build_strand_image of the expected units, byte for byte.
@@ -111,9 +111,9 @@ static void remove(StrandImage& im, bool wide, bool defect, const std::vector<ui
     static_assert(kTile % Block::kSyms == 0 && kTile % 32 == 0, "a tile is whole rank blocks and bitmap words");
     if(defect) for(uint64_t& d : im.dollars) d = ~0ull;           // no row is a '$' row any more
     const FmStrand fs = strand_of(im, wide);
-    const MergeStrand<Block> S = merge_strand<Block>(fs);
-    std::vector<uint32_t> mtab(MergeMaskTab<Block>::kWords);
-    for(uint32_t i = 0; i < mtab.size(); ++i) mtab[i] = merge_mask_word<Block>(i);
+    const StrandView<Block> S = strand_view<Block>(fs);
+    std::vector<uint32_t> mtab(MaskTab<Block>::kWords);
+    for(uint32_t i = 0; i < mtab.size(); ++i) mtab[i] = mask_word<Block>(i);
     const uint64_t N = S.N;
 
     // 1. the walks
@@ -127,7 +127,7 @@ static void remove(StrandImage& im, bool wide, bool defect, const std::vector<ui
             if(!defect && ((bitmap[row >> 5] >> (row & 31)) & 1u)) die("a row visited twice");
             bitmap[row >> 5] |= 1u << (row & 31);
         }, rows);
-        broken = broken || st != kLocateOk;
+        broken = broken || st != kWalkOk;
     }
     if(broken) format_path("a walk did not end at a '$' row");
     if(defect) die("the defective index was walked to an end");
@@ -166,7 +166,7 @@ static void remove(StrandImage& im, bool wide, bool defect, const std::vector<ui
         if(n_kept > n_valid) die("a tile keeps more rows than it has");
         if(n_kept == 0) continue;
         const uint32_t n_blk = (n_valid + Block::kSyms - 1) / Block::kSyms;
-        for(uint32_t u = 0; u < n_blk; ++u) merge_decode_block<Block>(S, p0 / Block::kSyms + u, &sym[u * (Block::kSyms / 16)]);
+        for(uint32_t u = 0; u < n_blk; ++u) decode_block<Block>(S, p0 / Block::kSyms + u, &sym[u * (Block::kSyms / 16)]);
         const uint32_t shift = (uint32_t)(off & 15u);
         uint32_t before = 0;
         for(uint32_t lane = 0; lane < kLanes; ++lane) {
