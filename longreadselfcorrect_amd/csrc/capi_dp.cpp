@@ -13,6 +13,14 @@ struct DpAlignClasses {
         Class& c = cls[dp_align_class(stage_bytes)];
         c.max_s1 = std::max(c.max_s1, s1_len); c.stage_max = std::max(c.stage_max, stage_bytes); c.jobs += n_jobs;
     }
+    // wavefronts of class k's launch
+    uint32_t waves(uint32_t k, uint32_t lds_waves) const
+    {
+        const Class& c = cls[k];
+        if(!c.jobs) return 0;
+        const uint64_t want = k < kDpAlignClasses ? lds_waves : 1024, stride = (uint64_t)(c.max_s1 + 17) * kDpTraceStride;
+        return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(want, c.jobs), (4ull << 30) / stride));
+    }
     // `al`: everything but the per-launch fields; lds_waves: wavefronts of an LDS launch (the traceback scratch is capped at 4 GB)
     int launch(lrsc_ctx* ctx, DpAlignArgs al, uint32_t lds_waves, DevBuf<uint8_t>& d_trace, DevBuf<uint8_t>& d_seq_ws) const
     {
@@ -22,8 +30,7 @@ struct DpAlignClasses {
             const Class& c = cls[k];
             if(!c.jobs) continue;
             stride[k] = (uint64_t)(c.max_s1 + 17) * kDpTraceStride;
-            const uint64_t want = k < kDpAlignClasses ? lds_waves : 1024;
-            nw[k] = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(want, c.jobs), (4ull << 30) / stride[k]));
+            nw[k] = waves(k, lds_waves);
             trace_bytes = std::max(trace_bytes, stride[k] * nw[k]);
             if(k == kDpAlignClasses) ws_bytes = (((uint64_t)c.stage_max + 255) & ~255ull) * nw[k];
         }
@@ -157,10 +164,27 @@ int DpStage::align_chunk(lrsc_ctx* ctx, const Tunables& tn, const std::vector<Dp
     if(tn.profile && ch.begin == 0 && jobs) {
         std::vector<DpAlignOut> ao(jobs);
         (void)hipMemcpy(ao.data(), d_align.p, jobs * sizeof(DpAlignOut), hipMemcpyDeviceToHost);
-        double tf = 0, tt = 0, cols = 0, na = 0;
-        for(const DpAlignOut& o : ao) if(!o.skipped) { tf += o.t_fill; tt += o.t_trace; cols += o.total_columns; na += 1; }
-        std::fprintf(stderr, "[lrsc] align: %llu jobs (%.0f aligned), %.0f columns avg, per job %.0f ticks fill + %.0f ticks traceback; %u waves; jobs / lds B per class:",
-                     (unsigned long long)jobs, na, cols / std::max(na, 1.0), tf / std::max(na, 1.0), tt / std::max(na, 1.0), (unsigned)lds_waves);
+        double tf = 0, tt = 0, cols = 0, na = 0, trips = 0;
+        for(const DpAlignOut& o : ao) if(!o.skipped) { tf += o.t_fill; tt += o.t_trace; cols += o.total_columns; na += 1; trips += o.t_trips; }
+        // how evenly the static hand-out (job % wavefronts of the launch) loads the wavefronts of the class with the most alignments
+        uint32_t big = 0;
+        for(uint32_t k = 1; k <= kDpAlignClasses; ++k) if(ch.classes.cls[k].jobs > ch.classes.cls[big].jobs) big = k;
+        const uint32_t nw = ch.classes.waves(big, lds_waves);
+        std::vector<double> wave(std::max(nw, 1u), 0.0);
+        for(uint32_t i = ch.begin; i < ch.end; ++i) {
+            const DpRequest& r = reqs[i];
+            if(dp_align_class(dp_align_stage_bytes(r.lq, r.str_cap)) != big) continue;
+            for(uint32_t s = 0; s < r.n_str; ++s) {
+                const DpAlignOut& o = ao[r.job_first + s];
+                wave[(r.job_first + s) % wave.size()] += (double)o.t_fill + o.t_trace;
+            }
+        }
+        double w_max = 0, w_sum = 0;
+        for(double w : wave) { w_max = std::max(w_max, w); w_sum += w; }
+        std::fprintf(stderr, "[lrsc] align: %llu jobs (%.0f aligned), %.0f columns avg, per job %.0f ticks fill + %.0f ticks traceback, %.1f trips of %.2f steps; "
+                             "%u waves, busiest / mean %.3f; jobs / lds B per class:",
+                     (unsigned long long)jobs, na, cols / std::max(na, 1.0), tf / std::max(na, 1.0), tt / std::max(na, 1.0), trips / std::max(na, 1.0),
+                     cols / std::max(trips, 1.0), (unsigned)nw, w_sum > 0 ? w_max * wave.size() / w_sum : 0.0);
         for(const DpAlignClasses::Class& k : ch.classes.cls) std::fprintf(stderr, " %llu / %u", (unsigned long long)k.jobs, k.stage_max);
         std::fprintf(stderr, " (the last from global memory)\n");
     }

@@ -227,7 +227,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8))) void dp
         }
         DpAlignOut o;
         o.m0s = 0; o.m0e = -1; o.m1s = 0; o.m1e = -1; o.score = -1; o.edit_distance = -1; o.total_columns = -1; o.n_ops = 0;
-        o.accept = 0; o.skipped = 1; o.t_fill = 0; o.t_trace = 0;
+        o.accept = 0; o.skipped = 1; o.t_fill = 0; o.t_trace = 0; o.t_trips = 0;
         const uint64_t t_job0 = __builtin_readcyclecounter();
         if(J.s1_len == 0 || J.s2_len == 0) {
             if(lane == 0) a.out[job] = o;
@@ -361,14 +361,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8))) void dp
         uint32_t w0 = 0, w1 = 0, w2 = 0, w3 = 0;
         int wb = -1;                                                // first column of the 16-column window held in w0..w3
         uint32_t wcur = 0, key = ~0u;                               // the one of w0..w3 that holds band rows 16 d ..: key = wb | d
-        // the sequence tests of a cell come from two windows across the lanes, one v_readlane each (the fill's indexing: h1 = c[k] == c[k + 1]
+        // the sequence tests of a cell come from two windows across the lanes (the fill's indexing: h1 = c[k] == c[k + 1]
         // with c[k] = S1[i - 1]; h2 = e == e' and mismatch = c[k] != e with e = S2[j - 1], e' = S2[j]; S1[L1] = 4, S2[j >= L2] = 4):
-        uint32_t v1 = 0;                                            // lane l, column i = wb + l: S1[i - 1] << 4 | h1 << 2; loaded with w0..w3
+        uint32_t v1 = 0;                                            // lane l, column i = wb + (l >> 2): S1[i - 1] << 4 | h1 << 2; loaded with w0..w3
         uint32_t v2 = 0;                                            // lane l, row j = s2_base + l + 1: S2[j - 1] << 4 | h2 << 3
         int s2_base = 0x40000000;
-        uint32_t acc = 0, n_ops = 0;
+        uint32_t acc = 0, n_ops = 0, trips = 0;
         uint8_t* ops = a.ops + J.ops_off;
         bool bad = false;
+        // One trip takes a whole run of M steps and the I or D step behind it.  A diagonal step keeps the band row r, so the cells an M
+        // run would visit from (ti, tj) lie in the window's columns wb + c, c = col, col - 1, ..., at row tj - (col - c), and the lane
+        // (c << 2 | r >> 6) that holds the code of (wb + c, r) finishes the decision of that cell: all 16 at once, each as if the walk
+        // stood there.  The walk does stand there exactly as long as every cell before it said M, so the steps are the serial walk's.
         while(ti > 0 && tj > 0) {
             const int r = tj - origin - ti;
             if((uint32_t)r >= (uint32_t)bw) { bad = true; break; }
@@ -382,7 +386,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8))) void dp
                     w1 = __hip_atomic_load(src + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     w2 = __hip_atomic_load(src + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     w3 = __hip_atomic_load(src + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    int x = wb + (int)lane;                         // lanes 0 .. 15 are read, at 1 <= i <= L1; the others stay inside S1[0 .. L1]
+                    int x = wb + (int)(lane >> 2);                  // a column is taken at 1 <= i <= L1; the others stay inside S1[0 .. L1]
                     x = x < 1 ? 1 : x > L1 ? L1 : x;
                     const uint32_t c_prev = S1[x - 1], c_here = S1[x];
                     v1 = c_prev << 4 | (c_prev == c_here ? 4u : 0u);
@@ -396,25 +400,48 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8))) void dp
                 const uint32_t e_prev = p[0], e_here = p[1];
                 v2 = e_prev << 4 | (e_prev == e_here ? 8u : 0u);
             }
-            const uint32_t col = (uint32_t)(ti - wb);
-            const uint32_t ab = ((uint32_t)__builtin_amdgcn_readlane((int)wcur, (int)(col << 2 | (uint32_t)r >> 6)) >> (2 * ((uint32_t)r & 15u))) & 3u;
-            // bits 2, 3: h1, h2; above them the two characters' difference
-            const uint32_t x = (uint32_t)__builtin_amdgcn_readlane((int)v1, (int)col) ^ (uint32_t)__builtin_amdgcn_readlane((int)v2, tj - 1 - s2_base);
+            ++trips;
+            const uint32_t col = (uint32_t)(ti - wb), t0 = (uint32_t)(tj - 1 - s2_base);
+            // the lane's cell: column wb + (lane >> 2), whose row tj - (col - (lane >> 2)) lane t0 - (col - (lane >> 2)) of v2 holds (a lane
+            // index that wraps belongs to a cell beyond `lim` below).  Bits 2, 3 of x: h1, h2; above them the two characters' difference.
+            const uint32_t ab = (wcur >> (2 * ((uint32_t)r & 15u))) & 3u;
+            const uint32_t x = v1 ^ (uint32_t)__builtin_amdgcn_ds_bpermute((int)((lane & ~3u) + 4u * (t0 - col)), (int)v2);
             const uint32_t step = (kDpStepTable >> (2 * (ab | (x & 12u)))) & 3u;                      // 3 = M, 2 = I, 1 = D
-            const uint32_t edit = (step ^ 3u) | x >> 4;             // not M, or M over a mismatch
-            o.edit_distance += (int)(edit < 1u ? edit : 1u);
-            ti -= (int)(step & 1u);
-            tj -= (int)(step >> 1);
-            const uint32_t op = (0x4D494400u >> (8 * step)) & 0xFFu;                                  // - 'D' 'I' 'M'
-            acc = lane == (n_ops & 63u) ? op : acc;
-            ++n_ops;
+            // the cells' answers in walk order from bit 63 down, one per four bits: the lanes of band rows 64 (r >> 6) ..
+            const uint32_t up = 63u - (col << 2 | (uint32_t)r >> 6);
+            const uint64_t mine = 0x1111111111111111ull << ((uint32_t)r >> 6);
+            const uint64_t stop = (__builtin_amdgcn_ballot_w64(step != 3u) & mine) << up;
+            const uint64_t mism = (__builtin_amdgcn_ballot_w64(x > 15u) & mine) << up;
+            const uint64_t ins = __builtin_amdgcn_ballot_w64(step == 2u) << up;
+            // M cells before the first other one; at most 15 because of the guard bit: 16 M cells count as 15
+            const uint32_t run = (uint32_t)__builtin_clzll(stop | 1u) >> 2;
+            // No step the serial walk would not take: ti > 0 and tj > 0 before each, the column in the window, the row in the v2 window,
+            // not past the next flush of `ops`, and not beyond the 15 cells `run` can tell of (the 16th waits for the next trip).
+            // (The minima are kept apart pair by pair so that they stay scalar: a three-way minimum exists on the vector side only.)
+            uint32_t lim = (uint32_t)(ti < tj ? ti : tj), lim_w = col < t0 ? col + 1 : t0 + 1;
+            asm volatile("" : "+s"(lim), "+s"(lim_w));
+            lim = lim < lim_w ? lim : lim_w;
+            asm volatile("" : "+s"(lim));
+            lim = lim < 64u - (n_ops & 63u) ? lim : 64u - (n_ops & 63u);
+            asm volatile("" : "+s"(lim));
+            lim = lim < 15u ? lim : 15u;
+            const uint32_t n = run < lim ? run : lim;               // M steps of this trip
+            const uint32_t other = run < lim ? 1u : 0u;             // and the I or D step behind them, where it is inside the limits too
+            const uint32_t is_i = other & (uint32_t)((ins << (4 * run)) >> 63);
+            o.edit_distance += (int)other + __builtin_popcountll((mism >> 4) >> (60 - 4 * n));        // M over a mismatch counts
+            ti -= (int)(n + (other ^ is_i));
+            tj -= (int)(n + is_i);
+            const uint32_t at = lane - (n_ops & 63u), tot = n + other;
+            const uint32_t last = other ? (is_i ? (uint32_t)'I' : (uint32_t)'D') : (uint32_t)'M';
+            acc = at < tot ? (at == tot - 1 ? last : (uint32_t)'M') : acc;
+            n_ops += tot;
             if((n_ops & 63u) == 0) ops[n_ops - 64 + lane] = (uint8_t)acc;
         }
         o.total_columns = (int)n_ops;
         if((n_ops & 63u) != 0 && lane < (n_ops & 63u)) ops[(n_ops & ~63u) + lane] = (uint8_t)acc;
         o.m0s = ti; o.m1s = tj;
         o.n_ops = bad ? 0xFFFFFFFFu : n_ops;
-        o.t_fill = (uint32_t)(t_job1 - t_job0); o.t_trace = (uint32_t)(__builtin_readcyclecounter() - t_job1);
+        o.t_fill = (uint32_t)(t_job1 - t_job0); o.t_trace = (uint32_t)(__builtin_readcyclecounter() - t_job1); o.t_trips = trips;
         if(a.reqs && !bad) {
             const DpRequest& R = a.reqs[J.req];
             const bool bPassedOverlap = (uint64_t)(int64_t)o.total_columns >= (uint64_t)R.min_overlap;

@@ -31,6 +31,7 @@ struct DpAlignOut {               // SequenceOverlap (Thirdparty/overlapper.h:69
     uint32_t accept;              // aligned, overlap length >= min_overlap and identity >= min_identity (LongReadOverlap.cpp:645-655)
     uint32_t skipped;
     uint32_t t_fill, t_trace;     // profiling: ticks spent in the DP fill / the traceback
+    uint32_t t_trips;             // profiling: trips of the traceback loop (total_columns op-steps were taken in them)
 };
 
 // one correctByMSAlignment call (PacBioSelfCorrectionProcess.cpp:208-245)
