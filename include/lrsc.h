@@ -231,6 +231,29 @@ void lrsc_dupcheck_destroy(lrsc_dupcheck* dc);
  * limits; on an error nothing stays allocated and *out is untouched. */
 int lrsc_index_remove(lrsc_index* idx, const uint8_t* drop, uint64_t n_reads, int device, lrsc_index** out);
 
+/* ---- k-mer read correction: `stride correct -a kmer` (Algorithm/ErrorCorrectProcess.cpp:287-438, 488-544) --------------------- */
+typedef struct lrsc_kcorrect_params { int32_t kmer_length, kmer_threshold, kmer_rounds, quality_cutoff; } lrsc_kcorrect_params; /* -k 31, -x 3, -i 10, 20 */
+typedef struct lrsc_kcorrect_result { uint32_t kmer_qc, n_changed, passes, pad; } lrsc_kcorrect_result;
+/* ErrorCorrectProcess::kmerCorrection for n_reads reads (concatenated ACGT bytes, n_reads + 1 offsets) against the ctx's index;
+ * the result is that of the reference's serial run, byte for byte.  The count of a k-mer is the size of its interval in .bwt plus
+ * that of its reverse complement's (BWTAlgorithms::countSequenceOccurrences).  A k-mer marks its bases solid when its count
+ * reaches the support of the lowest phred among them: kmer_threshold at quality_cutoff or above, else kmer_threshold + 1
+ * (Util/CorrectionThresholds.cpp:26-39); phred = one score per base (quality character - 33), NULL = 15 everywhere.  While a
+ * base is unsolid, the first unsolid base from the left for which attemptKmerCorrection succeeds with its leftmost or else its
+ * rightmost covering k-mer is replaced: by the last base in A,C,G,T order whose k-mer count is at least twice max(the k-mer's
+ * count, the support of the base's phred), if that is not the base itself.  `if(rounds++ > maxAttempts) break;` allows
+ * kmer_rounds + 1 corrections and kmer_rounds + 2 counting passes.
+ * corrected = the reads after it, at the same offsets: a read that ended all solid as edited with kmer_qc = 1, any other one,
+ * and a read shorter than kmer_length, unedited with kmer_qc = 0.  passes = the counting passes made (0 for a read shorter than
+ * kmer_length), n_changed = the bases of corrected that differ from the read.
+ * LRSC_ERR_ARG for kmer_length, kmer_threshold or kmer_rounds <= 0, for an empty read and for a base other than A,C,G,T;
+ * LRSC_ERR_FORMAT when an interval leaves the strand (an index that is no BWT of a string set); on an error corrected and out
+ * are untouched.  n_reads == 0 does nothing.  The launches are counted under LRSC_K_FIND; a backward-search step is two of its
+ * rank_queries. */
+int lrsc_kmer_correct(lrsc_ctx* ctx, const char* reads, const uint64_t* read_off, uint32_t n_reads,
+                      const uint8_t* phred /* one per base, NULL = 15 everywhere */,
+                      const lrsc_kcorrect_params* p, char* corrected /* same offsets as reads */, lrsc_kcorrect_result* out);
+
 /* ---- LongReadProbe k-mer feature grid -------------------------------------------------- */
 /* reads: concatenated ACGT bytes, read_off: n_reads+1 offsets.  ks: ascending k-mer sizes
  * (the "pool", e.g. {5,9,15,17,19}), n_k <= 8.  For read r, position p, pool slot j the record

@@ -196,6 +196,7 @@ SA_DTYPE = np.dtype([("read", "<u4"), ("pos", "<u4")])          # lrsc_sa_elem
 # lrsc_dup_result; cls is one of DUP_UNIQUE .. DUP_ABSENT
 DUP_DTYPE = np.dtype([("fwd_lower", "<i8"), ("fwd_upper", "<i8"), ("rvc_lower", "<i8"), ("rvc_upper", "<i8"), ("cls", "<i4"), ("pad", "<u4")])
 DUP_UNIQUE, DUP_SUBSTRING, DUP_FULL_LENGTH, DUP_ABSENT = range(4)
+KCORRECT_DTYPE = np.dtype([("kmer_qc", "<u4"), ("n_changed", "<u4"), ("passes", "<u4"), ("pad", "<u4")])      # lrsc_kcorrect_result
 assert RANK_DTYPE.itemsize == C.sizeof(RankQuery) and BIIV_DTYPE.itemsize == C.sizeof(BiInterval)
 
 
@@ -254,6 +255,7 @@ class Lrsc:
         L.lrsc_dupcheck_destroy.argtypes = [C.c_void_p]
         L.lrsc_dupcheck_destroy.restype = None
         L.lrsc_index_remove.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]
+        L.lrsc_kmer_correct.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.lrsc_params_default.argtypes = [C.c_int, C.c_int, C.POINTER(Params)]
         L.lrsc_ctx_create.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int, C.POINTER(C.c_void_p)]
         L.lrsc_ctx_destroy.argtypes = [C.c_void_p]
@@ -521,6 +523,22 @@ class Ctx:
         h = C.c_void_p()
         self.api.check(self.api.lib.lrsc_dupcheck_create(self.h, C.byref(h)), "lrsc_dupcheck_create")
         return DupCheck(self.api, self, h)
+
+    def kmer_correct(self, bases: np.ndarray, off: np.ndarray, phred: np.ndarray | None = None, kmer_length: int = 31, kmer_threshold: int = 3,
+                     kmer_rounds: int = 10, quality_cutoff: int = 20):
+        """lrsc_kmer_correct of the reads (ASCII bases, n + 1 offsets; phred one score per base or None) -> (the corrected reads at
+        the same offsets, KCORRECT_DTYPE per read)."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        if phred is not None:
+            phred = np.ascontiguousarray(phred, dtype=np.uint8)
+            assert phred.size == bases.size
+        params = np.array([kmer_length, kmer_threshold, kmer_rounds, quality_cutoff], dtype=np.int32)
+        corrected = np.zeros(bases.size, dtype=np.uint8)
+        out = np.zeros(off.size - 1, dtype=KCORRECT_DTYPE)
+        self.api.check(self.api.lib.lrsc_kmer_correct(self.h, _ptr(bases), _ptr(off), off.size - 1, None if phred is None else _ptr(phred), _ptr(params),
+                                                      _ptr(corrected), _ptr(out)), "lrsc_kmer_correct")
+        return corrected, out
 
     def rank(self, bases: np.ndarray, idx: np.ndarray, strand: np.ndarray | int) -> np.ndarray:
         n = len(idx)

@@ -174,7 +174,11 @@ struct lrsc_ctx {
     lrsc::DevBuf<lrsc::SaipbJob> sp_jobs;
     lrsc::DevBuf<lrsc::SaipbOut> sp_out;
     lrsc::DevBuf<char> sp_text;
-    ~lrsc_ctx();                                         // drains the stream, then frees cs and the ctx's own objects (capi_correct.cpp)
+    // lrsc_kmer_correct's: the long reads' workspace and their places in it, the results
+    lrsc::DevBuf<uint8_t> kc_ws;
+    lrsc::DevBuf<uint64_t> kc_ws_off;
+    lrsc::DevBuf<lrsc_kcorrect_result> kc_res;
+    ~lrsc_ctx();                                        // drains the stream, then frees cs and the ctx's own objects (capi_correct.cpp)
 };
 
 struct lrsc_batch {

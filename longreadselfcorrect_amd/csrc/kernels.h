@@ -108,6 +108,15 @@ hipError_t launch_dup_chains(const FmIndexDev& fm, const uint32_t* words, const 
                              hipStream_t stream);
 hipError_t launch_dup_classify(const FmIndexDev& fm, const DupChainOut* chains, uint32_t n, uint64_t n_slots, DupResult* results, uint64_t* slots, uint32_t* winner,
                                uint32_t* bits, uint32_t* broken, hipStream_t stream);
+// The k-mer correction of n reads (fm_kcorrect.hip), one wavefront each: codes and read_off as above, phred one score per base
+// or nullptr (15 everywhere); corrected = the reads' codes after it, at the same offsets.  ws_off[read] is the read's place in
+// the workspace ws (kc_workspace_bytes of its length) when it has more than kKcLdsBases bases, anything otherwise.  *broken is
+// set to 1 when an interval leaves the strand.
+struct KcParams;
+struct KcResult;
+hipError_t launch_kmer_correct(const FmIndexDev& fm, const uint8_t* codes, const uint64_t* read_off, const uint8_t* phred, uint32_t n, const KcParams& p,
+                               uint8_t* ws, const uint64_t* ws_off, uint8_t* corrected, KcResult* results, uint32_t* broken, DevCounters* ctr,
+                               hipStream_t stream);
 hipError_t launch_bwt_chars(const FmIndexDev& fm, int strand, const uint64_t* idx, uint64_t n, char* out,
                             hipStream_t stream);
 hipError_t launch_find_kmers(const FmIndexDev& fm, const uint8_t* kmer_codes, uint32_t k, uint64_t n,

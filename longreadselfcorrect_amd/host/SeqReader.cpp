@@ -20,7 +20,7 @@ static void openFailure(const std::string& filename)
     exit(EXIT_FAILURE);
 }
 
-SeqReader::SeqReader(const std::string& filename)
+SeqReader::SeqReader(const std::string& filename, bool acceptOtherBases) : m_acceptOtherBases(acceptOtherBases)
 {
     const bool gz = filename.size() > 3 && filename.compare(filename.size() - 3, 3, ".gz") == 0;
     if(gz) {
@@ -137,7 +137,7 @@ bool SeqReader::get(SeqRecord& sr)
             *d++ = u;
             bad |= (unsigned)!(u == 'A' || u == 'C' || u == 'G' || u == 'T');
         }
-    if(bad) {
+    if(bad && !m_acceptOtherBases) {
         std::cerr << "Error: read " << sr.id << " contains non-ACGT characters.\n";
         std::cerr << "Please run sga preprocess on the data first.\n";
         exit(EXIT_FAILURE);

@@ -27,10 +27,11 @@ struct SequenceWorkItem {
 //     without a newline is not part of it; a record without sequence ends the input;
 //   * FASTQ: sequence, separator and quality line; a record whose quality line hits the end of the input without a
 //     newline is dropped; a warning if sequence or quality is empty;
-//   * the sequence is upper-cased, and a base other than ACGT is a fatal error (message + exit).
+//   * the sequence is upper-cased, and a base other than ACGT is a fatal error (message + exit), unless the reader was made
+//     with acceptOtherBases: `stride correct` passes such reads through.
 class SeqReader {
 public:
-    explicit SeqReader(const std::string& filename);
+    explicit SeqReader(const std::string& filename, bool acceptOtherBases = false);
     ~SeqReader();
     SeqReader(const SeqReader&) = delete;
     SeqReader& operator=(const SeqReader&) = delete;
@@ -43,6 +44,7 @@ private:
     size_t m_size = 0, m_pos = 0;
     bool m_good = true;                            // the stream's good(): cleared once a read ran into the end of the input
     bool m_mapped = false;
+    bool m_acceptOtherBases = false;
     std::vector<char> m_owned;                     // inflated .gz contents
     std::vector<Span> m_lines;                     // sequence lines of the record being cut
 };

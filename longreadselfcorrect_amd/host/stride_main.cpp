@@ -1,5 +1,5 @@
 // stride_main.cpp -- `stride pbcorrect` (a.k.a. PacBioSelfCorrection), `stride index`, `stride merge`, `stride sai`,
-// `stride grep` and `stride filter` on the MI355X back end.  Option surface, defaults, validation messages and exit codes follow the reference's
+// `stride grep`, `stride filter` and `stride correct` on the MI355X back end.  Option surface, defaults, validation messages and exit codes follow the reference's
 // StriDe/PacBioSelfCorrection.cpp:32-140,262-434 and StriDe/StriDe.cpp:62-126; extra flags: --devices, --batch.
 #include <getopt.h>
 
@@ -16,6 +16,7 @@
 
 #include "../../include/lrsc.h"
 #include "BCode.h"
+#include "ErrorCorrectProcess.h"
 #include "LexicoOrder.h"
 #include "PacBioSelfCorrectionProcess.h"
 #include "QCProcess.h"
@@ -768,19 +769,209 @@ static int filterMain(int argc, char** argv)
     return 0;
 }
 
+// `stride correct -a kmer READSFILE`: the reference's correct (StriDe/correct.cpp:44-78,145-258,312-465) with the k-mer algorithm
+// (ErrorCorrectProcess::kmerCorrection) run on the device, a batch of reads per lrsc_kmer_correct call.  The overlap and hybrid
+// algorithms are not built, and neither is --learn: it samples the index with rand() seeded from the clock.
+static const char* KCORRECT_USAGE_MESSAGE =
+    "Usage: " PACKAGE_NAME " correct [OPTION] ... READSFILE\n"
+    "Correct sequencing errors in all the reads in READSFILE\n"
+    "\n"
+    "      --help                           display this help and exit\n"
+    "      -v, --verbose                    display verbose output\n"
+    "      -p, --prefix=PREFIX              use PREFIX for the names of the index files (default: prefix of the input file)\n"
+    "      --build-index                    index READSFILE in memory on the device instead of loading PREFIX.bwt/.rbwt\n"
+    "      -o, --outfile=FILE               write the corrected reads to FILE (default: READSFILE.ec.fa)\n"
+    "      -t, --threads=NUM                use NUM threads for the computation (default: 1)\n"
+    "          --discard                    detect and discard low-quality reads\n"
+    "      -d, --sample-rate=N              use occurrence array sample rate of N in the FM-index. Higher values use significantly\n"
+    "                                       less memory at the cost of higher runtime. This value must be a power of 2 (default: 128)\n"
+    "      -a, --algorithm=STR              specify the correction algorithm to use. STR must be one of kmer, hybrid, overlap. (default: kmer)\n"
+    "          --metrics=FILE               collect error correction metrics (error rate by position in read, etc) and write them to FILE\n"
+    "      --device=N                       HIP device to work on (default: 0)\n"
+    "\nKmer correction parameters:\n"
+    "      -k, --kmer-size=N                The length of the kmer to use. (default: 31)\n"
+    "      -x, --kmer-threshold=N           Attempt to correct kmers that are seen less than N times. (default: 3)\n"
+    "      -i, --kmer-rounds=N              Perform N rounds of k-mer correction, correcting up to N bases (default: 10)\n"
+    "          --learn                      Attempt to learn the k-mer correction threshold (experimental). Overrides -x parameter.\n"
+    "\nOverlap correction parameters:\n"
+    "      -e, --error-rate                 the maximum error rate allowed between two sequences to consider them overlapped (default: 0.04)\n"
+    "      -m, --min-overlap=LEN            minimum overlap required between two reads (default: 45)\n"
+    "      -c, --conflict=INT               use INT as the threshold to detect a conflicted base in the multi-overlap (default: 5)\n"
+    "      -l, --seed-length=LEN            force the seed length to be LEN. By default, the seed length in the overlap step\n"
+    "                                       is calculated to guarantee all overlaps with --error-rate differences are found.\n"
+    "                                       This option removes the guarantee but will be (much) faster. As SGA can tolerate some\n"
+    "                                       missing edges, this option may be preferable for some data sets.\n"
+    "      -s, --seed-stride=LEN            force the seed stride to be LEN. This parameter will be ignored unless --seed-length\n"
+    "                                       is specified (see above). This parameter defaults to the same value as --seed-length\n"
+    "      -b, --branch-cutoff=N            stop the overlap search at N branches. This parameter is used to control the search time for\n"
+    "                                       highly-repetitive reads. If the number of branches exceeds N, the search stops and the read\n"
+    "                                       will not be corrected. This is not enabled by default.\n"
+    "      -r, --rounds=NUM                 iteratively correct reads up to a maximum of NUM rounds (default: 1)\n"
+    "\nReport bugs to " PACKAGE_BUGREPORT "\n\n";
+
+namespace correctopt {
+static unsigned int verbose = 0;
+static int numThreads = 1, numOverlapRounds = 1, sampleRate = 128, seedLength = 0, seedStride = 0, conflictCutoff = 3, branchCutoff = -1;
+static int kmerLength = 31, kmerThreshold = 3, numKmerRounds = 10, device = 0;
+static unsigned int minOverlap = 45;
+static double errorRate = 0.04;
+static std::string prefix, readsFile, outFile, discardFile, metricsFile;
+static bool buildIndex = false;
+static const size_t batch = 100000;                             // reads per device call
+}
+
+static void parseCorrectOptions(int argc, char** argv)
+{
+    enum { C_HELP = 1, C_VERSION, C_METRICS, C_DISCARD, C_LEARN, C_DIPLOID, C_DEVICE, C_BUILDINDEX };
+    static const struct option correct_longopts[] = {
+        {"verbose", no_argument, nullptr, 'v'},               {"threads", required_argument, nullptr, 't'},
+        {"min-overlap", required_argument, nullptr, 'm'},     {"rounds", required_argument, nullptr, 'r'},
+        {"outfile", required_argument, nullptr, 'o'},         {"prefix", required_argument, nullptr, 'p'},
+        {"error-rate", required_argument, nullptr, 'e'},      {"seed-length", required_argument, nullptr, 'l'},
+        {"seed-stride", required_argument, nullptr, 's'},     {"algorithm", required_argument, nullptr, 'a'},
+        {"sample-rate", required_argument, nullptr, 'd'},     {"conflict", required_argument, nullptr, 'c'},
+        {"branch-cutoff", required_argument, nullptr, 'b'},   {"kmer-size", required_argument, nullptr, 'k'},
+        {"kmer-threshold", required_argument, nullptr, 'x'},  {"kmer-rounds", required_argument, nullptr, 'i'},
+        {"learn", no_argument, nullptr, C_LEARN},             {"discard", no_argument, nullptr, C_DISCARD},
+        {"help", no_argument, nullptr, C_HELP},               {"version", no_argument, nullptr, C_VERSION},
+        {"metrics", required_argument, nullptr, C_METRICS},   {"diploid", no_argument, nullptr, C_DIPLOID},
+        {"device", required_argument, nullptr, C_DEVICE},     {"build-index", no_argument, nullptr, C_BUILDINDEX},
+        {nullptr, 0, nullptr, 0}};
+    optind = 1;
+    std::string algo_str;
+    bool discardReads = false, learn = false, die = false;
+    for(int c; (c = getopt_long(argc, argv, "p:m:d:e:t:l:s:o:r:b:a:c:k:x:i:v", correct_longopts, nullptr)) != -1;) {
+        std::istringstream arg(optarg != nullptr ? optarg : "");
+        switch(c) {
+            case 'm': arg >> correctopt::minOverlap; break;
+            case 'p': arg >> correctopt::prefix; break;
+            case 'o': arg >> correctopt::outFile; break;
+            case 'e': arg >> correctopt::errorRate; break;
+            case 't': arg >> correctopt::numThreads; break;
+            case 'l': arg >> correctopt::seedLength; break;
+            case 's': arg >> correctopt::seedStride; break;
+            case 'r': arg >> correctopt::numOverlapRounds; break;
+            case 'a': arg >> algo_str; break;
+            case 'd': arg >> correctopt::sampleRate; break;
+            case 'c': arg >> correctopt::conflictCutoff; break;
+            case 'k': arg >> correctopt::kmerLength; break;
+            case 'x': arg >> correctopt::kmerThreshold; break;
+            case 'v': correctopt::verbose++; break;
+            case 'b': arg >> correctopt::branchCutoff; break;
+            case 'i': arg >> correctopt::numKmerRounds; break;
+            case C_LEARN: learn = true; break;
+            case C_DISCARD: discardReads = true; break;
+            case C_METRICS: arg >> correctopt::metricsFile; break;
+            case C_DIPLOID: break;                                // read by the overlap algorithm only
+            case C_DEVICE: arg >> correctopt::device; break;
+            case C_BUILDINDEX: correctopt::buildIndex = true; break;
+            case C_HELP: std::cout << KCORRECT_USAGE_MESSAGE; exit(EXIT_SUCCESS);
+            case C_VERSION: std::cout << "correct Version " PACKAGE_VERSION " (MI355X back end)\n"; exit(EXIT_SUCCESS);
+            default: die = true; break;
+        }
+    }
+    if(argc - optind < 1) { std::cerr << "correct: missing arguments\n"; die = true; }
+    else if(argc - optind > 1) { std::cerr << "correct: too many arguments\n"; die = true; }
+    if(correctopt::numThreads <= 0) { std::cerr << "correct: invalid number of threads: " << correctopt::numThreads << "\n"; die = true; }
+    if(correctopt::numOverlapRounds <= 0) { std::cerr << "correct: invalid number of overlap rounds: " << correctopt::numOverlapRounds << ", must be at least 1\n"; die = true; }
+    if(correctopt::numKmerRounds <= 0) { std::cerr << "correct: invalid number of kmer rounds: " << correctopt::numKmerRounds << ", must be at least 1\n"; die = true; }
+    if(correctopt::kmerLength <= 0) { std::cerr << "correct: invalid kmer length: " << correctopt::kmerLength << ", must be greater than zero\n"; die = true; }
+    if(correctopt::kmerThreshold <= 0) { std::cerr << "correct: invalid kmer threshold: " << correctopt::kmerThreshold << ", must be greater than zero\n"; die = true; }
+    if(algo_str.empty()) {
+        // the reference starts from the overlap algorithm, whatever its usage text says of the default
+        std::cerr << "correct: without -a the reference runs its overlap algorithm, which is not built here: say -a kmer\n";
+        die = true;
+    } else if(algo_str == "hybrid" || algo_str == "overlap") {
+        std::cerr << "correct: -a " << algo_str << " is not built here: only -a kmer is\n";
+        die = true;
+    } else if(algo_str != "kmer") {
+        std::cerr << "correct: unrecognized -a,--algorithm parameter: " << algo_str << "\n";
+        die = true;
+    }
+    if(learn) { std::cerr << "correct: --learn is not built here (it samples the index at random, seeded from the clock): set -x\n"; die = true; }
+    if(die) { std::cout << "\n" << KCORRECT_USAGE_MESSAGE; exit(EXIT_FAILURE); }
+    if(correctopt::errorRate > 1.0f) { std::cerr << "Invalid error-rate parameter: " << correctopt::errorRate << "\n"; exit(EXIT_FAILURE); }
+    correctopt::readsFile = argv[optind++];
+    if(correctopt::prefix.empty()) correctopt::prefix = getFilename(correctopt::readsFile);
+    const std::string out_prefix = getFilename(correctopt::readsFile);
+    if(correctopt::outFile.empty()) correctopt::outFile = out_prefix + ".ec.fa";
+    correctopt::discardFile = discardReads ? out_prefix + ".discard.fa" : std::string();
+}
+
+static int correctMain(int argc, char** argv)
+{
+    parseCorrectOptions(argc, argv);
+    const int device = correctopt::device;
+    std::cout << "Correcting sequencing errors for " << correctopt::readsFile << "\n";
+    lrsc_index* idx = nullptr;
+    if(correctopt::buildIndex) {
+        std::string bases;
+        std::vector<uint64_t> off;
+        loadReads(correctopt::readsFile, bases, off);
+        lrscOrDie(lrsc_index_build(bases.data(), off.data(), (uint32_t)(off.size() - 1), device, &idx), "lrsc_index_build");
+    } else {
+        std::cout << "Loading BWT: " << correctopt::prefix + BWT_EXT << " and " << correctopt::prefix + RBWT_EXT << std::endl;
+        lrscOrDie(lrsc_index_open_device((correctopt::prefix + BWT_EXT).c_str(), (correctopt::prefix + RBWT_EXT).c_str(), device, &idx), "lrsc_index_open_device");
+    }
+    lrsc_ctx* ctx = nullptr;
+    lrscOrDie(lrsc_ctx_create(idx, nullptr, device, &ctx), "lrsc_ctx_create");
+
+    ErrorCorrectParameters params;
+    params.ctx = ctx;
+    params.kmerLength = correctopt::kmerLength;
+    params.kmerThreshold = correctopt::kmerThreshold;
+    params.numKmerRounds = correctopt::numKmerRounds;
+    params.readsFile = correctopt::readsFile;
+    std::cout << "Perform error correction using" << std::endl
+              << "kmer size=" << params.kmerLength << std::endl
+              << "kmer threshold=" << correctopt::kmerThreshold << std::endl
+              << "overlap rounds=" << correctopt::numOverlapRounds << std::endl;
+    {
+        std::ofstream writer(correctopt::outFile.c_str()), discard;
+        if(!correctopt::discardFile.empty()) discard.open(correctopt::discardFile.c_str());
+        if(!writer || (!correctopt::discardFile.empty() && !discard)) {
+            std::cerr << "Error: could not open " << correctopt::outFile << (correctopt::discardFile.empty() ? "" : " / " + correctopt::discardFile) << " for write\n";
+            return EXIT_FAILURE;
+        }
+        const bool collectMetrics = !correctopt::metricsFile.empty();
+        ErrorCorrectProcess processor(params);
+        ErrorCorrectPostProcess post(&writer, correctopt::discardFile.empty() ? nullptr : &discard, collectMetrics);
+        SeqReader reader(correctopt::readsFile, true);
+        WorkItemGenerator<SequenceWorkItem> generator(&reader);
+        std::vector<SequenceWorkItem> items;
+        for(bool more = true; more;) {
+            items.clear();
+            SequenceWorkItem item;
+            while(items.size() < correctopt::batch && (more = generator.generate(item))) items.push_back(item);
+            const std::vector<ErrorCorrectResult> results = processor.process_batch(items);
+            for(size_t i = 0; i < items.size(); ++i) post.process(items[i], results[i]);
+        }
+        if(collectMetrics) {
+            std::ofstream metrics(correctopt::metricsFile.c_str());
+            if(!metrics) { std::cerr << "Error: could not open " << correctopt::metricsFile << " for write\n"; return EXIT_FAILURE; }
+            post.writeMetrics(&metrics);
+        }
+    }                                                             // the counters are printed here
+    std::cout.flush();
+    lrsc_ctx_destroy(ctx);
+    lrsc_index_close(idx);
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
     // several workers on one device (--devices 0,0) only overlap if their streams get hardware queues of their own (default: 4)
     setenv("GPU_MAX_HW_QUEUES", "16", 0);
-    if(argc <= 1) { std::cerr << "Usage: " PACKAGE_NAME " <command> [options]\nCommands: index, merge, sai, grep, filter, pbcorrect, kmerfreq, kmercheck\n"; return EXIT_FAILURE; }
+    if(argc <= 1) { std::cerr << "Usage: " PACKAGE_NAME " <command> [options]\nCommands: index, merge, sai, grep, filter, correct, pbcorrect, kmerfreq, kmercheck\n"; return EXIT_FAILURE; }
     const std::string command(argv[1]);
-    if(command == "help" || command == "--help") { std::cout << "Usage: " PACKAGE_NAME " <command> [options]\nCommands: index, merge, sai, grep, filter, pbcorrect, kmerfreq, kmercheck\n"; return 0; }
+    if(command == "help" || command == "--help") { std::cout << "Usage: " PACKAGE_NAME " <command> [options]\nCommands: index, merge, sai, grep, filter, correct, pbcorrect, kmerfreq, kmercheck\n"; return 0; }
     if(command == "pbcorrect" || command == SUBPROGRAM) return PacBioSelfCorrectionMain(argc - 1, argv + 1);
     if(command == "index") return indexMain(argc - 1, argv + 1);
     if(command == "merge") return mergeMain(argc - 1, argv + 1);
     if(command == "sai") return saiMain(argc - 1, argv + 1);
     if(command == "grep") return grepMain(argc - 1, argv + 1);
     if(command == "filter") return filterMain(argc - 1, argv + 1);
+    if(command == "correct") return correctMain(argc - 1, argv + 1);
     if(command == "kmerfreq") return kmerfreqMain(argc - 1, argv + 1);
     if(command == "kmercheck") return kmercheckMain(argc - 1, argv + 1);
     std::cerr << "Unrecognized command: " << command << "\n";
