@@ -254,6 +254,39 @@ int lrsc_kmer_correct(lrsc_ctx* ctx, const char* reads, const uint64_t* read_off
                       const uint8_t* phred /* one per base, NULL = 15 everywhere */,
                       const lrsc_kcorrect_params* p, char* corrected /* same offsets as reads */, lrsc_kcorrect_result* out);
 
+/* ---- paired-end reads merged by an FM-index walk: `stride fmwalk -a merge` (FMIndexWalk/FMIndexWalkProcess.cpp:153-226, 825-870;
+ * FMIndexWalk/SAIntervalTree.cpp:20-56, 103-170, 248-449, 494-507) ---------------------------------------------------------- */
+typedef struct lrsc_fmwalk_params { int32_t kmer_length, kmer_threshold, min_overlap, max_overlap /* -1: from the lengths */, max_insert, max_leaves; } lrsc_fmwalk_params; /* -k 31 -x 3 -m 81 -M -1 -I 400 -L 32 */
+typedef struct lrsc_fmwalk_result { uint32_t merged, length; int32_t status[2]; uint32_t max_used_leaves[2]; uint64_t coverage[2]; uint32_t trimmed_length[2]; } lrsc_fmwalk_result;
+/* The kernel's limits: LRSC_ERR_UNSUPPORTED above them. */
+#define LRSC_FMWALK_MAX_LEAVES 64
+#define LRSC_FMWALK_MAX_INSERT 2000
+#define LRSC_FMWALK_MAX_MIN_OVERLAP 255
+#define LRSC_FMWALK_MAX_KMER 255
+/* FMIndexWalkProcess::MergePairedReads for n_pairs pairs against the ctx's index, reads 2i and 2i + 1 (concatenated ACGT bytes,
+ * 2 * n_pairs + 1 offsets) being pair i; the result is that of the reference's serial run, byte for byte.  Both reads are trimmed
+ * (trimRead: a head or tail kmer_length-mer that no base extends outwards is cut back to the first position that two or more
+ * bases extend); a pair with a trimmed read shorter than min_overlap is not merged, status = {0, 0}.  Otherwise two walks
+ * (SAIntervalTree::mergeTwoReads) go from the first min_overlap bases of one trimmed read to the reverse complement of the
+ * other's, walk 0 from the first read and walk 1 from the second: a breadth-first frontier of at most max_leaves leaves that
+ * extends by every base whose k-mer occurs kmer_threshold times on both strands together, the k-mer growing from min_overlap to
+ * max_overlap (-1: 0.9 * the mean of the two untrimmed lengths) and falling back, until a leaf's interval lies within the
+ * target's or the string is longer than max_insert.  Of a walk's results the one with the strictly greatest coverage (the sum
+ * of the occurrences of its min_overlap-mers at stride min_overlap / 2) is its string.  The pair is merged when one walk has a
+ * string, or both have one of the same length (then walk 0's if its coverage is greater, else walk 1's, which reads on the other
+ * strand).
+ * out[i]: merged, the string's length, and per walk status (1 found, -1 the frontier emptied, -2 depth, -3 leaves, -4 otherwise),
+ * max_used_leaves, coverage (getKmerCoverage()); trimmed_length per read.  A read shorter than kmer_length, on which the
+ * reference throws, leaves its pair unmerged with trimmed_length 0.  merged + i * stride holds pair i's string when it is merged
+ * and is not written otherwise.
+ * LRSC_ERR_ARG for a parameter <= 0 other than max_overlap == -1, min_overlap < 2, an empty read, a base other than A,C,G,T and
+ * a stride below max(max_insert + 1, min_overlap); LRSC_ERR_UNSUPPORTED above the limits; LRSC_ERR_FORMAT when an interval leaves
+ * the strand (an index that is no BWT of a string set); on an error merged and out are untouched.  n_pairs == 0 does nothing.  The
+ * launches are counted under LRSC_K_FIND; a backward-search step is two of its rank_queries. */
+int lrsc_fmwalk_merge(lrsc_ctx* ctx, const char* reads, const uint64_t* read_off, uint32_t n_pairs /* reads 2i, 2i+1 */,
+                      const lrsc_fmwalk_params* p, char* merged /* n_pairs * stride */, uint64_t stride /* >= max(max_insert + 1, min_overlap) */,
+                      lrsc_fmwalk_result* out);
+
 /* ---- LongReadProbe k-mer feature grid -------------------------------------------------- */
 /* reads: concatenated ACGT bytes, read_off: n_reads+1 offsets.  ks: ascending k-mer sizes
  * (the "pool", e.g. {5,9,15,17,19}), n_k <= 8.  For read r, position p, pool slot j the record

@@ -197,6 +197,8 @@ SA_DTYPE = np.dtype([("read", "<u4"), ("pos", "<u4")])          # lrsc_sa_elem
 DUP_DTYPE = np.dtype([("fwd_lower", "<i8"), ("fwd_upper", "<i8"), ("rvc_lower", "<i8"), ("rvc_upper", "<i8"), ("cls", "<i4"), ("pad", "<u4")])
 DUP_UNIQUE, DUP_SUBSTRING, DUP_FULL_LENGTH, DUP_ABSENT = range(4)
 KCORRECT_DTYPE = np.dtype([("kmer_qc", "<u4"), ("n_changed", "<u4"), ("passes", "<u4"), ("pad", "<u4")])      # lrsc_kcorrect_result
+FMWALK_DTYPE = np.dtype([("merged", "<u4"), ("length", "<u4"), ("status", "<i4", (2,)), ("max_used_leaves", "<u4", (2,)), ("coverage", "<u8", (2,)),
+                         ("trimmed_length", "<u4", (2,))], align=True)      # lrsc_fmwalk_result
 assert RANK_DTYPE.itemsize == C.sizeof(RankQuery) and BIIV_DTYPE.itemsize == C.sizeof(BiInterval)
 
 
@@ -256,6 +258,7 @@ class Lrsc:
         L.lrsc_dupcheck_destroy.restype = None
         L.lrsc_index_remove.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]
         L.lrsc_kmer_correct.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.lrsc_fmwalk_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         L.lrsc_params_default.argtypes = [C.c_int, C.c_int, C.POINTER(Params)]
         L.lrsc_ctx_create.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int, C.POINTER(C.c_void_p)]
         L.lrsc_ctx_destroy.argtypes = [C.c_void_p]
@@ -539,6 +542,22 @@ class Ctx:
         self.api.check(self.api.lib.lrsc_kmer_correct(self.h, _ptr(bases), _ptr(off), off.size - 1, None if phred is None else _ptr(phred), _ptr(params),
                                                       _ptr(corrected), _ptr(out)), "lrsc_kmer_correct")
         return corrected, out
+
+    def fmwalk_merge(self, bases: np.ndarray, off: np.ndarray, kmer_length: int = 31, kmer_threshold: int = 3, min_overlap: int = 81, max_overlap: int = -1,
+                     max_insert: int = 400, max_leaves: int = 32, stride: int | None = None):
+        """lrsc_fmwalk_merge of the pairs (ASCII bases, 2 * n_pairs + 1 offsets, reads 2i and 2i + 1 being pair i) -> (the merged
+        strings, one row of `stride` bytes per pair, zero where nothing was written; FMWALK_DTYPE per pair)."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        assert off.size % 2 == 1
+        n_pairs = (off.size - 1) // 2
+        if stride is None:
+            stride = max(max_insert + 1, min_overlap, 1)
+        params = np.array([kmer_length, kmer_threshold, min_overlap, max_overlap, max_insert, max_leaves], dtype=np.int32)
+        merged = np.zeros((n_pairs, stride), dtype=np.uint8)
+        out = np.zeros(n_pairs, dtype=FMWALK_DTYPE)
+        self.api.check(self.api.lib.lrsc_fmwalk_merge(self.h, _ptr(bases), _ptr(off), n_pairs, _ptr(params), _ptr(merged), stride, _ptr(out)), "lrsc_fmwalk_merge")
+        return merged, out
 
     def rank(self, bases: np.ndarray, idx: np.ndarray, strand: np.ndarray | int) -> np.ndarray:
         n = len(idx)

@@ -178,6 +178,9 @@ struct lrsc_ctx {
     lrsc::DevBuf<uint8_t> kc_ws;
     lrsc::DevBuf<uint64_t> kc_ws_off;
     lrsc::DevBuf<lrsc_kcorrect_result> kc_res;
+    // lrsc_fmwalk_merge's: the wavefronts' workspace, the walks' start and end strings, their strings, the trimmed lengths
+    lrsc::DevBuf<uint8_t> fw_ws, fw_strs, fw_best, fw_outs;
+    lrsc::DevBuf<uint32_t> fw_trimmed;
     ~lrsc_ctx();                                        // drains the stream, then frees cs and the ctx's own objects (capi_correct.cpp)
 };
 

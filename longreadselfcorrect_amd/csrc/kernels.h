@@ -117,6 +117,20 @@ struct KcResult;
 hipError_t launch_kmer_correct(const FmIndexDev& fm, const uint8_t* codes, const uint64_t* read_off, const uint8_t* phred, uint32_t n, const KcParams& p,
                                uint8_t* ws, const uint64_t* ws_off, uint8_t* corrected, KcResult* results, uint32_t* broken, DevCounters* ctr,
                                hipStream_t stream);
+// The merge of n_pairs paired-end reads (fm_fmwalk.hip), reads 2i and 2i + 1 of codes / read_off being pair i.
+// launch_fmwalk_trim, a wavefront per pair: trimmed[2i], [2i + 1] = the trimmed lengths, and where both reach min_overlap
+// strs + i * 4 * m4 (m4 = min_overlap rounded up to a multiple of 4) = the four strings of the pair's walks.
+// launch_fmwalk_walks, a wavefront per walk, walk 2i + w being pair i's walk w: `groups` workgroups of kFwThreads, every wavefront
+// with its own ws_slice >= fw_workspace_bytes(p) bytes of ws, take the walks in turn; outs[walk] = its code, length, leaves and
+// coverage (zeros for a pair the gate stopped), best + walk * stride = its string's codes.
+// *broken is set to 1 when an interval leaves the strand.
+struct FwParams;
+struct FwWalkOut;
+hipError_t launch_fmwalk_trim(const FmIndexDev& fm, const uint8_t* codes, const uint64_t* read_off, uint32_t n_pairs, const FwParams& p, uint8_t* strs,
+                              uint32_t* trimmed, uint32_t* broken, DevCounters* ctr, hipStream_t stream);
+hipError_t launch_fmwalk_walks(const FmIndexDev& fm, const uint64_t* read_off, uint32_t n_pairs, const FwParams& p, const uint8_t* strs, const uint32_t* trimmed,
+                               uint32_t groups, uint8_t* ws, uint64_t ws_slice, uint8_t* best, uint64_t stride, FwWalkOut* outs, uint32_t* broken, DevCounters* ctr,
+                               hipStream_t stream);
 hipError_t launch_bwt_chars(const FmIndexDev& fm, int strand, const uint64_t* idx, uint64_t n, char* out,
                             hipStream_t stream);
 hipError_t launch_find_kmers(const FmIndexDev& fm, const uint8_t* kmer_codes, uint32_t k, uint64_t n,

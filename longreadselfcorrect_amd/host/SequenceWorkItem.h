@@ -19,6 +19,10 @@ struct SequenceWorkItem {
     SeqRecord read;
 };
 
+struct SequenceWorkItemPair {            // two consecutive records: the ends of a fragment
+    SequenceWorkItem first, second;
+};
+
 // FASTA (multi-line allowed) / FASTQ, plain or gzip (.gz, Util/Util.cpp:276-309).  The whole input is one memory block
 // (mmap for plain files, inflated once for .gz) and records are cut out of it with memchr: no stream, no per-line string.
 // Record rules = the reference's (Util/SeqReader.cpp:26-135), including its corner cases:
@@ -58,6 +62,14 @@ public:
         if(!m_pReader->get(out.read)) return false;
         out.idx = m_numConsumedTotal;
         m_numConsumedTotal += 1;
+        return true;
+    }
+    // Two consecutive records.  False at the end of the input; *odd is set when the input ends after a first record (the
+    // reference asserts there).
+    bool generate(SequenceWorkItemPair& out, bool* odd)
+    {
+        if(!generate(out.first)) return false;
+        if(!generate(out.second)) { *odd = true; return false; }
         return true;
     }
     size_t getNumConsumed() const { return m_numConsumedTotal; }

@@ -1,5 +1,5 @@
 // stride_main.cpp -- `stride pbcorrect` (a.k.a. PacBioSelfCorrection), `stride index`, `stride merge`, `stride sai`,
-// `stride grep`, `stride filter` and `stride correct` on the MI355X back end.  Option surface, defaults, validation messages and exit codes follow the reference's
+// `stride grep`, `stride filter`, `stride correct` and `stride fmwalk` on the MI355X back end.  Option surface, defaults, validation messages and exit codes follow the reference's
 // StriDe/PacBioSelfCorrection.cpp:32-140,262-434 and StriDe/StriDe.cpp:62-126; extra flags: --devices, --batch.
 #include <getopt.h>
 
@@ -17,6 +17,7 @@
 #include "../../include/lrsc.h"
 #include "BCode.h"
 #include "ErrorCorrectProcess.h"
+#include "FMIndexWalkProcess.h"
 #include "LexicoOrder.h"
 #include "PacBioSelfCorrectionProcess.h"
 #include "QCProcess.h"
@@ -958,13 +959,169 @@ static int correctMain(int argc, char** argv)
     return 0;
 }
 
+// `stride fmwalk -a merge READSFILE`: the reference's FMIndexWalk (StriDe/FMIndexWalk.cpp:40-58,112-238,244-362) with the merge
+// algorithm (FMIndexWalkProcess::MergePairedReads) run on the device, a batch of pairs per lrsc_fmwalk_merge call.  The kmerize,
+// validate and hybrid algorithms are not built.  Not taken over: the empty kmerized.fa that the reference opens and never writes
+// in merge mode, and the `Median kmer frequency` line, which comes from 100000 rand() samples that merge mode does not use.
+static const char* FMWALK_USAGE_MESSAGE =
+    "Usage: " PACKAGE_NAME " FMIndexWalk [OPTION] ... READSFILE\n"
+    "Merge paired end reads into long reads via FM-index walk\n"
+    "\n"
+    "      --help                           display this help and exit\n"
+    "      -v, --verbose                    display verbose output\n"
+    "      -p, --prefix=PREFIX              use PREFIX for the names of the index files (default: prefix of the input file)\n"
+    "      --build-index                    index READSFILE in memory on the device instead of loading PREFIX.bwt/.rbwt\n"
+    "      --load-on-device                 decode PREFIX.bwt/.rbwt on the device (what loading does here; accepted for symmetry)\n"
+    "      -o, --outfile=FILE               write the corrected reads to FILE (default: READSFILE.ec.fa)\n"
+    "      -t, --threads=NUM                use NUM threads for the computation (default: 1)\n"
+    "      -a, --algorithm=STR              specify the walking algorithm (hybrid (default), merge, kmerize, or validate)\n"
+    "      --device=N                       HIP device to work on (default: 0)\n"
+    "\nAlgorithm parameters:\n"
+    "      -k, --kmer-size=N                The length of the kmer to use. (default: 31)\n"
+    "      -x, --kmer-threshold=N           Attempt to correct kmers that are seen less than N times. (default: 3)\n"
+    "      -L, --max-leaves=N               Number of maximum leaves in the search tree (default: 32)\n"
+    "      -I, --max-insertsize=N           the maximum insert size (i.e. search depth) (deault: 400)\n"
+    "      -m, --min-overlap=N           the min overlap (default: 81)\n"
+    "      -M, --max-overlap=N           the max overlap (default: avg read length*0.9)\n"
+    "\nReport bugs to " PACKAGE_BUGREPORT "\n\n";
+
+namespace fmwalkopt {
+static unsigned int verbose = 0;
+static int numThreads = 1, kmerLength = 31, kmerThreshold = 3, maxLeaves = 32, maxInsertSize = 400, minOverlap = 81, maxOverlap = -1, device = 0;
+static std::string prefix, readsFile, outFile;
+static bool buildIndex = false;
+static const size_t batch = 100000;                             // pairs per device call
+}
+
+static void parseFMWalkOptions(int argc, char** argv)
+{
+    enum { F_HELP = 1, F_VERSION, F_METRICS, F_DISCARD, F_LEARN, F_DEVICE, F_BUILDINDEX, F_LOADONDEVICE };
+    static const struct option fmwalk_longopts[] = {
+        {"verbose", no_argument, nullptr, 'v'},               {"threads", required_argument, nullptr, 't'},
+        {"outfile", required_argument, nullptr, 'o'},         {"prefix", required_argument, nullptr, 'p'},
+        {"algorithm", required_argument, nullptr, 'a'},       {"kmer-size", required_argument, nullptr, 'k'},
+        {"kmer-threshold", required_argument, nullptr, 'x'},  {"max-leaves", required_argument, nullptr, 'L'},
+        {"max-insertsize", required_argument, nullptr, 'I'},  {"min-overlap", required_argument, nullptr, 'm'},
+        {"max-overlap", required_argument, nullptr, 'M'},     // the reference's table lacks it, its usage text names it
+        {"learn", no_argument, nullptr, F_LEARN},             {"discard", no_argument, nullptr, F_DISCARD},
+        {"help", no_argument, nullptr, F_HELP},               {"version", no_argument, nullptr, F_VERSION},
+        {"metrics", required_argument, nullptr, F_METRICS},   {"device", required_argument, nullptr, F_DEVICE},
+        {"build-index", no_argument, nullptr, F_BUILDINDEX},  {"load-on-device", no_argument, nullptr, F_LOADONDEVICE},
+        {nullptr, 0, nullptr, 0}};
+    optind = 1;
+    std::string algo_str;
+    bool die = false;
+    for(int c; (c = getopt_long(argc, argv, "p:t:o:a:k:x:L:I:m:M:v", fmwalk_longopts, nullptr)) != -1;) {
+        std::istringstream arg(optarg != nullptr ? optarg : "");
+        switch(c) {
+            case 'p': arg >> fmwalkopt::prefix; break;
+            case 'o': arg >> fmwalkopt::outFile; break;
+            case 't': arg >> fmwalkopt::numThreads; break;
+            case 'a': arg >> algo_str; break;
+            case 'k': arg >> fmwalkopt::kmerLength; break;
+            case 'x': arg >> fmwalkopt::kmerThreshold; break;
+            case 'v': fmwalkopt::verbose++; break;
+            case 'L': arg >> fmwalkopt::maxLeaves; break;
+            case 'I': arg >> fmwalkopt::maxInsertSize; break;
+            case 'm': arg >> fmwalkopt::minOverlap; break;
+            case 'M': arg >> fmwalkopt::maxOverlap; break;
+            case F_LEARN: case F_DISCARD: case F_METRICS: case F_LOADONDEVICE: break;     // read and not used, as in the reference
+            case F_DEVICE: arg >> fmwalkopt::device; break;
+            case F_BUILDINDEX: fmwalkopt::buildIndex = true; break;
+            case F_HELP: std::cout << FMWALK_USAGE_MESSAGE; exit(EXIT_SUCCESS);
+            case F_VERSION: std::cout << "FMIndexWalk Version " PACKAGE_VERSION " (MI355X back end)\n"; exit(EXIT_SUCCESS);
+            default: die = true; break;
+        }
+    }
+    if(argc - optind < 1) { std::cerr << "FMIndexWalk: missing arguments\n"; die = true; }
+    else if(argc - optind > 1) { std::cerr << "FMIndexWalk: too many arguments\n"; die = true; }
+    if(fmwalkopt::numThreads <= 0) { std::cerr << "FMIndexWalk: invalid number of threads: " << fmwalkopt::numThreads << "\n"; die = true; }
+    if(fmwalkopt::kmerLength <= 0) { std::cerr << "FMIndexWalk: invalid kmer length: " << fmwalkopt::kmerLength << ", must be greater than zero\n"; die = true; }
+    if(fmwalkopt::kmerThreshold <= 0) { std::cerr << "FMIndexWalk: invalid kmer threshold: " << fmwalkopt::kmerThreshold << ", must be greater than zero\n"; die = true; }
+    if(algo_str.empty()) {
+        std::cerr << "FMIndexWalk: without -a the reference runs its hybrid algorithm, which is not built here: say -a merge\n";
+        die = true;
+    } else if(algo_str == "hybrid" || algo_str == "kmerize" || algo_str == "validate") {
+        std::cerr << "FMIndexWalk: -a " << algo_str << " is not built here: only -a merge is\n";
+        die = true;
+    } else if(algo_str != "merge") {
+        std::cerr << "FMIndexWalk: unrecognized -a,--algorithm parameter: " << algo_str << "\n";
+        die = true;
+    }
+    if(die) { std::cout << "\n" << FMWALK_USAGE_MESSAGE; exit(EXIT_FAILURE); }
+    fmwalkopt::readsFile = argv[optind++];
+    if(fmwalkopt::prefix.empty()) fmwalkopt::prefix = getFilename(fmwalkopt::readsFile);
+    if(fmwalkopt::outFile.empty()) fmwalkopt::outFile = getFilename(fmwalkopt::readsFile) + ".merge.fa";
+}
+
+static int fmwalkMain(int argc, char** argv)
+{
+    parseFMWalkOptions(argc, argv);
+    const int device = fmwalkopt::device;
+    lrsc_index* idx = nullptr;
+    if(fmwalkopt::buildIndex) {
+        std::string bases;
+        std::vector<uint64_t> off;
+        loadReads(fmwalkopt::readsFile, bases, off);
+        lrscOrDie(lrsc_index_build(bases.data(), off.data(), (uint32_t)(off.size() - 1), device, &idx), "lrsc_index_build");
+    } else {
+        std::cout << std::endl << "Loading BWT: " << fmwalkopt::prefix + BWT_EXT << "\n";
+        std::cout << "Loading RBWT: " << fmwalkopt::prefix + RBWT_EXT << "\n";
+        lrscOrDie(lrsc_index_open_device((fmwalkopt::prefix + BWT_EXT).c_str(), (fmwalkopt::prefix + RBWT_EXT).c_str(), device, &idx), "lrsc_index_open_device");
+    }
+    lrsc_ctx* ctx = nullptr;
+    lrscOrDie(lrsc_ctx_create(idx, nullptr, device, &ctx), "lrsc_ctx_create");
+
+    FMIndexWalkParameters params;
+    params.ctx = ctx;
+    params.kmerLength = fmwalkopt::kmerLength;
+    params.kmerThreshold = fmwalkopt::kmerThreshold;
+    params.maxLeaves = fmwalkopt::maxLeaves;
+    params.maxInsertSize = fmwalkopt::maxInsertSize;
+    params.minOverlap = fmwalkopt::minOverlap;
+    params.maxOverlap = fmwalkopt::maxOverlap;
+    bool odd = false;
+    {
+        std::ofstream writer(fmwalkopt::outFile.c_str());
+        if(!writer) { std::cerr << "Error: could not open " << fmwalkopt::outFile << " for write\n"; return EXIT_FAILURE; }
+        std::cout << "Merge paired end reads into long reads for " << fmwalkopt::readsFile << " using \n"
+                  << "min overlap=" << params.minOverlap << "\t"
+                  << "max overlap=" << params.maxOverlap << "\t"
+                  << "max leaves=" << params.maxLeaves << "\t"
+                  << "max Insert size=" << params.maxInsertSize << "\t"
+                  << "kmer size=" << params.kmerLength << "\n\n";
+        FMIndexWalkProcess processor(params);
+        FMIndexWalkPostProcess post(&writer);
+        SeqReader reader(fmwalkopt::readsFile, true);
+        WorkItemGenerator<SequenceWorkItem> generator(&reader);
+        std::vector<SequenceWorkItemPair> pairs;
+        for(bool more = true; more;) {
+            pairs.clear();
+            SequenceWorkItemPair pair;
+            while(pairs.size() < fmwalkopt::batch && (more = generator.generate(pair, &odd))) pairs.push_back(pair);
+            if(odd) break;
+            const std::vector<FMIndexWalkResult> results = processor.process_batch(pairs);
+            for(size_t i = 0; i < pairs.size(); ++i) post.process(pairs[i], results[i]);
+        }
+    }                                                             // the counters are printed here
+    std::cout.flush();
+    lrsc_ctx_destroy(ctx);
+    lrsc_index_close(idx);
+    if(odd) {                                                     // the reference asserts
+        std::cerr << "FMIndexWalk: " << fmwalkopt::readsFile << " holds an odd number of records: the reads of a pair follow one another\n";
+        std::remove(fmwalkopt::outFile.c_str());
+        return EXIT_FAILURE;
+    }
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
     // several workers on one device (--devices 0,0) only overlap if their streams get hardware queues of their own (default: 4)
     setenv("GPU_MAX_HW_QUEUES", "16", 0);
-    if(argc <= 1) { std::cerr << "Usage: " PACKAGE_NAME " <command> [options]\nCommands: index, merge, sai, grep, filter, correct, pbcorrect, kmerfreq, kmercheck\n"; return EXIT_FAILURE; }
+    if(argc <= 1) { std::cerr << "Usage: " PACKAGE_NAME " <command> [options]\nCommands: index, merge, sai, grep, filter, correct, pbcorrect, kmerfreq, kmercheck\n          and fmwalk\n"; return EXIT_FAILURE; }
     const std::string command(argv[1]);
-    if(command == "help" || command == "--help") { std::cout << "Usage: " PACKAGE_NAME " <command> [options]\nCommands: index, merge, sai, grep, filter, correct, pbcorrect, kmerfreq, kmercheck\n"; return 0; }
+    if(command == "help" || command == "--help") { std::cout << "Usage: " PACKAGE_NAME " <command> [options]\nCommands: index, merge, sai, grep, filter, correct, pbcorrect, kmerfreq, kmercheck\n          and fmwalk\n"; return 0; }
     if(command == "pbcorrect" || command == SUBPROGRAM) return PacBioSelfCorrectionMain(argc - 1, argv + 1);
     if(command == "index") return indexMain(argc - 1, argv + 1);
     if(command == "merge") return mergeMain(argc - 1, argv + 1);
@@ -972,6 +1129,7 @@ int main(int argc, char** argv)
     if(command == "grep") return grepMain(argc - 1, argv + 1);
     if(command == "filter") return filterMain(argc - 1, argv + 1);
     if(command == "correct") return correctMain(argc - 1, argv + 1);
+    if(command == "fmwalk") return fmwalkMain(argc - 1, argv + 1);
     if(command == "kmerfreq") return kmerfreqMain(argc - 1, argv + 1);
     if(command == "kmercheck") return kmercheckMain(argc - 1, argv + 1);
     std::cerr << "Unrecognized command: " << command << "\n";

@@ -1,0 +1,126 @@
+"""Rate of lrsc_fmwalk_merge (csrc/fm_fmwalk.hip), `stride fmwalk -a merge`'s device step, on one box in one run:
+
+  1. a genome from the testkit generator (--genome-mb, default 1); fragments of 250 to 400 bases from random places at 30x, half of
+     them reverse-complemented; a pair is the 100-base ends of a fragment, the second end read from the other strand, with 1 %
+     substitutions (--substitution-rate; with 0 the reads are what `stride correct`, the step before fmwalk in the pipeline, aims
+     to leave); all reads' own index by lrsc_index_build, which stays resident;
+  2. lrsc_fmwalk_merge over all pairs in batches of 100 000, as `stride fmwalk` calls it, with -k 31 -x 3 -m 81 -I 400 -L 32 and
+     -M from the lengths: one warm-up run, then three timed runs.  Per run: wall seconds of the calls, pairs/s, merged output
+     bases/s, the kernels' own milliseconds, their LF steps per second (one LF step is two Occ queries, from lrsc_ctx_stats under
+     K_FIND) and block loads per LF step;
+  3. the share of pairs merged, the share of merged strings that are the fragment (on either strand), and the walks' return codes.
+
+Prints profiles/kmer_correct.json's LF steps per second beside the result: the k-mer corrector's chains are the same backward
+search, a lane each with no frontier to keep.  Writes profiles/fmwalk_merge.json (or --out)."""
+from __future__ import annotations
+
+import argparse
+import json
+import statistics
+import sys
+import time
+from collections import Counter
+from pathlib import Path
+
+REPO = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(REPO))
+
+import numpy as np  # noqa: E402
+
+from longreadselfcorrect_amd import Lrsc, capi  # noqa: E402
+
+READ_LEN, FRAG_MIN, FRAG_MAX, COVERAGE, P_SUB, BATCH = 100, 250, 400, 30, 0.01, 100000
+OPTIONS = dict(kmer_length=31, kmer_threshold=3, min_overlap=81, max_overlap=-1, max_insert=400, max_leaves=32)
+
+
+def workload(api, genome_mb: float, p_sub: float):
+    """-> (the pairs' reads as ASCII, 2 n + 1 offsets, the fragments as ASCII strings)"""
+    rng = np.random.default_rng(0xF3A1C)
+    n = int(genome_mb * 1e6)
+    ascii_of = np.frombuffer(b"ACGT", dtype=np.uint8)
+    code_of = np.zeros(256, dtype=np.uint8)
+    code_of[ascii_of] = np.arange(4, dtype=np.uint8)
+    genome = code_of[np.frombuffer(api.synth_genome(0x5EED0001, n), dtype=np.uint8)]
+    n_pairs = n * COVERAGE // (2 * READ_LEN)
+    sizes = rng.integers(FRAG_MIN, FRAG_MAX + 1, size=n_pairs)
+    starts = rng.integers(0, n - FRAG_MAX, size=n_pairs)
+    flip = rng.random(n_pairs) < 0.5
+    cols = np.arange(READ_LEN)
+    left = genome[starts[:, None] + cols[None, :]]
+    right = 3 - genome[(starts + sizes - 1)[:, None] - cols[None, :]]          # the other strand, from the fragment's end
+    first, second = np.where(flip[:, None], right, left), np.where(flip[:, None], left, right)
+    reads = np.stack([first, second], axis=1).reshape(2 * n_pairs, READ_LEN)
+    hit = rng.random(reads.shape) < p_sub
+    reads[hit] = (reads[hit] + rng.integers(1, 4, size=int(hit.sum()), dtype=np.uint8)) & 3
+    off = (np.arange(2 * n_pairs + 1, dtype=np.uint64) * READ_LEN).astype(np.uint64)
+    text = ascii_of[genome].tobytes().decode()
+    return ascii_of[reads].reshape(-1), off, [text[s: s + z] for s, z in zip(starts.tolist(), sizes.tolist())]
+
+
+def one_run(ctx, bases, off):
+    n_pairs = (off.size - 1) // 2
+    ctx.stats_reset()
+    rows, res = [], np.zeros(n_pairs, dtype=capi.FMWALK_DTYPE)
+    t = time.perf_counter()
+    for a in range(0, n_pairs, BATCH):
+        b = min(a + BATCH, n_pairs)
+        lo, hi = int(off[2 * a]), int(off[2 * b])
+        merged, res[a:b] = ctx.fmwalk_merge(bases[lo:hi], off[2 * a: 2 * b + 1] - off[2 * a], **OPTIONS)
+        rows.append(merged)
+    wall = time.perf_counter() - t
+    s = ctx.stats(capi.K_FIND)
+    lf = s.rank_queries / 2
+    out_bases = int(res["length"][res["merged"] != 0].sum())
+    return np.concatenate(rows), res, {"wall_s": wall, "pairs_per_s": n_pairs / wall, "merged_bases_per_s": out_bases / wall, "kernel_ms": s.total_ms,
+                                       "launches": s.launches, "lf_steps": lf, "lf_steps_per_s": lf / (s.total_ms / 1e3),
+                                       "block_loads_per_lf_step": s.block_loads / lf}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--genome-mb", type=float, default=1.0)
+    ap.add_argument("--substitution-rate", type=float, default=P_SUB, help="0: reads as `stride correct` would leave them")
+    ap.add_argument("--out", default=str(REPO / "profiles" / "fmwalk_merge.json"))
+    args = ap.parse_args()
+    api = Lrsc()
+    bases, off, fragments = workload(api, args.genome_mb, args.substitution_rate)
+    t = time.perf_counter()
+    index = api.index_build(bases, off, 0)
+    build_s = time.perf_counter() - t
+    ctx = index.ctx(api.params_default(5, 90), 0)
+    one_run(ctx, bases, off)                                           # warm-up: buffers, code objects
+    runs = []
+    for _ in range(3):
+        rows, res, r = one_run(ctx, bases, off)
+        runs.append(r)
+        print(r, flush=True)
+    ctx.close()
+    index.close()
+    merged = np.flatnonzero(res["merged"])
+    comp = bytes.maketrans(b"ACGT", b"TGCA")
+    exact = 0
+    for i in merged.tolist():
+        s = rows[i, : int(res["length"][i])].tobytes()
+        exact += s.decode() == fragments[i] or s.translate(comp)[::-1].decode() == fragments[i]
+    kc = REPO / "profiles" / "kmer_correct.json"
+    kc_rate = json.loads(kc.read_text())["median"]["lf_steps_per_s"] if kc.exists() else None
+    result = {
+        "workload": {"genome_mb": args.genome_mb, "pairs": int(res.size), "read_length": READ_LEN, "fragment_bases": [FRAG_MIN, FRAG_MAX], "coverage": COVERAGE,
+                     "substitution_rate": args.substitution_rate, "bases": int(bases.size), "batch": BATCH, **OPTIONS, "index_build_s": build_s},
+        "runs": runs,
+        "median": {k: statistics.median(r[k] for r in runs) for k in ("wall_s", "pairs_per_s", "merged_bases_per_s", "kernel_ms", "lf_steps_per_s",
+                                                                      "block_loads_per_lf_step")},
+        "outcome": {"pairs_merged_share": float(merged.size / res.size), "merged_strings_that_are_the_fragment_share": float(exact / max(merged.size, 1)),
+                    "walk_codes": {str(k): int(v) for k, v in sorted(Counter(res["status"].reshape(-1).tolist()).items())},
+                    "max_used_leaves_mean": float(res["max_used_leaves"].mean())},
+        "kmer_correct_lf_steps_per_s": kc_rate,                        # profiles/kmer_correct.json, for context
+    }
+    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+    Path(args.out).write_text(json.dumps(result, indent=1) + "\n")
+    print(json.dumps(result))
+    if kc_rate:
+        print(f"LF steps/s: fmwalk merge {result['median']['lf_steps_per_s'] / 1e9:.2f} G, kmer correct {kc_rate / 1e9:.1f} G")
+
+
+if __name__ == "__main__":
+    main()
