@@ -171,6 +171,26 @@ int lrsc::upload_and_encode(lrsc_ctx* ctx, const char* ascii, uint64_t n, uint8_
     return LRSC_OK;
 }
 
+int lrsc::stage_reads(lrsc_ctx* ctx, const char* tool, unsigned limit_log2, const char* reads, const uint64_t* read_off, uint32_t n_reads, uint64_t slack)
+{
+    const int st = check_offsets(read_off, n_reads);
+    if(st != LRSC_OK) return st;
+    for(uint32_t i = 0; i < n_reads; ++i) {
+        const uint64_t len = read_off[i + 1] - read_off[i];
+        if(len == 0) return fail(LRSC_ERR_ARG, std::string(tool) + ": read " + std::to_string(i) + " is empty");
+        if(len >> limit_log2) return fail(LRSC_ERR_UNSUPPORTED, std::string(tool) + ": a read of 2^" + std::to_string(limit_log2) + " bases or more");
+    }
+    const uint64_t total = read_off[n_reads];
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(ctx->s_codes.reserve(total + slack));
+    HIP_TRY(ctx->s_off.reserve((uint64_t)n_reads + 1));
+    const int enc = upload_and_encode(ctx, reads, total, ctx->s_codes.p);    // reserves s_flag; the stream is idle after it
+    if(enc != LRSC_OK) return enc;
+    HIP_TRY(hipMemcpyAsync(ctx->s_off.p, read_off, ((uint64_t)n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemsetAsync(ctx->s_flag.p, 0, sizeof(int), ctx->stream));
+    return LRSC_OK;
+}
+
 // ---------------------------------------------------------------------------------------
 // context
 // ---------------------------------------------------------------------------------------

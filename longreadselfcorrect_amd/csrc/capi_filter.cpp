@@ -51,25 +51,13 @@ extern "C" int lrsc_dupcheck_reads(lrsc_dupcheck* dc, const char* reads, const u
     if(!dc || (n_reads && (!reads || !read_off || !out))) return fail(LRSC_ERR_ARG, "null");
     if(n_reads == 0) return LRSC_OK;
     lrsc_ctx* ctx = dc->ctx;
-    int st = check_offsets(read_off, n_reads);
+    // the codes are read as 32-bit words up to the one that holds the last base; a base other than A,C,G,T is rejected before
+    // anything is claimed
+    int st = stage_reads(ctx, "duplicate check", 32, reads, read_off, n_reads, 4);
     if(st != LRSC_OK) return st;
-    for(uint32_t i = 0; i < n_reads; ++i) {
-        const uint64_t len = read_off[i + 1] - read_off[i];
-        if(len == 0) return fail(LRSC_ERR_ARG, "duplicate check: read " + std::to_string(i) + " is empty");
-        if(len >= (1ull << 32)) return fail(LRSC_ERR_UNSUPPORTED, "duplicate check: a read of 2^32 bases or more");
-    }
-    const uint64_t total = read_off[n_reads];
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(ctx->s_codes.reserve(total + 4));                     // read as 32-bit words up to the one that holds the last base
-    HIP_TRY(ctx->s_off.reserve((uint64_t)n_reads + 1));
-    HIP_TRY(ctx->s_flag.reserve(1));
     HIP_TRY(dc->chains.reserve((uint64_t)n_reads * kDupKinds));
     HIP_TRY(dc->results.reserve(n_reads));
     HIP_TRY(dc->slots.reserve(n_reads));
-    st = upload_and_encode(ctx, reads, total, ctx->s_codes.p);    // rejects a base other than A,C,G,T before anything is claimed
-    if(st != LRSC_OK) return st;
-    HIP_TRY(hipMemcpyAsync(ctx->s_off.p, read_off, ((uint64_t)n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemsetAsync(ctx->s_flag.p, 0, sizeof(int), ctx->stream));
     st = timed_launch(ctx, LRSC_K_FIND, [&]() {
         return launch_dup_chains(ctx->fm, reinterpret_cast<const uint32_t*>(ctx->s_codes.p), ctx->s_off.p, n_reads, dc->chains.p, ctx->d_ctr, ctx->stream);
     });

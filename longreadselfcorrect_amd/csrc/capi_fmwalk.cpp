@@ -31,31 +31,19 @@ extern "C" int lrsc_fmwalk_merge(lrsc_ctx* ctx, const char* reads, const uint64_
     if(n_pairs == 0) return LRSC_OK;
     if(n_pairs >= (1u << 30)) return fail(LRSC_ERR_UNSUPPORTED, "fmwalk: 2^30 pairs or more in one call");
     const uint32_t n_reads = 2 * n_pairs;
-    int st = check_offsets(read_off, n_reads);
+    int st = stage_reads(ctx, "fmwalk", 31, reads, read_off, n_reads, 0);
     if(st != LRSC_OK) return st;
-    for(uint32_t i = 0; i < n_reads; ++i) {
-        const uint64_t len = read_off[i + 1] - read_off[i];
-        if(len == 0) return fail(LRSC_ERR_ARG, "fmwalk: read " + std::to_string(i) + " is empty");
-        if(len >= (1ull << 31)) return fail(LRSC_ERR_UNSUPPORTED, "fmwalk: a read of 2^31 bases or more");
-    }
     const FwParams fp{p->kmer_length, p->kmer_threshold, p->min_overlap, p->max_overlap, p->max_insert, p->max_leaves};
     const uint64_t slice = fw_workspace_bytes(fp);
     const uint32_t waves_per_group = kFwThreads / kFwLanes, n_walks = 2 * n_pairs;
     uint64_t groups = std::min<uint64_t>(((uint64_t)n_walks + waves_per_group - 1) / waves_per_group, resident_waves(ctx, kFwWavesPerSimd) / waves_per_group);
     groups = std::max<uint64_t>(1, std::min<uint64_t>(groups, kFwWorkspaceBytes / (slice * waves_per_group)));
-    const uint64_t total = read_off[n_reads], m4 = ((uint64_t)p->min_overlap + 3) & ~3ull;
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(ctx->s_codes.reserve(total));
-    HIP_TRY(ctx->s_off.reserve((uint64_t)n_reads + 1));
+    const uint64_t m4 = ((uint64_t)p->min_overlap + 3) & ~3ull;
     HIP_TRY(ctx->fw_ws.reserve(groups * waves_per_group * slice));
     HIP_TRY(ctx->fw_strs.reserve((uint64_t)n_pairs * 4 * m4));
     HIP_TRY(ctx->fw_trimmed.reserve(n_reads));
     HIP_TRY(ctx->fw_best.reserve((uint64_t)n_walks * stride));
     HIP_TRY(ctx->fw_outs.reserve((uint64_t)n_walks * sizeof(FwWalkOut)));
-    st = upload_and_encode(ctx, reads, total, ctx->s_codes.p);    // rejects a base other than A,C,G,T; the stream is idle after it
-    if(st != LRSC_OK) return st;
-    HIP_TRY(hipMemcpyAsync(ctx->s_off.p, read_off, ((uint64_t)n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemsetAsync(ctx->s_flag.p, 0, sizeof(int), ctx->stream));
     uint32_t* d_broken = reinterpret_cast<uint32_t*>(ctx->s_flag.p);
     FwWalkOut* d_outs = reinterpret_cast<FwWalkOut*>(ctx->fw_outs.p);
     st = timed_launch(ctx, LRSC_K_FIND, [&]() {

@@ -240,6 +240,10 @@ void kmer_freq_table(const lrsc_params& p, double freqs[101]);
 int encode_acgt(const char* seq, uint64_t n, uint8_t* codes);
 // upload ASCII bases, encode to 2-bit codes on the device, reject non-ACGT
 int upload_and_encode(lrsc_ctx* ctx, const char* ascii, uint64_t n, uint8_t* d_codes);
+// How the entries that search a strand for a batch of reads open (duplicate check, k-mer correction, fmwalk): the offsets are
+// checked, every read has a base and fewer than 2^limit_log2 ("<tool>: read i is empty", "<tool>: a read of 2^K bases or more");
+// then s_codes = the reads' codes with `slack` bytes behind them, s_off = their offsets, s_flag = 0, on the ctx's device.
+int stage_reads(lrsc_ctx* ctx, const char* tool, unsigned limit_log2, const char* reads, const uint64_t* read_off, uint32_t n_reads, uint64_t slack);
 
 // what the entries that make an index on the device share (capi_index.cpp)
 void free_device_copy(DeviceCopy& dc);

@@ -14,34 +14,25 @@ extern "C" int lrsc_kmer_correct(lrsc_ctx* ctx, const char* reads, const uint64_
     if(p->kmer_threshold <= 0) return fail(LRSC_ERR_ARG, "kmer correct: invalid kmer threshold: " + std::to_string(p->kmer_threshold));
     if(p->kmer_rounds <= 0) return fail(LRSC_ERR_ARG, "kmer correct: invalid number of kmer rounds: " + std::to_string(p->kmer_rounds));
     if(n_reads == 0) return LRSC_OK;
-    int st = check_offsets(read_off, n_reads);
+    int st = stage_reads(ctx, "kmer correct", 31, reads, read_off, n_reads, 0);
     if(st != LRSC_OK) return st;
     // the reads that do not fit LDS get a slice of the workspace
     std::vector<uint64_t> ws_off(n_reads, 0);
     uint64_t ws_bytes = 0;
     for(uint32_t i = 0; i < n_reads; ++i) {
         const uint64_t len = read_off[i + 1] - read_off[i];
-        if(len == 0) return fail(LRSC_ERR_ARG, "kmer correct: read " + std::to_string(i) + " is empty");
-        if(len >= (1ull << 31)) return fail(LRSC_ERR_UNSUPPORTED, "kmer correct: a read of 2^31 bases or more");
         if(len > kKcLdsBases) {
             ws_off[i] = ws_bytes;
             ws_bytes += kc_workspace_bytes(len);
         }
     }
     const uint64_t total = read_off[n_reads];
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(ctx->s_codes.reserve(total));
     HIP_TRY(ctx->s_out.reserve(total));
-    HIP_TRY(ctx->s_off.reserve((uint64_t)n_reads + 1));
     HIP_TRY(ctx->kc_ws_off.reserve(n_reads));
     HIP_TRY(ctx->kc_ws.reserve(std::max<uint64_t>(ws_bytes, 4)));
     HIP_TRY(ctx->kc_res.reserve(n_reads));
-    st = upload_and_encode(ctx, reads, total, ctx->s_codes.p);    // rejects a base other than A,C,G,T; the stream is idle after it
-    if(st != LRSC_OK) return st;
     if(phred) HIP_TRY(hipMemcpyAsync(ctx->s_in.p, phred, total, hipMemcpyHostToDevice, ctx->stream));   // the ASCII bases are done with
-    HIP_TRY(hipMemcpyAsync(ctx->s_off.p, read_off, ((uint64_t)n_reads + 1) * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(ctx->kc_ws_off.p, ws_off.data(), (uint64_t)n_reads * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemsetAsync(ctx->s_flag.p, 0, sizeof(int), ctx->stream));
     const KcParams kp{p->kmer_length, p->kmer_threshold, p->kmer_rounds, p->quality_cutoff};
     st = timed_launch(ctx, LRSC_K_FIND, [&]() {
         return launch_kmer_correct(ctx->fm, ctx->s_codes.p, ctx->s_off.p, phred ? ctx->s_in.p : nullptr, n_reads, kp, ctx->kc_ws.p, ctx->kc_ws_off.p, ctx->s_out.p,

@@ -9,8 +9,8 @@
 //   kind 2   rc              in .bwt    consumes comp(w[0]), comp(w[1]), ...
 //   kind 3   complement(w)   in .rbwt   consumes comp(w[L-1]), comp(w[L-2]), ...
 //
-// A chain (dup_chain) is one lane's: a step is one base and two Occ queries, one rank block when both ends of the interval lie in
-// one block (the rule once the interval has narrowed), and a chain whose interval becomes empty ends there, as findIntervalPair
+// A chain (dup_chain) is one lane's: a step (fm_strand.h's search_step) is one base and two Occ queries, one rank block when both
+// ends of the interval lie in one block (the rule once the interval has narrowed), and a chain whose interval becomes empty ends there, as findIntervalPair
 // does.  The bases are read a 32-bit word, four codes, at a time.  A chain that lives to its end reports its lower end, D(lower)
 // and D(upper + 1), D(p) being the '$' rows of the strand before row p: D(upper + 1) - D(lower) rows of the interval have '$' as
 // their preceding symbol, every other row is an extension by a base.
@@ -74,18 +74,6 @@ LRSC_HD uint32_t dup_code(const uint32_t* words, uint64_t pos, DupReader& r)
     return (r.word >> (8 * (uint32_t)(pos & 3u))) & 3u;
 }
 
-// Occ over the first `off` symbols of block g, held in b, plus the block's base count ('$' rows are stored as A and taken out)
-template <class Block>
-LRSC_HD uint64_t dup_occ(const StrandView<Block>& S, const Block& b, uint64_t g, uint32_t off, uint32_t code, const uint32_t* mtab)
-{
-    uint64_t c = block_base_count(b, code) + block_prefix_count(b, code, mtab + off * BlockLay<Block>::kRow);
-    if(code == 0 && off != 0 && has_dollar_flag(b)) {
-        bool at = false;
-        uint64_t j = 0;
-        c -= dollars_before(S, g, g * Block::kSyms, g * Block::kSyms + off, at, j);
-    }
-    return c;
-}
 // The '$' list of a strand without its rank blocks.
 struct DupDollars {
     const uint64_t* dollars;
@@ -112,24 +100,8 @@ LRSC_HD DupChainOut dup_chain(const StrandView<Block>& S, const uint32_t* mtab, 
     for(uint32_t t = 0; t < len; ++t) {
         const uint32_t code = dup_code(words, forward ? begin + t : begin + (len - 1 - t), rd) ^ flip;
         const P pred = strand_pred(S, code);
-        if(t == 0) {
-            lo = pred;
-            hi1 = code == 3u ? (P)S.N : strand_pred(S, code + 1);
-        } else {
-            const uint64_t gl = block_of<Block>(lo), gu = block_of<Block>(hi1);
-            const Block bl = S.blocks[gl];
-            const uint64_t ca = dup_occ(S, bl, gl, (uint32_t)(lo - (P)(gl * Block::kSyms)), code, mtab);
-            uint64_t cb;
-            if(gu == gl) cb = dup_occ(S, bl, gl, (uint32_t)(hi1 - (P)(gl * Block::kSyms)), code, mtab);
-            else {
-                const Block bu = S.blocks[gu];
-                cb = dup_occ(S, bu, gu, (uint32_t)(hi1 - (P)(gu * Block::kSyms)), code, mtab);
-            }
-            lo = pred + (P)ca;
-            hi1 = pred + (P)cb;
-            n_rank += 2;
-            n_blk += gu == gl ? 1u : 2u;
-        }
+        if(t == 0) search_first(S, code, pred, lo, hi1);
+        else search_step(S, mtab, code, pred, lo, hi1, n_rank, n_blk);
         if(hi1 > S.N || lo > hi1) { out.state = kDupBroken; return out; }     // never with the BWT of a string set
         if(lo == hi1) return out;                                 // the search string does not occur
     }

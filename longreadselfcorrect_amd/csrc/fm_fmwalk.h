@@ -3,14 +3,12 @@
 // SAIntervalTree::mergeTwoReads and what it calls (FMIndexWalk/SAIntervalTree.cpp:20-56, 103-170, 248-449, 494-507) on the
 // rank-block layout.
 //
-// An interval is held as its rows [lo, hi1); it is valid when lo < hi1.  A backward-search step (fw_update) is two Occ queries,
-// one rank block when both ends lie in one block.  A search (fw_search) ends where findInterval ends: at the first empty interval
-// after the first step, whose rows it keeps, because isTwoReadsOverlap compares intervals whether they are valid or not.
+// An interval is held as its rows [lo, hi1); it is valid when lo < hi1.  A backward-search step (fw_update) is fm_strand.h's
+// search_step of an interval that is one of the strand.  A search (fw_search) ends where findInterval ends: at the first empty
+// interval after the first step, whose rows it keeps, because isTwoReadsOverlap compares intervals whether they are valid or not.
 //
-// One wavefront owns a pair's trim (fw_trim_pair) and one each of its two walks (fw_walk); fw_merge_pair is the whole of a pair.  `W` says what a wavefront is: each(f) runs f(lane) for the kFwLanes lanes and makes
-// what they wrote visible to all; min_over(f) and sum64_over(f) do the same and give every lane the smallest f(lane) and their
-// sum; scan(f, g) runs f(lane) for every lane and then g(lane, the sum of f over the lanes before it, f(lane)), and gives every
-// lane the sum over all.  Everything outside them is the same in every lane; uniform(v) says so of a value read from the state.
+// One wavefront owns a pair's trim (fw_trim_pair) and one each of its two walks (fw_walk); fw_merge_pair is the whole of a pair.
+// `W` is fm_wave.h's wavefront, of which this uses each, min_over, sum64_over, scan, uniform and uniform64.
 //
 // views[0] is .bwt and views[1] is .rbwt; a lane picks its strand's by index, so the kernel keeps the two in LDS.
 //
@@ -33,8 +31,8 @@
 #pragma once
 #include <stdint.h>
 
-#include "fm_dup.h"
 #include "fm_strand.h"
+#include "fm_wave.h"
 
 #if defined(__clang__)
 #define LRSC_FW_NOUNROLL _Pragma("nounroll")
@@ -44,7 +42,7 @@
 
 namespace lrsc {
 
-constexpr uint32_t kFwLanes = 64;                                 // a wavefront: one pair's trim, or one walk
+constexpr uint32_t kFwLanes = kWaveLanes;                         // a wavefront: one pair's trim, or one walk
 constexpr uint32_t kFwThreads = 256;                              // four wavefronts per workgroup, one mask table
 // Wavefronts per SIMD that the launch is sized for: a walk is dependent 64-byte loads and latency-bound, so more wavefronts hide
 // more of it.  Four: 512 / 4 = 128 VGPRs hold a lane's rank block, interval and strand view (104 with 64-bit positions), which
@@ -59,7 +57,7 @@ constexpr uint32_t kFwMaxKmer = 255;
 constexpr uint32_t kFwRound = 8;                                  // leaves of a step that share the wavefront: 8 x 4 bases x 2 strands
 constexpr uint32_t kFwScan = 8;                                   // positions of a trim scan step: 8 x 4 bases x 2 strands
 constexpr uint32_t kFwChainLeaves = kFwLanes / 2;                 // leaves whose refinement chains share the wavefront
-constexpr uint32_t kFwNone = 0xFFFFFFFFu;
+constexpr uint32_t kFwNone = kWaveNone;
 
 struct FwParams {                                                 // lrsc_fmwalk_params
     int32_t kmer_length, kmer_threshold, min_overlap, max_overlap, max_insert, max_leaves;
@@ -124,23 +122,8 @@ LRSC_HD uint64_t fw_workspace_bytes(const FwParams& p)           // a multiple o
 template <class Block>
 LRSC_HD bool fw_update(const StrandView<Block>& S, const uint32_t* mtab, uint32_t code, FwIv& v, uint32_t& n_rank, uint32_t& n_blk)
 {
-    using P = typename BlockLay<Block>::pos_t;
     if(v.hi1 > S.N || v.lo > v.hi1) return false;
-    const P lo = (P)v.lo, hi1 = (P)v.hi1;
-    const P pred = strand_pred(S, code);
-    const uint64_t gl = block_of<Block>(lo), gu = block_of<Block>(hi1);
-    const Block bl = S.blocks[gl];
-    const uint64_t ca = dup_occ(S, bl, gl, (uint32_t)(lo - (P)(gl * Block::kSyms)), code, mtab);
-    uint64_t cb;
-    if(gu == gl) cb = dup_occ(S, bl, gl, (uint32_t)(hi1 - (P)(gl * Block::kSyms)), code, mtab);
-    else {
-        const Block bu = S.blocks[gu];
-        cb = dup_occ(S, bu, gu, (uint32_t)(hi1 - (P)(gu * Block::kSyms)), code, mtab);
-    }
-    v.lo = (uint64_t)pred + ca;
-    v.hi1 = (uint64_t)pred + cb;
-    n_rank += 2;
-    n_blk += gu == gl ? 1u : 2u;
+    search_step(S, mtab, code, strand_pred(S, code), v.lo, v.hi1, n_rank, n_blk);
     return v.hi1 <= S.N && v.lo <= v.hi1;
 }
 // findInterval of the string whose bases, in the order the search consumes them, are code_at(0 .. len), len >= 1
@@ -148,8 +131,7 @@ template <class Block, class CodeAt>
 LRSC_HD bool fw_search(const StrandView<Block>& S, const uint32_t* mtab, uint32_t len, CodeAt&& code_at, FwIv& v, uint32_t& n_rank, uint32_t& n_blk)
 {
     const uint32_t first = code_at(0u) & 3u;
-    v.lo = (uint64_t)strand_pred(S, first);
-    v.hi1 = first == 3u ? S.N : (uint64_t)strand_pred(S, first + 1);
+    search_first(S, first, strand_pred(S, first), v.lo, v.hi1);
     if(v.hi1 > S.N || v.lo > v.hi1) return false;
     for(uint32_t t = 1; t < len; ++t) {
         if(!fw_update<Block>(S, mtab, code_at(t) & 3u, v, n_rank, n_blk)) return false;

@@ -27,61 +27,6 @@ static_assert(sizeof(FwWalkOut) == 24, "no padding that a copy could leave unset
 
 constexpr uint32_t kFwWaves = kFwThreads / kFwLanes;
 
-// What fm_fmwalk.h calls a wavefront: a phase is every lane's call and then the wavefront's agreement on memory.
-struct FwWaveExec {
-    __device__ __forceinline__ static void sync()
-    {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    }
-    // The lane of a phase, opaque to the compiler: what a phase asks of its lane (is it below 4, odd, which base) would otherwise
-    // be computed once, before the walk, and held through it as a mask in two scalar registers each.
-    __device__ __forceinline__ static uint32_t lane()
-    {
-        uint32_t l = threadIdx.x & (kFwLanes - 1);
-        asm volatile("" : "+v"(l));
-        return l;
-    }
-    // a value that every lane holds alike, in scalar registers
-    __device__ __forceinline__ static uint32_t uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-    __device__ __forceinline__ static uint64_t uniform64(uint64_t v) { return ((uint64_t)uniform((uint32_t)(v >> 32)) << 32) | uniform((uint32_t)v); }
-    template <class F> __device__ __forceinline__ void each(F&& f)
-    {
-        f(lane());
-        sync();
-    }
-    template <class F> __device__ __forceinline__ uint32_t min_over(F&& f)
-    {
-        uint32_t v = f(lane());
-        sync();
-#pragma unroll
-        for(int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o, 64));
-        return uniform(v);
-    }
-    template <class F> __device__ __forceinline__ uint64_t sum64_over(F&& f)
-    {
-        unsigned long long v = f(lane());
-        sync();
-#pragma unroll
-        for(int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-        return uniform64(v);
-    }
-    template <class F, class G> __device__ __forceinline__ uint32_t scan(F&& f, G&& g)
-    {
-        const uint32_t l = lane(), mine = f(l);
-        uint32_t incl = mine;
-#pragma unroll
-        for(int o = 1; o < 64; o <<= 1) {
-            const uint32_t up = (uint32_t)__shfl_up((int)incl, o, 64);
-            incl += l >= (uint32_t)o ? up : 0u;
-        }
-        g(l, incl - mine, mine);
-        sync();
-        return uniform((uint32_t)__shfl((int)incl, 63, 64));
-    }
-};
-
 template <bool WIDE>
 __global__ __launch_bounds__(kFwThreads) __attribute__((amdgpu_waves_per_eu(kFwWavesPerSimd, kFwWavesPerSimd)))
 void fmwalk_trim_kernel(StrandView<typename BlockOf<WIDE>::type> bwt, const uint8_t* __restrict__ codes, const uint64_t* __restrict__ read_off, uint32_t n_pairs,
@@ -94,16 +39,16 @@ void fmwalk_trim_kernel(StrandView<typename BlockOf<WIDE>::type> bwt, const uint
     fill_mask_table<B>(mtab);
     if(threadIdx.x == 0) view = bwt;
     __syncthreads();
-    const uint32_t wave = FwWaveExec::uniform(threadIdx.x / kFwLanes);
+    const uint32_t wave = WaveExec::uniform(threadIdx.x / kFwLanes);
     const uint64_t pair = (uint64_t)blockIdx.x * kFwWaves + wave;     // uniform in the wavefront
     uint32_t n_rank = 0, n_blk = 0, bad = 0;
     if(pair < n_pairs) {
         const uint64_t b1 = read_off[2 * pair], b2 = read_off[2 * pair + 1], end = read_off[2 * pair + 2];
         const uint32_t m4 = ((uint32_t)p.min_overlap + 3u) & ~3u;
-        FwWaveExec w;
+        WaveExec w;
         uint32_t t[2];
         fw_trim_pair<B>(view, mtab, codes + b1, (uint32_t)(b2 - b1), codes + b2, (uint32_t)(end - b2), p, att[wave], w, strs + pair * 4 * m4, m4, t, bad, n_rank, n_blk);
-        if(FwWaveExec::lane() == 0) {
+        if(WaveExec::lane() == 0) {
             trimmed[2 * pair] = t[0];
             trimmed[2 * pair + 1] = t[1];
         }
@@ -144,23 +89,23 @@ void fmwalk_walk_kernel(StrandView<typename BlockOf<WIDE>::type> bwt, StrandView
     }
     if(threadIdx.x < kFwWaves) work[threadIdx.x] = fw_work_at(ws + ((uint64_t)blockIdx.x * kFwWaves + threadIdx.x) * ws_slice, args.p);
     __syncthreads();
-    const uint32_t wave = FwWaveExec::uniform(threadIdx.x / kFwLanes);
+    const uint32_t wave = WaveExec::uniform(threadIdx.x / kFwLanes);
     const uint32_t slot = blockIdx.x * kFwWaves + wave, n_slots = gridDim.x * kFwWaves;     // uniform in the wavefront
     uint32_t n_rank = 0, n_blk = 0, bad = 0;
-    for(uint32_t walk = slot; walk < FwWaveExec::uniform(a.n_walks) && !bad; walk += n_slots) {
+    for(uint32_t walk = slot; walk < WaveExec::uniform(a.n_walks) && !bad; walk += n_slots) {
         const uint64_t pair = walk >> 1;
         const uint32_t wk = walk & 1u, m = (uint32_t)a.p.min_overlap, m4 = work[wave].m4;
-        FwWaveExec w;
+        WaveExec w;
         FwWalkOut o{0, 0u, 0u, 0u, 0ull};
-        if(FwWaveExec::uniform(a.trimmed[2 * pair]) >= m && FwWaveExec::uniform(a.trimmed[2 * pair + 1]) >= m) {    // the gate
+        if(WaveExec::uniform(a.trimmed[2 * pair]) >= m && WaveExec::uniform(a.trimmed[2 * pair + 1]) >= m) {    // the gate
             const uint8_t* s = a.strs + pair * 4 * m4;
             const uint32_t n1 = (uint32_t)(a.read_off[2 * pair + 1] - a.read_off[2 * pair]), n2 = (uint32_t)(a.read_off[2 * pair + 2] - a.read_off[2 * pair + 1]);
-            fw_walk<B>(views, mtab, s + wk * m4, s + (3 - wk) * m4, a.p, FwWaveExec::uniform(fw_max_overlap(a.p, n1, n2)), work[wave], w, o, bad, n_rank, n_blk);
+            fw_walk<B>(views, mtab, s + wk * m4, s + (3 - wk) * m4, a.p, WaveExec::uniform(fw_max_overlap(a.p, n1, n2)), work[wave], w, o, bad, n_rank, n_blk);
             bad = fw_any_bad(w, bad) ? 1u : 0u;                   // the wavefront leaves the loop together
             uint8_t* to = a.best + (uint64_t)walk * a.stride;
-            for(uint32_t i = FwWaveExec::lane(); i < o.length && i < a.stride; i += kFwLanes) to[i] = work[wave].best()[i];
+            for(uint32_t i = WaveExec::lane(); i < o.length && i < a.stride; i += kFwLanes) to[i] = work[wave].best()[i];
         }
-        if(FwWaveExec::lane() == 0) {
+        if(WaveExec::lane() == 0) {
             if(!bad) a.outs[walk] = o;
             else *a.broken = 1u;
         }

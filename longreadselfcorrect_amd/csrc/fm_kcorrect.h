@@ -2,14 +2,12 @@
 // (fm_kcorrect.hip), the reference's ErrorCorrectProcess::kmerCorrection and attemptKmerCorrection
 // (Algorithm/ErrorCorrectProcess.cpp:287-438, 488-544) on the rank-block layout.
 //
-// count(w) is the interval of w in .bwt plus that of revcomp(w) in .bwt, each a backward search of its own (kc_chain): the
-// forward chain consumes w[k-1] .. w[0], the other comp(w[0]) .. comp(w[k-1]).  A chain can be told to read one base of the
-// read as another: the substitutions of an attempt are counted without touching the read.
+// count(w) is the interval of w in .bwt plus that of revcomp(w) in .bwt, each a backward search of its own (kc_chain, on
+// fm_strand.h's search_step): the forward chain consumes w[k-1] .. w[0], the other comp(w[0]) .. comp(w[k-1]).  A chain can be
+// told to read one base of the read as another: the substitutions of an attempt are counted without touching the read.
 //
 // One wavefront owns a read (kc_correct_read).  Its state is the edited codes seq[n], a flag byte per base and the two counts
-// per k-mer; `W` says what a wavefront is: each(f) runs f(lane) for the kKcLanes lanes and makes what they wrote visible to all,
-// min_over(f) and sum_over(f) do the same and give every lane the smallest f(lane) and their sum.  Everything outside them is
-// the same in every lane; uniform(v) says so of a value that was read from the state.  A pass:
+// per k-mer; `W` is fm_wave.h's wavefront, of which this uses each, min_over, sum_over and uniform.  A pass:
 //
 //   count     lanes take chains, k-mer by k-mer a forward and a reverse-complement one.  The first pass counts all nk k-mers, a
 //             later one only those that cover the base the pass before changed: a count is a function of the k-mer's string.
@@ -25,12 +23,12 @@
 #pragma once
 #include <stdint.h>
 
-#include "fm_dup.h"
 #include "fm_strand.h"
+#include "fm_wave.h"
 
 namespace lrsc {
 
-constexpr uint32_t kKcLanes = 64;                                 // a wavefront: one read
+constexpr uint32_t kKcLanes = kWaveLanes;                         // a wavefront: one read
 constexpr uint32_t kKcThreads = 256;                              // four reads per workgroup, one mask table
 // Wavefronts per SIMD that the launch is sized for: a chain is dependent 64-byte loads and latency-bound, so the kernel has to
 // stay within 512 / kKcWavesPerSimd VGPRs (allocated in eights: 80) and a workgroup within 160 KiB / (4 * kKcWavesPerSimd /
@@ -43,7 +41,7 @@ constexpr uint32_t kKcChainsPerBase = kKcLanes / kKcGroup;        // 16
 constexpr uint32_t kKcStateBytesPerBase = 10;                     // code, flag, two 32-bit counts
 
 constexpr uint64_t kKcBroken = ~0ull;                             // a chain whose interval left the strand
-constexpr uint32_t kKcNone = 0xFFFFFFFFu;
+constexpr uint32_t kKcNone = kWaveNone;
 constexpr uint32_t kKcCountMax = 0x7FFFFFFFu;                     // a count is held as the reference holds it, in 31 bits
 
 enum : uint8_t { kKcSolid = 1, kKcLowBase = 2, kKcLowKmer = 4, kKcGoodKmer = 8 };    // the flag byte of a base / of the k-mer that starts there
@@ -86,24 +84,8 @@ LRSC_HD uint64_t kc_chain(const StrandView<Block>& S, const uint32_t* mtab, cons
         uint32_t code = pos == ov_pos ? ov_code : (uint32_t)seq[pos];
         code = (code & 3u) ^ (rvc ? 3u : 0u);
         const P pred = strand_pred(S, code);
-        if(t == 0) {
-            lo = pred;
-            hi1 = code == 3u ? (P)S.N : strand_pred(S, code + 1);
-        } else {
-            const uint64_t gl = block_of<Block>(lo), gu = block_of<Block>(hi1);
-            const Block bl = S.blocks[gl];
-            const uint64_t ca = dup_occ(S, bl, gl, (uint32_t)(lo - (P)(gl * Block::kSyms)), code, mtab);
-            uint64_t cb;
-            if(gu == gl) cb = dup_occ(S, bl, gl, (uint32_t)(hi1 - (P)(gl * Block::kSyms)), code, mtab);
-            else {
-                const Block bu = S.blocks[gu];
-                cb = dup_occ(S, bu, gu, (uint32_t)(hi1 - (P)(gu * Block::kSyms)), code, mtab);
-            }
-            lo = pred + (P)ca;
-            hi1 = pred + (P)cb;
-            n_rank += 2;
-            n_blk += gu == gl ? 1u : 2u;
-        }
+        if(t == 0) search_first(S, code, pred, lo, hi1);
+        else search_step(S, mtab, code, pred, lo, hi1, n_rank, n_blk);
         if(hi1 > S.N || lo > hi1) return kKcBroken;               // never with the BWT of a string set
         if(lo == hi1) return 0;                                   // the k-mer does not occur
     }

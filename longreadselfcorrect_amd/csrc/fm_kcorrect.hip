@@ -21,39 +21,6 @@ constexpr uint32_t kKcWaves = kKcThreads / kKcLanes;
 constexpr uint32_t kKcLdsStateWords = (kKcLdsBases * kKcStateBytesPerBase + 4 * kKcLanes) / 4;
 static_assert(kKcLdsBases % 4 == 0 && kKcLanes == 64 && kKcGroup == 4, "the state's layout and the lanes of an attempt step");
 
-// What fm_kcorrect.h calls a wavefront: a phase is every lane's call and then the wavefront's agreement on memory.
-struct WaveExec {
-    __device__ __forceinline__ static void sync()
-    {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-    }
-    // a value that every lane holds alike, in a scalar register
-    __device__ __forceinline__ static uint32_t uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-    template <class F> __device__ __forceinline__ void each(F&& f)
-    {
-        f(threadIdx.x & (kKcLanes - 1));
-        sync();
-    }
-    template <class F> __device__ __forceinline__ uint32_t min_over(F&& f)
-    {
-        uint32_t v = f(threadIdx.x & (kKcLanes - 1));
-        sync();
-#pragma unroll
-        for(int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o, 64));
-        return uniform(v);
-    }
-    template <class F> __device__ __forceinline__ uint32_t sum_over(F&& f)
-    {
-        uint32_t v = f(threadIdx.x & (kKcLanes - 1));
-        sync();
-#pragma unroll
-        for(int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
-        return uniform(v);
-    }
-};
-
 template <bool WIDE>
 __global__ __launch_bounds__(kKcThreads) __attribute__((amdgpu_waves_per_eu(kKcWavesPerSimd, kKcWavesPerSimd)))
 void kmer_correct_kernel(StrandView<typename BlockOf<WIDE>::type> S, const uint8_t* __restrict__ codes, const uint64_t* __restrict__ read_off,

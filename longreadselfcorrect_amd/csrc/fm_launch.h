@@ -1,5 +1,6 @@
 // fm_launch.h -- what the .hip units of the index tools share around their kernels: the layout of a WIDE flag, the mask table in
-// LDS, a wavefront's sum into a counter, and on the host the device allocations of one call and the error check of a HIP call.
+// LDS, a wavefront's sum into a counter, the wavefront of fm_wave.h (WaveExec), and on the host the device allocations of one call
+// and the error check of a HIP call.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,6 +10,7 @@
 
 #include "../../include/lrsc.h"
 #include "fm_strand.h"
+#include "fm_wave.h"
 #include "kernels.h"
 
 namespace lrsc {
@@ -39,6 +41,71 @@ __device__ __forceinline__ void wave_count(DevCounters* ctr, unsigned long long 
         atomicAdd(&shard->block_loads, block_loads);
     }
 }
+
+// fm_wave.h's wavefront on the device: a phase is every lane's call and then the wavefront's agreement on memory.
+struct WaveExec {
+    __device__ __forceinline__ static void sync()
+    {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    }
+    // The lane of a phase, opaque to the compiler: what a phase asks of its lane (is it below 4, odd, which base) would otherwise
+    // be computed once, before the first phase, and held through all of them as a mask in two scalar registers each.
+    __device__ __forceinline__ static uint32_t lane()
+    {
+        uint32_t l = threadIdx.x & (kWaveLanes - 1);
+        asm volatile("" : "+v"(l));
+        return l;
+    }
+    // a value that every lane holds alike, in scalar registers
+    __device__ __forceinline__ static uint32_t uniform(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
+    __device__ __forceinline__ static uint64_t uniform64(uint64_t v) { return ((uint64_t)uniform((uint32_t)(v >> 32)) << 32) | uniform((uint32_t)v); }
+    template <class F> __device__ __forceinline__ void each(F&& f)
+    {
+        f(lane());
+        sync();
+    }
+    template <class F> __device__ __forceinline__ uint32_t min_over(F&& f)
+    {
+        uint32_t v = f(lane());
+        sync();
+#pragma unroll
+        for(int o = 32; o > 0; o >>= 1) v = min(v, (uint32_t)__shfl_xor((int)v, o, 64));
+        return uniform(v);
+    }
+    template <class F> __device__ __forceinline__ uint32_t sum_over(F&& f)
+    {
+        uint32_t v = f(lane());
+        sync();
+#pragma unroll
+        for(int o = 32; o > 0; o >>= 1) v += (uint32_t)__shfl_xor((int)v, o, 64);
+        return uniform(v);
+    }
+    template <class F> __device__ __forceinline__ uint64_t sum64_over(F&& f)
+    {
+        unsigned long long v = f(lane());
+        sync();
+#pragma unroll
+        for(int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+        return uniform64(v);
+    }
+    template <class F, class G> __device__ __forceinline__ uint32_t scan(F&& f, G&& g)
+    {
+        const uint32_t l = lane(), mine = f(l);
+        uint32_t incl = mine;
+#pragma unroll
+        for(int o = 1; o < 64; o <<= 1) {
+            const uint32_t up = (uint32_t)__shfl_up((int)incl, o, 64);
+            incl += l >= (uint32_t)o ? up : 0u;
+        }
+        g(l, incl - mine, mine);
+        sync();
+        return uniform((uint32_t)__shfl((int)incl, 63, 64));
+    }
+};
+static_assert(kWaveLanes == 64, "WaveExec's shuffles and wave_sum are a 64-lane wavefront's");
+
 // The device allocations of one call: freed when it ends, except those the call hands to its caller (keep).
 struct Owned {
     std::vector<void*> ptrs;

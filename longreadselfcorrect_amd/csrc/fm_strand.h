@@ -1,5 +1,5 @@
 // fm_strand.h -- one strand of a resident index as a lane sees it: what the device index tools (RL encode, merge, locate,
-// duplicate check, removal) share of the rank-block layout of fm_device.h.
+// duplicate check, removal, k-mer correction, paired-end walk) share of the rank-block layout of fm_device.h.
 //
 // A strand of an index is the BWT of a string set whose sentinels sort in input order: row i < n is the suffix that is read
 // i's sentinel alone.  Its image is the rank blocks (Block32 or Block64: the A,C,G,T counts before the block and two bit planes,
@@ -14,6 +14,9 @@
 //             the few list entries of the group; dollar_rank: the '$' rows of the strand before a position
 //   LF        lf_step: i <- C[c] + Occ(c, i) with c = BWT[i], both from the one rank block of row i; walk_read_back: the steps
 //             from a read's sentinel row to its '$' row, which ends on any input
+//   search    block_occ: Occ(c, p) from the rank block of p; search_first, search_step: the interval of a one-base string, and
+//             the interval [lo, hi1) narrowed by one more base.  The loop around them, how it reads its bases and what it makes
+//             of an empty interval is each tool's own.
 //
 // All functions here are LRSC_HD and free of HIP types: the kernels call them, and the drivers under tests/host_tools compile
 // the same source for the CPU.
@@ -226,14 +229,49 @@ LRSC_HD uint32_t walk_read_back(const StrandView<Block>& S, const uint32_t* mtab
     return kWalkBroken;
 }
 
-// ---- the names these had while they lived in fm_merge.h and fm_locate.h, for sources written against those ----
-template <class Block> using MergeLay = BlockLay<Block>;
-template <class Block> using MergeMaskTab = MaskTab<Block>;
-template <class Block> using MergeStrand = StrandView<Block>;
-template <class Block> LRSC_HD uint32_t merge_mask_word(uint32_t i) { return mask_word<Block>(i); }
-template <class Block> LRSC_HD StrandView<Block> merge_strand(const FmStrand& s) { return strand_view<Block>(s); }
-template <class Block> LRSC_HD uint64_t merge_block_of(typename BlockLay<Block>::pos_t p) { return block_of<Block>(p); }
-template <class Block> LRSC_HD void merge_decode_block(const StrandView<Block>& s, uint64_t g, Sym16* out) { decode_block<Block>(s, g, out); }
-enum : uint32_t { kLocateOk = kWalkOk, kLocateBroken = kWalkBroken };
+// ---- the backward search: an interval of rows [lo, hi1), narrowed one base at a time ----
+// Occ over the first `off` symbols of block g, held in b, plus the block's base count ('$' rows are stored as A and taken out)
+template <class Block>
+LRSC_HD uint64_t block_occ(const StrandView<Block>& S, const Block& b, uint64_t g, uint32_t off, uint32_t code, const uint32_t* mtab)
+{
+    uint64_t c = block_base_count(b, code) + block_prefix_count(b, code, mtab + off * BlockLay<Block>::kRow);
+    if(code == 0 && off != 0 && has_dollar_flag(b)) {
+        bool at = false;
+        uint64_t j = 0;
+        c -= dollars_before(S, g, g * Block::kSyms, g * Block::kSyms + off, at, j);
+    }
+    return c;
+}
+// Pos below is the type in which the caller holds its interval and in which the step adds: pos_t, or 64 bits whatever the
+// layout.  pred = strand_pred(S, code), which the caller has at hand.
+// the interval of the one-base string `code`
+template <class Block, class Pos>
+LRSC_HD void search_first(const StrandView<Block>& S, uint32_t code, typename BlockLay<Block>::pos_t pred, Pos& lo, Pos& hi1)
+{
+    lo = (Pos)pred;
+    hi1 = code == 3u ? (Pos)S.N : (Pos)strand_pred(S, code + 1);
+}
+// One step with `code` from an interval of the strand, lo <= hi1 <= S.N: two Occ queries, one rank block when both ends lie in
+// one block.  n_rank += the Occ queries, n_blk += the block loads.  Whether the new interval is empty, or one of the strand at
+// all (it always is with the BWT of a string set), is the caller's to ask.
+template <class Block, class Pos>
+LRSC_HD void search_step(const StrandView<Block>& S, const uint32_t* mtab, uint32_t code, typename BlockLay<Block>::pos_t pred, Pos& lo, Pos& hi1,
+                         uint32_t& n_rank, uint32_t& n_blk)
+{
+    using P = typename BlockLay<Block>::pos_t;
+    const uint64_t gl = block_of<Block>((P)lo), gu = block_of<Block>((P)hi1);
+    const Block bl = S.blocks[gl];
+    const uint64_t ca = block_occ(S, bl, gl, (uint32_t)((P)lo - (P)(gl * Block::kSyms)), code, mtab);
+    uint64_t cb;
+    if(gu == gl) cb = block_occ(S, bl, gl, (uint32_t)((P)hi1 - (P)(gl * Block::kSyms)), code, mtab);
+    else {
+        const Block bu = S.blocks[gu];
+        cb = block_occ(S, bu, gu, (uint32_t)((P)hi1 - (P)(gu * Block::kSyms)), code, mtab);
+    }
+    lo = (Pos)pred + (Pos)ca;
+    hi1 = (Pos)pred + (Pos)cb;
+    n_rank += 2;
+    n_blk += gu == gl ? 1u : 2u;
+}
 
 } // namespace lrsc

@@ -9,51 +9,12 @@
 // every read, kind by kind; dup_combine and the claim of the slot for every read; dup_classify for every read; then the bits
 // are set and the winner words released.  A broken chain or a winner word left claimed ends the run.
 // output: per call n records of 40 bytes (lrsc_dup_result); then u64 Occ queries, u64 block loads of all chains.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
+static const char kDriver[] = "dup_driver";
+#include "strand_driver.h"
 
 #include "../../longreadselfcorrect_amd/csrc/fm_dup.h"
-#include "../../longreadselfcorrect_amd/csrc/fm_layout.h"
 
 using namespace lrsc;
-
-static void die(const char* what)
-{
-    std::fprintf(stderr, "dup_driver: %s\n", what);
-    std::exit(1);
-}
-
-static FmStrand strand_of(const StrandImage& im, bool wide)
-{
-    FmStrand fs;
-    fs.blocks = im.blocks.data();
-    fs.dollars = im.dollars.data();
-    fs.dollar_dir = im.dollar_dir.data();
-    fs.dollar_group_syms = (uint64_t)(wide ? Block64::kSyms : Block32::kSyms) << kDollarDirShift;
-    fs.n_dollars = im.dollars.size();
-    fs.n_symbols = im.n_symbols;
-    fs.n_blocks = im.n_blocks;
-    for(int c = 0; c < 5; ++c) fs.pred[c] = im.pred[c];
-    return fs;
-}
-
-static void read_exact(void* p, size_t n)
-{
-    if(n && std::fread(p, 1, n, stdin) != n) die("short input");
-}
-
-static void read_image(bool wide, StrandImage& im)
-{
-    uint64_t hdr[2];
-    read_exact(hdr, 16);
-    std::vector<uint8_t> units(hdr[1]);
-    read_exact(units.data(), units.size());
-    std::string err;
-    if(build_strand_image(units.data(), units.size(), hdr[0], wide, im, err) != 0) die(err.c_str());
-}
 
 template <class Block>
 static void run(const StrandImage& i0, const StrandImage& i1, bool wide)
@@ -61,8 +22,7 @@ static void run(const StrandImage& i0, const StrandImage& i1, bool wide)
     static_assert(sizeof(DupResult) == 40, "lrsc_dup_result");
     const FmStrand f0 = strand_of(i0, wide), f1 = strand_of(i1, wide);
     const StrandView<Block> S[2] = {strand_view<Block>(f0), strand_view<Block>(f1)};
-    std::vector<uint32_t> mtab(MaskTab<Block>::kWords);
-    for(uint32_t i = 0; i < mtab.size(); ++i) mtab[i] = mask_word<Block>(i);
+    const std::vector<uint32_t> mtab = mask_table<Block>();
     const uint64_t n_slots = S[0].n_dollars;
     if(n_slots == 0 || S[1].n_dollars != n_slots) die("the strands hold no reads, or not the same number");
     std::vector<uint32_t> bits((n_slots + 31) / 32, 0u), winner(n_slots, kDupNoWinner);

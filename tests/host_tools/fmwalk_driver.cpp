@@ -10,76 +10,12 @@
 // of a pair is an allocation of exactly fw_workspace_bytes, its reads and its merged string allocations of their own.
 // output: n_pairs records of 48 bytes (lrsc_fmwalk_result), n_pairs rows of max(max_insert + 1, min_overlap) codes (0xFF where
 //         nothing was written), then u64 Occ queries, u64 block loads.  A broken interval ends the run with "FORMAT" and status 3.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
+static const char kDriver[] = "fmwalk_driver";
+#include "strand_driver.h"
 
 #include "../../longreadselfcorrect_amd/csrc/fm_fmwalk.h"
-#include "../../longreadselfcorrect_amd/csrc/fm_layout.h"
 
 using namespace lrsc;
-
-static void die(const char* what)
-{
-    std::fprintf(stderr, "fmwalk_driver: %s\n", what);
-    std::exit(1);
-}
-
-static FmStrand strand_of(const StrandImage& im, bool wide)
-{
-    FmStrand fs;
-    fs.blocks = im.blocks.data();
-    fs.dollars = im.dollars.data();
-    fs.dollar_dir = im.dollar_dir.data();
-    fs.dollar_group_syms = (uint64_t)(wide ? Block64::kSyms : Block32::kSyms) << kDollarDirShift;
-    fs.n_dollars = im.dollars.size();
-    fs.n_symbols = im.n_symbols;
-    fs.n_blocks = im.n_blocks;
-    for(int c = 0; c < 5; ++c) fs.pred[c] = im.pred[c];
-    return fs;
-}
-
-static void read_exact(void* p, size_t n)
-{
-    if(n && std::fread(p, 1, n, stdin) != n) die("short input");
-}
-
-// a wavefront, one lane after the other
-struct SerialExec {
-    static uint32_t uniform(uint32_t v) { return v; }
-    static uint64_t uniform64(uint64_t v) { return v; }
-    template <class F> void each(F&& f)
-    {
-        for(uint32_t lane = 0; lane < kFwLanes; ++lane) f(lane);
-    }
-    template <class F> uint32_t min_over(F&& f)
-    {
-        uint32_t v = kFwNone;
-        for(uint32_t lane = 0; lane < kFwLanes; ++lane) {
-            const uint32_t x = f(lane);
-            v = x < v ? x : v;
-        }
-        return v;
-    }
-    template <class F> uint64_t sum64_over(F&& f)
-    {
-        uint64_t v = 0;
-        for(uint32_t lane = 0; lane < kFwLanes; ++lane) v += f(lane);
-        return v;
-    }
-    template <class F, class G> uint32_t scan(F&& f, G&& g)
-    {
-        uint32_t mine[kFwLanes], before = 0;
-        for(uint32_t lane = 0; lane < kFwLanes; ++lane) mine[lane] = f(lane);
-        for(uint32_t lane = 0; lane < kFwLanes; ++lane) {
-            g(lane, before, mine[lane]);
-            before += mine[lane];
-        }
-        return before;
-    }
-};
 
 template <class Block>
 static int run(const StrandImage im[2], bool wide)
@@ -87,8 +23,7 @@ static int run(const StrandImage im[2], bool wide)
     static_assert(sizeof(FwResult) == 48 && sizeof(FwParams) == 24, "lrsc_fmwalk_result, lrsc_fmwalk_params");
     const FmStrand fs[2] = {strand_of(im[0], wide), strand_of(im[1], wide)};
     const StrandView<Block> views[2] = {strand_view<Block>(fs[0]), strand_view<Block>(fs[1])};
-    std::vector<uint32_t> mtab(MaskTab<Block>::kWords);
-    for(uint32_t i = 0; i < mtab.size(); ++i) mtab[i] = mask_word<Block>(i);
+    const std::vector<uint32_t> mtab = mask_table<Block>();
     FwParams p;
     read_exact(&p, sizeof(p));
     if(p.kmer_length <= 0 || p.kmer_threshold <= 0 || p.min_overlap < 2 || (p.max_overlap <= 0 && p.max_overlap != -1) || p.max_insert <= 0 || p.max_leaves <= 0 ||
@@ -112,7 +47,7 @@ static int run(const StrandImage im[2], bool wide)
         std::vector<uint64_t> state(fw_workspace_bytes(p) / 8, 0xA5A5A5A5A5A5A5A5ull);
         const FwWork ws = fw_work_at(reinterpret_cast<uint8_t*>(state.data()), p);
         std::vector<uint8_t> merged(stride, 0xFF);
-        SerialExec w;
+        SerialWave w;
         uint32_t n_rank = 0, n_blk = 0, bad = 0;
         fw_merge_pair<Block>(views, mtab.data(), r1.data(), (uint32_t)r1.size(), r2.data(), (uint32_t)r2.size(), p, ws, w, merged.data(), res[r], bad, n_rank,
                              n_blk);
@@ -135,13 +70,6 @@ int main(int argc, char** argv)
     if(argc != 2) { std::fprintf(stderr, "usage: fmwalk_driver <wide> < input\n"); return 2; }
     const bool wide = std::atoi(argv[1]) != 0;
     StrandImage im[2];
-    for(int s = 0; s < 2; ++s) {
-        uint64_t hdr[2];
-        read_exact(hdr, 16);
-        std::vector<uint8_t> units(hdr[1]);
-        read_exact(units.data(), units.size());
-        std::string err;
-        if(build_strand_image(units.data(), units.size(), hdr[0], wide, im[s], err) != 0) die(err.c_str());
-    }
+    for(int s = 0; s < 2; ++s) read_image(wide, im[s]);
     return wide ? run<Block64>(im, true) : run<Block32>(im, false);
 }

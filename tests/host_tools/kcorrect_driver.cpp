@@ -10,65 +10,12 @@
 // of a read is an allocation of exactly kc_workspace_bytes of its length, whatever its length.
 // output: n records of 16 bytes (lrsc_kcorrect_result), the corrected codes, then u64 Occ queries, u64 block loads.
 //         A broken chain ends the run with "FORMAT" and status 3.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
+static const char kDriver[] = "kcorrect_driver";
+#include "strand_driver.h"
 
 #include "../../longreadselfcorrect_amd/csrc/fm_kcorrect.h"
-#include "../../longreadselfcorrect_amd/csrc/fm_layout.h"
 
 using namespace lrsc;
-
-static void die(const char* what)
-{
-    std::fprintf(stderr, "kcorrect_driver: %s\n", what);
-    std::exit(1);
-}
-
-static FmStrand strand_of(const StrandImage& im, bool wide)
-{
-    FmStrand fs;
-    fs.blocks = im.blocks.data();
-    fs.dollars = im.dollars.data();
-    fs.dollar_dir = im.dollar_dir.data();
-    fs.dollar_group_syms = (uint64_t)(wide ? Block64::kSyms : Block32::kSyms) << kDollarDirShift;
-    fs.n_dollars = im.dollars.size();
-    fs.n_symbols = im.n_symbols;
-    fs.n_blocks = im.n_blocks;
-    for(int c = 0; c < 5; ++c) fs.pred[c] = im.pred[c];
-    return fs;
-}
-
-static void read_exact(void* p, size_t n)
-{
-    if(n && std::fread(p, 1, n, stdin) != n) die("short input");
-}
-
-// a wavefront, one lane after the other
-struct SerialExec {
-    static uint32_t uniform(uint32_t v) { return v; }
-    template <class F> void each(F&& f)
-    {
-        for(uint32_t lane = 0; lane < kKcLanes; ++lane) f(lane);
-    }
-    template <class F> uint32_t min_over(F&& f)
-    {
-        uint32_t v = kKcNone;
-        for(uint32_t lane = 0; lane < kKcLanes; ++lane) {
-            const uint32_t x = f(lane);
-            v = x < v ? x : v;
-        }
-        return v;
-    }
-    template <class F> uint32_t sum_over(F&& f)
-    {
-        uint32_t v = 0;
-        for(uint32_t lane = 0; lane < kKcLanes; ++lane) v += f(lane);
-        return v;
-    }
-};
 
 template <class Block>
 static int run(const StrandImage& im, bool wide)
@@ -76,8 +23,7 @@ static int run(const StrandImage& im, bool wide)
     static_assert(sizeof(KcResult) == 16 && sizeof(KcParams) == 16, "lrsc_kcorrect_result, lrsc_kcorrect_params");
     const FmStrand fs = strand_of(im, wide);
     const StrandView<Block> S = strand_view<Block>(fs);
-    std::vector<uint32_t> mtab(MaskTab<Block>::kWords);
-    for(uint32_t i = 0; i < mtab.size(); ++i) mtab[i] = mask_word<Block>(i);
+    const std::vector<uint32_t> mtab = mask_table<Block>();
     KcParams p;
     read_exact(&p, sizeof(p));
     if(p.kmer_length <= 0 || p.kmer_threshold <= 0 || p.kmer_rounds <= 0) die("the parameters");
@@ -103,7 +49,7 @@ static int run(const StrandImage& im, bool wide)
         const std::vector<uint8_t> mine(codes.begin() + (long)off[r], codes.begin() + (long)off[r + 1]);
         std::vector<uint8_t> scores, corrected(len);
         if(has_phred) scores.assign(phred.begin() + (long)off[r], phred.begin() + (long)off[r + 1]);
-        SerialExec w;
+        SerialWave w;
         uint32_t n_rank = 0, n_blk = 0;
         if(!kc_correct_read<Block>(S, mtab.data(), mine.data(), has_phred ? scores.data() : nullptr, len, p, st, w, corrected.data(), res[r], n_rank, n_blk)) {
             std::fwrite("FORMAT", 1, 6, stdout);
@@ -123,12 +69,7 @@ int main(int argc, char** argv)
 {
     if(argc != 2) { std::fprintf(stderr, "usage: kcorrect_driver <wide> < input\n"); return 2; }
     const bool wide = std::atoi(argv[1]) != 0;
-    uint64_t hdr[2];
-    read_exact(hdr, 16);
-    std::vector<uint8_t> units(hdr[1]);
-    read_exact(units.data(), units.size());
     StrandImage im;
-    std::string err;
-    if(build_strand_image(units.data(), units.size(), hdr[0], wide, im, err) != 0) die(err.c_str());
+    read_image(wide, im);
     return wide ? run<Block64>(im, true) : run<Block32>(im, false);
 }

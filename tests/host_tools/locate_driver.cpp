@@ -8,36 +8,12 @@
 // locate_row for every row of the strand.  A walk that reports kWalkBroken, a table entry written twice or never, ends the run.
 // output: u64 n, order[] as u32; u64 n, read_len[] as u32; u64 n_samples, the samples as (u32 read, u32 pos); u64 N, the located
 // (u32 read, u32 pos) of every row; u64 1, the LF steps of all locate walks as u64.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
+static const char kDriver[] = "locate_driver";
+#include "strand_driver.h"
 
-#include "../../longreadselfcorrect_amd/csrc/fm_layout.h"
 #include "../../longreadselfcorrect_amd/csrc/fm_locate.h"
 
 using namespace lrsc;
-
-static void die(const char* what)
-{
-    std::fprintf(stderr, "locate_driver: %s\n", what);
-    std::exit(1);
-}
-
-static FmStrand strand_of(const StrandImage& im, bool wide)
-{
-    FmStrand fs;
-    fs.blocks = im.blocks.data();
-    fs.dollars = im.dollars.data();
-    fs.dollar_dir = im.dollar_dir.data();
-    fs.dollar_group_syms = (uint64_t)(wide ? Block64::kSyms : Block32::kSyms) << kDollarDirShift;
-    fs.n_dollars = im.dollars.size();
-    fs.n_symbols = im.n_symbols;
-    fs.n_blocks = im.n_blocks;
-    for(int c = 0; c < 5; ++c) fs.pred[c] = im.pred[c];
-    return fs;
-}
 
 template <class T>
 static void dump(const std::vector<T>& v)
@@ -52,8 +28,7 @@ static void locate(const StrandImage& im, bool wide, uint32_t rate)
 {
     const FmStrand fs = strand_of(im, wide);
     const StrandView<Block> S = strand_view<Block>(fs);
-    std::vector<uint32_t> mtab(MaskTab<Block>::kWords);
-    for(uint32_t i = 0; i < mtab.size(); ++i) mtab[i] = mask_word<Block>(i);
+    const std::vector<uint32_t> mtab = mask_table<Block>();
     const uint64_t n = S.n_dollars, N = S.N;
     if(n == 0) die("the strand holds no read");
 
@@ -98,13 +73,8 @@ int main(int argc, char** argv)
     if(argc != 3) { std::fprintf(stderr, "usage: locate_driver <wide> <rate> < input\n"); return 2; }
     const bool wide = std::atoi(argv[1]) != 0;
     const uint32_t rate = (uint32_t)std::strtoul(argv[2], nullptr, 10);
-    uint64_t hdr[2];
-    if(std::fread(hdr, 8, 2, stdin) != 2) die("short input");
-    std::vector<uint8_t> units(hdr[1]);
-    if(hdr[1] && std::fread(units.data(), 1, hdr[1], stdin) != hdr[1]) die("short input");
     StrandImage im;
-    std::string err;
-    if(build_strand_image(units.data(), units.size(), hdr[0], wide, im, err) != 0) die(err.c_str());
+    read_image(wide, im);
     if(wide) locate<Block64>(im, true, rate);
     else locate<Block32>(im, false, rate);
     return 0;

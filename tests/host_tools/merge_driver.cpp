@@ -9,44 +9,12 @@
 // merge_origin_slot for every '$' row of B; with the kernels' tile (small = 0) or one of 384 positions, two Block32 or three
 // Block64 (small = 1).  What the kernels leave unwritten in LDS is 0xA5 here.
 // output: u64 N_A + N_B, the merged codes ($ACGT = 0..4); u64 N_B, rank[] as u64; u64 n_A + n_B, the origin bytes.
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
+static const char kDriver[] = "merge_driver";
+#include "strand_driver.h"
 
-#include "../../longreadselfcorrect_amd/csrc/fm_layout.h"
 #include "../../longreadselfcorrect_amd/csrc/fm_merge.h"
 
 using namespace lrsc;
-
-static void die(const char* what)
-{
-    std::fprintf(stderr, "merge_driver: %s\n", what);
-    std::exit(1);
-}
-
-static FmStrand strand_of(const StrandImage& im, bool wide)
-{
-    FmStrand fs;
-    fs.blocks = im.blocks.data();
-    fs.dollars = im.dollars.data();
-    fs.dollar_dir = im.dollar_dir.data();
-    fs.dollar_group_syms = (uint64_t)(wide ? Block64::kSyms : Block32::kSyms) << kDollarDirShift;
-    fs.n_dollars = im.dollars.size();
-    fs.n_symbols = im.n_symbols;
-    fs.n_blocks = im.n_blocks;
-    for(int c = 0; c < 5; ++c) fs.pred[c] = im.pred[c];
-    return fs;
-}
-
-template <class Block>
-static std::vector<uint32_t> mask_table()
-{
-    std::vector<uint32_t> t(MaskTab<Block>::kWords);
-    for(uint32_t i = 0; i < t.size(); ++i) t[i] = mask_word<Block>(i);
-    return t;
-}
 
 template <class T>
 static void dump(const std::vector<T>& v)
@@ -139,16 +107,6 @@ static void merge_tiled(const StrandImage& ia, const StrandImage& ib, bool wide_
     static_assert(kMergeTile == kMergeLanes * 16, "the kernels' tile");
     if(small) merge<BA, BB, 24>(ia, ib, wide_a, wide_b);
     else merge<BA, BB, kMergeLanes>(ia, ib, wide_a, wide_b);
-}
-
-static void read_image(bool wide, StrandImage& im)
-{
-    uint64_t hdr[2];
-    if(std::fread(hdr, 8, 2, stdin) != 2) die("short input");
-    std::vector<uint8_t> units(hdr[1]);
-    if(hdr[1] && std::fread(units.data(), 1, hdr[1], stdin) != hdr[1]) die("short input");
-    std::string err;
-    if(build_strand_image(units.data(), units.size(), hdr[0], wide, im, err) != 0) die(err.c_str());
 }
 
 int main(int argc, char** argv)

@@ -13,57 +13,18 @@
 // defect = 1: the '$' list of the image is emptied first, so that no walk meets its '$' row; the run must end in the FORMAT
 // path (exit status 3, "FORMAT" on stdout) with every mark inside the bitmap.
 // output: u64 N', the compacted codes ($ACGT = 0..4).
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <string>
-#include <vector>
+static const char kDriver[] = "remove_driver";
+#include "strand_driver.h"
 
-#include "../../longreadselfcorrect_amd/csrc/fm_layout.h"
 #include "../../longreadselfcorrect_amd/csrc/fm_remove.h"
 
 using namespace lrsc;
-
-static void die(const char* what)
-{
-    std::fprintf(stderr, "remove_driver: %s\n", what);
-    std::exit(1);
-}
 
 static void format_path(const char* why)
 {
     std::fprintf(stderr, "remove_driver: %s\n", why);
     std::fputs("FORMAT", stdout);
     std::exit(3);
-}
-
-static FmStrand strand_of(const StrandImage& im, bool wide)
-{
-    FmStrand fs;
-    fs.blocks = im.blocks.data();
-    fs.dollars = im.dollars.data();
-    fs.dollar_dir = im.dollar_dir.data();
-    fs.dollar_group_syms = (uint64_t)(wide ? Block64::kSyms : Block32::kSyms) << kDollarDirShift;
-    fs.n_dollars = im.dollars.size();
-    fs.n_symbols = im.n_symbols;
-    fs.n_blocks = im.n_blocks;
-    for(int c = 0; c < 5; ++c) fs.pred[c] = im.pred[c];
-    return fs;
-}
-
-static void read_exact(void* p, size_t n)
-{
-    if(n && std::fread(p, 1, n, stdin) != n) die("short input");
-}
-
-static void read_image(bool wide, StrandImage& im)
-{
-    uint64_t hdr[2];
-    read_exact(hdr, 16);
-    std::vector<uint8_t> units(hdr[1]);
-    read_exact(units.data(), units.size());
-    std::string err;
-    if(build_strand_image(units.data(), units.size(), hdr[0], wide, im, err) != 0) die(err.c_str());
 }
 
 // fm_pack.hip's steps on the CPU (tests/host_tools/pack_driver.cpp)
@@ -112,8 +73,7 @@ static void remove(StrandImage& im, bool wide, bool defect, const std::vector<ui
     if(defect) for(uint64_t& d : im.dollars) d = ~0ull;           // no row is a '$' row any more
     const FmStrand fs = strand_of(im, wide);
     const StrandView<Block> S = strand_view<Block>(fs);
-    std::vector<uint32_t> mtab(MaskTab<Block>::kWords);
-    for(uint32_t i = 0; i < mtab.size(); ++i) mtab[i] = mask_word<Block>(i);
+    const std::vector<uint32_t> mtab = mask_table<Block>();
     const uint64_t N = S.N;
 
     // 1. the walks
