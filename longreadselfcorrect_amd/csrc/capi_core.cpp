@@ -107,6 +107,7 @@ Tunables lrsc::read_tunables(const lrsc_ctx* ctx)
     t.wp_wave = env_clamped("LRSC_WP_WAVE", 1, 0, 2);                                        // 1, 0..2
     { const char* e = std::getenv("LRSC_WP_BEGIN_SORT"); t.wp_begin_sort = e && e[0] != '0'; } // off; on unless the value starts with 0
     t.dp_chunk_bytes = env_bytes("LRSC_DP_CHUNK_MB", 16ull << 30, 20);                       // 16384 MB, at least 1
+    t.dp_align_waves = env_clamped("LRSC_DP_ALIGN_WAVES", 0, 0, kIntMax);                    // 0 = sized as usual, at least 0
     t.msa_force_global = std::getenv("LRSC_MSA_FORCE_GLOBAL") != nullptr;                    // off; on when set
     { const char* e = std::getenv("LRSC_MSA_BATCH"); t.msa_batch = !(e && e[0] == '0'); }    // on; off when the value starts with 0
     t.profile = std::getenv("LRSC_CORRECT_PROFILE") != nullptr;                              // off; on when set

@@ -6,23 +6,45 @@ using namespace lrsc;
 
 // The launches of one set of alignments: one per non-empty staging-size class (dp_dev.h), each with the LDS, the traceback stride and
 // the wavefront count of its own largest alignment, then the global-workspace variant for what is beyond the LDS stage.
+// Each launch's wavefronts draw its alignments from the class's list in `order` (dp_order.h), uploaded by the caller, and from one
+// head word per class.
 struct DpAlignClasses {
     struct Class { uint32_t max_s1 = 0, stage_max = 0; uint64_t jobs = 0; } cls[kDpAlignClasses + 1];
-    void add(uint32_t s1_len, uint32_t stage_bytes, uint64_t n_jobs)
+    std::vector<DpOrderRun> runs;
+    DpOrder order;                         // set by sort(); the host copy outlives its asynchronous upload
+    // jobs first_job .. first_job + n_jobs - 1: alignments of s1_len columns that need stage_bytes of staging
+    void add(uint32_t s1_len, uint32_t stage_bytes, uint32_t first_job, uint32_t n_jobs)
     {
-        Class& c = cls[dp_align_class(stage_bytes)];
+        const uint32_t k = dp_align_class(stage_bytes);
+        Class& c = cls[k];
         c.max_s1 = std::max(c.max_s1, s1_len); c.stage_max = std::max(c.stage_max, stage_bytes); c.jobs += n_jobs;
+        if(n_jobs) runs.push_back({k, first_job, n_jobs});
     }
-    // wavefronts of class k's launch
-    uint32_t waves(uint32_t k, uint32_t lds_waves) const
+    void sort() { order = dp_order_build(runs); }
+    // wavefronts of class k's launch; wave_cap: LRSC_DP_ALIGN_WAVES (0 = none)
+    uint32_t waves(uint32_t k, uint32_t lds_waves, uint32_t wave_cap) const
     {
         const Class& c = cls[k];
         if(!c.jobs) return 0;
-        const uint64_t want = k < kDpAlignClasses ? lds_waves : 1024, stride = (uint64_t)(c.max_s1 + 17) * kDpTraceStride;
+        uint64_t want = k < kDpAlignClasses ? lds_waves : 1024;
+        if(wave_cap) want = std::min<uint64_t>(want, wave_cap);
+        const uint64_t stride = (uint64_t)(c.max_s1 + 17) * kDpTraceStride;
         return (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(std::min<uint64_t>(want, c.jobs), (4ull << 30) / stride));
     }
-    // `al`: everything but the per-launch fields; lds_waves: wavefronts of an LDS launch (the traceback scratch is capped at 4 GB)
-    int launch(lrsc_ctx* ctx, DpAlignArgs al, uint32_t lds_waves, DevBuf<uint8_t>& d_trace, DevBuf<uint8_t>& d_seq_ws) const
+    // `order` to the device and the head words zeroed, on the ctx's stream; d_heads: kDpAlignClasses + 1 words
+    int upload(lrsc_ctx* ctx, DevBuf<uint32_t>& d_order, DevBuf<uint32_t>& d_heads) const
+    {
+        HIP_TRY(d_order.reserve(std::max<size_t>(order.list.size(), 1)));
+        HIP_TRY(d_heads.reserve(kDpAlignClasses + 1));
+        if(!order.list.empty())
+            HIP_TRY(hipMemcpyAsync(d_order.p, order.list.data(), order.list.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipMemsetAsync(d_heads.p, 0, (kDpAlignClasses + 1) * sizeof(uint32_t), ctx->stream));
+        return LRSC_OK;
+    }
+    // `al`: everything but the per-launch fields; lds_waves: wavefronts of an LDS launch (the traceback scratch is capped at 4 GB);
+    // d_order, d_heads: as upload() left them
+    int launch(lrsc_ctx* ctx, DpAlignArgs al, uint32_t lds_waves, uint32_t wave_cap, DevBuf<uint8_t>& d_trace, DevBuf<uint8_t>& d_seq_ws,
+               const DevBuf<uint32_t>& d_order, const DevBuf<uint32_t>& d_heads) const
     {
         uint32_t nw[kDpAlignClasses + 1] = {};
         uint64_t stride[kDpAlignClasses + 1] = {}, trace_bytes = 0, ws_bytes = 0;
@@ -30,7 +52,7 @@ struct DpAlignClasses {
             const Class& c = cls[k];
             if(!c.jobs) continue;
             stride[k] = (uint64_t)(c.max_s1 + 17) * kDpTraceStride;
-            nw[k] = waves(k, lds_waves);
+            nw[k] = waves(k, lds_waves, wave_cap);
             trace_bytes = std::max(trace_bytes, stride[k] * nw[k]);
             if(k == kDpAlignClasses) ws_bytes = (((uint64_t)c.stage_max + 255) & ~255ull) * nw[k];
         }
@@ -39,8 +61,8 @@ struct DpAlignClasses {
         al.trace = d_trace.p;
         for(uint32_t k = 0; k <= kDpAlignClasses; ++k) {
             if(!nw[k]) continue;
-            al.stage_lo = k ? kDpAlignClassCap[k - 1] : 0;
-            al.stage_hi = k < kDpAlignClasses ? kDpAlignClassCap[k] : 0xFFFFFFFFu;
+            if(order.size(k) != cls[k].jobs) return fail(LRSC_ERR_DEVICE, "dp_align: a class's job list does not hold its jobs");
+            al.list = d_order.p + order.begin[k]; al.n_list = order.size(k); al.head = d_heads.p + k;
             al.stage_max = cls[k].stage_max;
             al.trace_stride = stride[k];
             al.seq_ws = k < kDpAlignClasses ? nullptr : d_seq_ws.p;
@@ -99,7 +121,7 @@ DpStage::Chunk DpStage::plan_chunk(std::vector<DpRequest>& reqs, uint32_t begin,
         if(ch.end > begin && ch.sbytes + ch.obytes + sb + ob + (ch.jobs + r.n_str) * (sizeof(DpJob) + sizeof(DpAlignOut)) > budget) break;
         r.job_first = ch.jobs; r.str_off = ch.sbytes; r.ops_off = ch.obytes;
         ch.jobs += r.n_str; ch.sbytes += sb; ch.obytes += ob;
-        ch.classes.add(r.lq, dp_align_stage_bytes(r.lq, r.str_cap), r.n_str);
+        ch.classes.add(r.lq, dp_align_stage_bytes(r.lq, r.str_cap), (uint32_t)r.job_first, r.n_str);
         ch.lds = std::max(ch.lds, dp_msa_lds_bytes(r.w_cols, r.lq, r.str_cap, r.ops_cap, r.n_str));
         ++ch.end;
     }
@@ -139,6 +161,10 @@ int DpStage::run(lrsc_ctx* ctx, const Tunables& tn, const uint8_t* d_query_codes
         c.reqs = d_reqs.p + begin; c.n_reqs = ch.size(); c.n_jobs = ch.jobs;
         c.strings = d_strings.p; c.jobs = d_jobs.p; c.align = d_align.p; c.ops = d_ops.p;
         c.cons = d_cons.p; c.msa = d_msa.p + begin; c.lds_bytes = ch.lds;
+        // the align launches' job lists go up before the retrieve launch: the copy is then not between it and the first align launch
+        ch.classes.sort();
+        st = ch.classes.upload(ctx, d_align_order, d_align_heads);
+        if(st != LRSC_OK) return st;
         st = timed_launch(ctx, LRSC_K_LF, [&]() { return launch_dp_retrieve(ctx->fm, c, ctx->stream); });
         if(st == LRSC_OK) st = align_chunk(ctx, tn, reqs, ch, (uint32_t)std::min<uint64_t>(n_waves, ch.jobs));
         if(st == LRSC_OK) st = msa_chunk(ctx, tn, reqs, ch);
@@ -158,7 +184,7 @@ int DpStage::align_chunk(lrsc_ctx* ctx, const Tunables& tn, const std::vector<Dp
         al.codes = ch.args.codes; al.strings = d_strings.p; al.jobs = d_jobs.p; al.n_jobs = (uint32_t)jobs;
         al.band_width = 200; al.match_score = 1; al.gap_penalty = -1; al.mismatch_penalty = -8;   // LongReadOverlap.cpp:635-643
         al.ops = d_ops.p; al.out = d_align.p; al.reqs = ch.args.reqs;
-        const int st = ch.classes.launch(ctx, al, lds_waves, d_trace, d_seq_ws);
+        const int st = ch.classes.launch(ctx, al, lds_waves, tn.dp_align_waves, d_trace, d_seq_ws, d_align_order, d_align_heads);
         if(st != LRSC_OK) return st;
     }
     if(tn.profile && ch.begin == 0 && jobs) {
@@ -166,18 +192,15 @@ int DpStage::align_chunk(lrsc_ctx* ctx, const Tunables& tn, const std::vector<Dp
         (void)hipMemcpy(ao.data(), d_align.p, jobs * sizeof(DpAlignOut), hipMemcpyDeviceToHost);
         double tf = 0, tt = 0, cols = 0, na = 0, trips = 0;
         for(const DpAlignOut& o : ao) if(!o.skipped) { tf += o.t_fill; tt += o.t_trace; cols += o.total_columns; na += 1; trips += o.t_trips; }
-        // how evenly the static hand-out (job % wavefronts of the launch) loads the wavefronts of the class with the most alignments
+        // how evenly the queue loaded the wavefronts of the class with the most alignments: every alignment records who drew it
         uint32_t big = 0;
         for(uint32_t k = 1; k <= kDpAlignClasses; ++k) if(ch.classes.cls[k].jobs > ch.classes.cls[big].jobs) big = k;
-        const uint32_t nw = ch.classes.waves(big, lds_waves);
+        const uint32_t nw = ch.classes.waves(big, lds_waves, tn.dp_align_waves);
         std::vector<double> wave(std::max(nw, 1u), 0.0);
-        for(uint32_t i = ch.begin; i < ch.end; ++i) {
-            const DpRequest& r = reqs[i];
-            if(dp_align_class(dp_align_stage_bytes(r.lq, r.str_cap)) != big) continue;
-            for(uint32_t s = 0; s < r.n_str; ++s) {
-                const DpAlignOut& o = ao[r.job_first + s];
-                wave[(r.job_first + s) % wave.size()] += (double)o.t_fill + o.t_trace;
-            }
+        const DpOrder& order = ch.classes.order;
+        for(uint32_t t = order.begin[big]; t < order.begin[big + 1]; ++t) {
+            const DpAlignOut& o = ao[order.list[t]];
+            wave[o.wave % wave.size()] += (double)o.t_fill + o.t_trace;
         }
         double w_max = 0, w_sum = 0;
         for(double w : wave) { w_max = std::max(w_max, w); w_sum += w; }
@@ -347,9 +370,11 @@ extern "C" int lrsc_dp_align(lrsc_ctx* ctx, const char* seq, uint64_t seq_len, c
         d.s1_off = j.s1_off; d.s2_off = j.s2_off; d.s1_len = j.s1_len; d.s2_len = j.s2_len; d.start1 = j.start1; d.start2 = j.start2;
         d.mode = 0; d.req = 0; d.ops_off = ops_total;
         ops_total += (uint64_t)j.s1_len + j.s2_len + 1;
-        classes.add(j.s1_len, dp_align_stage_bytes(j.s1_len, j.s2_len), 1);
+        classes.add(j.s1_len, dp_align_stage_bytes(j.s1_len, j.s2_len), i, 1);
     }
+    classes.sort();
     DevBuf<uint8_t> d_codes, d_ops, d_trace, d_stage;
+    DevBuf<uint32_t> d_order, d_heads;                   // of this call: another ctx may be in its own align launches on this device
     DevBuf<DpJob> d_jobs;
     DevBuf<DpAlignOut> d_out;
     DpAlignArgs a{};
@@ -364,7 +389,8 @@ extern "C" int lrsc_dp_align(lrsc_ctx* ctx, const char* seq, uint64_t seq_len, c
     a.ops = d_ops.p; a.out = d_out.p;
     // one launch per staging-size class; sequences beyond the 64 KB LDS stage: the same kernel with its staging in a global slice per
     // wavefront (fewer wavefronts)
-    st = classes.launch(ctx, a, resident_waves(ctx, 2), d_trace, d_stage);
+    st = classes.upload(ctx, d_order, d_heads);
+    if(st == LRSC_OK) st = classes.launch(ctx, a, resident_waves(ctx, 2), read_tunables(ctx).dp_align_waves, d_trace, d_stage, d_order, d_heads);
     if(st != LRSC_OK) return st;
     std::vector<DpAlignOut> out(n);
     std::vector<uint8_t> ops(ops_total);

@@ -92,6 +92,7 @@ struct Tunables {
     uint64_t wp_prep_bytes, wp_lane_bytes;
     uint32_t wp_gen_quorum, wp_gen_wait;
     uint64_t dp_chunk_bytes;
+    uint32_t dp_align_waves;
     bool msa_batch, msa_force_global;
 };
 
@@ -117,6 +118,9 @@ struct DpStage {
     DevBuf<uint32_t> d_list;
     DevBuf<uint8_t> d_msa_ws, d_seq_ws;
     DevBuf<uint32_t> d_msa_ctr;
+    // the align launches' job lists (dp_order.h) and their head words, one per staging-size class: this stage's own, since two ctxs
+    // run their DP stages on one device at the same time
+    DevBuf<uint32_t> d_align_order, d_align_heads;
     uint64_t cons_total = 0, n_strings = 0;
     // the MSA size buckets of a round run concurrently on side streams (each bucket's launch ends with a tail of a few long
     // pile-ups; serialised, those tails cost more than the work)

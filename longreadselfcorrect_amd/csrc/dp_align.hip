@@ -179,6 +179,15 @@ __device__ __forceinline__ void dp_edge_column(const DpLane& C, const DpScores& 
         if(v > best_row_val) { best_row_val = v; best_row_i = E.i + K; }
     }
 }
+// The next ticket of a wavefront that has had its first (its block index): tickets from the grid size on come from the launch's head
+// word, one relaxed device-scope add by one lane.  An alignment takes hundreds of microseconds, so one word per launch is far from
+// its limit, and nothing is ordered by the add: every alignment reads only what earlier launches wrote.
+__device__ __forceinline__ uint32_t dp_next_ticket(uint32_t* head)
+{
+    uint32_t t = 0;
+    if(threadIdx.x == 0) t = __hip_atomic_fetch_add(head, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return gridDim.x + uni(t);
+}
 __device__ __forceinline__ void dp_copy(int (&dst)[4], const int (&src)[4])
 {
 #pragma unroll
@@ -210,7 +219,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8))) void dp
         C.zero[t] = r < bw ? -g * r : kNeg;
     }
 
-    for(uint32_t job = blockIdx.x; job < a.n_jobs; job += gridDim.x) {
+    // The launch's alignments are a.list: the jobs of its staging-size class (dp_order.h).  A wavefront's first ticket is its block index, so that the
+    // launch does not open with every wavefront at the head word; each further one is drawn when the alignment before it is done,
+    // so a wavefront that met long alignments, or shares its CU with another kernel, takes fewer.
+    for(uint32_t ticket = blockIdx.x; ticket < a.n_list; ticket = dp_next_ticket(a.head)) {
+        const uint32_t job = uni(a.list[ticket]);
         // (the lane number is made opaque here and before the traceback: addresses derived from it are then formed where they are used and
         //  do not stay in registers through the fill)
         uint32_t lane = tid;
@@ -219,15 +232,9 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8))) void dp
         J.s1_off = uni64(J.s1_off); J.s2_off = uni64(J.s2_off); J.ops_off = uni64(J.ops_off);
         J.s1_len = uni(J.s1_len); J.s2_len = uni(J.s2_len); J.start1 = (int32_t)uni((uint32_t)J.start1); J.start2 = (int32_t)uni((uint32_t)J.start2);
         J.mode = uni(J.mode); J.req = uni(J.req);
-        {
-            // every launch does the alignments of one staging-size class (by the owning request's capacities where there is one, as
-            // the host sized the launches: a long query with a short retrieved string is still long)
-            const uint32_t sb = a.reqs ? dp_align_stage_bytes(a.reqs[J.req].lq, a.reqs[J.req].str_cap) : dp_align_stage_bytes(J.s1_len, J.s2_len);
-            if(sb <= a.stage_lo || sb > a.stage_hi) continue;
-        }
         DpAlignOut o;
         o.m0s = 0; o.m0e = -1; o.m1s = 0; o.m1e = -1; o.score = -1; o.edit_distance = -1; o.total_columns = -1; o.n_ops = 0;
-        o.accept = 0; o.skipped = 1; o.t_fill = 0; o.t_trace = 0; o.t_trips = 0;
+        o.accept = 0; o.skipped = 1; o.t_fill = 0; o.t_trace = 0; o.t_trips = 0; o.wave = blockIdx.x;
         const uint64_t t_job0 = __builtin_readcyclecounter();
         if(J.s1_len == 0 || J.s2_len == 0) {
             if(lane == 0) a.out[job] = o;
@@ -272,7 +279,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8))) void dp
         for(int i = 1; i <= L1; i += 4) {
             const int n = L1 - i + 1 < 4 ? L1 - i + 1 : 4;
             const int jb0 = origin + i;                             // first matrix row of the band in the first of the columns
-            uint8_t* tr = trace + (uint64_t)i * kDpTraceStride + tid;
+            uint8_t* tr = trace + (uint64_t)i * kDpTraceStride + lane;
             if(n == 4 && (jb0 + 3 + bw <= 1 || jb0 >= num_rows)) {  // the band lies outside the matrix in all four: cells read as 0
                                                                     // (codes the traceback never reads, see dp_column)
 #pragma unroll
@@ -454,10 +461,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(8))) void dp
 
 hipError_t launch_dp_align(const DpAlignArgs& a, uint32_t n_waves, hipStream_t stream)
 {
-    if(a.n_jobs == 0) return hipSuccess;
+    if(a.n_list == 0) return hipSuccess;
     if(a.band_width < 2 || (a.band_width / 2) * 2 + 1 > kDpMaxBand) return hipErrorInvalidValue;
+    if(!a.list || !a.head || a.n_list > a.n_jobs || n_waves == 0) return hipErrorInvalidValue;
     const size_t lds = a.stage_max;
-    if(n_waves > a.n_jobs) n_waves = a.n_jobs;
+    if(n_waves > a.n_list) n_waves = a.n_list;
     if(a.seq_ws) {
         if(a.seq_ws_stride < lds) return hipErrorInvalidValue;
         hipLaunchKernelGGL(dp_align_kernel<true>, dim3(n_waves), dim3(64), 0, stream, a);

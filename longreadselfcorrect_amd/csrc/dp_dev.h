@@ -5,6 +5,7 @@
 #include <hip/hip_runtime_api.h>
 #include <stdint.h>
 
+#include "dp_order.h"
 #include "kernels.h"
 
 namespace lrsc {
@@ -32,6 +33,7 @@ struct DpAlignOut {               // SequenceOverlap (Thirdparty/overlapper.h:69
     uint32_t skipped;
     uint32_t t_fill, t_trace;     // profiling: ticks spent in the DP fill / the traceback
     uint32_t t_trips;             // profiling: trips of the traceback loop (total_columns op-steps were taken in them)
+    uint32_t wave;                // profiling: the wavefront (block) of the launch that drew this alignment
 };
 
 // one correctByMSAlignment call (PacBioSelfCorrectionProcess.cpp:208-245)
@@ -89,10 +91,14 @@ struct DpAlignArgs {
     uint8_t* trace;               // n_waves x trace_stride
     uint64_t trace_stride;        // (max s1_len of this launch + 17) * kDpTraceStride
     const DpRequest* reqs;        // optional
-    // One launch does the alignments of one staging-size class, stage_lo < dp_align_stage_bytes <= stage_hi (of the owning request's
-    // capacities where reqs is set, else of the job's own lengths), and skips the others: a wavefront reserves the LDS of the largest
-    // alignment of its launch, so a few long queries in the launch of the short ones would cost those their occupancy.
-    uint32_t stage_lo, stage_hi;
+    // One launch does the alignments of one staging-size class (dp_order.h: of the owning request's capacities where reqs is set,
+    // else of the job's own lengths): a wavefront reserves the LDS of the largest alignment of its launch, so a few long queries in
+    // the launch of the short ones would cost those their occupancy.  The launch's alignments are list[0 .. n_list), job indices
+    // in ascending order; a wavefront takes list[its block index] and then draws tickets from *head (zeroed by the caller, one
+    // word per launch): ticket = blocks of the launch + atomicAdd(head, 1).
+    const uint32_t* list;
+    uint32_t n_list;
+    uint32_t* head;
     uint32_t stage_max;           // staging bytes of the largest alignment of this launch: its dynamic LDS
     // staging of the two sequences: LDS (seq_ws == nullptr, stage_max <= kDpAlignLdsCap) or, for the few alignments beyond it (a raw
     // segment of tens of kb between two seeds), a per-wavefront slice of this global workspace (seq_ws_stride >= stage_max, 256-aligned)
@@ -100,20 +106,8 @@ struct DpAlignArgs {
     uint64_t seq_ws_stride;
 };
 
-// n_waves = gridDim.x; every wave loops over jobs wave, wave + n_waves, ...
+// n_waves = gridDim.x (at most n_list are launched)
 hipError_t launch_dp_align(const DpAlignArgs& a, uint32_t n_waves, hipStream_t stream);
-// bytes of sequence staging one alignment needs (LDS or global slice)
-constexpr uint32_t dp_align_stage_bytes(uint32_t s1_len, uint32_t s2_len) { return ((s1_len + 2 + 3) & ~3u) + 264u + ((s2_len + 3) & ~3u) + 16u; }
-constexpr uint32_t kDpAlignLdsCap = 64u * 1024u;
-// upper bounds of the staging-size classes that run from LDS; what is beyond the last one runs from the global workspace
-constexpr uint32_t kDpAlignClasses = 3;
-constexpr uint32_t kDpAlignClassCap[kDpAlignClasses] = {4u * 1024u, 16u * 1024u, kDpAlignLdsCap};
-constexpr uint32_t dp_align_class(uint32_t stage_bytes)
-{
-    uint32_t c = 0;
-    while(c < kDpAlignClasses && stage_bytes > kDpAlignClassCap[c]) ++c;
-    return c;                     // kDpAlignClasses = the global-workspace launch
-}
 // lane per (request, direction): the two seed k-mers' bi-intervals -> row_lo / cnt
 hipError_t launch_dp_seeds(const FmIndexDev& fm, const DpPipeArgs& a, hipStream_t stream);
 // lane per retrieved string: LF-walk (retrieveStr), writes the string in its final orientation and its DpJob
