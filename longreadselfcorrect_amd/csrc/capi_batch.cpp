@@ -173,7 +173,7 @@ static int batch_setup_seeds(lrsc_ctx* ctx, lrsc_batch* b)
     HIP_TRY(hipMalloc(reinterpret_cast<void**>(&b->d_thr), 3 * 52 * sizeof(float)));
     float thr[3 * 52];
     (void)lrsc_kmer_thresholds(ctx->params.pb_coverage, thr);
-    HIP_TRY(hipMemcpy(b->d_thr, thr, sizeof(thr), hipMemcpyHostToDevice));
+    COPY_TRY(ctx, b->d_thr, thr, sizeof(thr), hipMemcpyHostToDevice);
     return LRSC_OK;
 }
 

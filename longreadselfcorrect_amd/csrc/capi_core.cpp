@@ -109,6 +109,7 @@ Tunables lrsc::read_tunables(const lrsc_ctx* ctx)
     t.dp_chunk_bytes = env_bytes("LRSC_DP_CHUNK_MB", 16ull << 30, 20);                       // 16384 MB, at least 1
     t.dp_align_waves = env_clamped("LRSC_DP_ALIGN_WAVES", 0, 0, kIntMax);                    // 0 = sized as usual, at least 0
     t.msa_force_global = std::getenv("LRSC_MSA_FORCE_GLOBAL") != nullptr;                    // off; on when set
+    t.msa_lds_max = env_clamped("LRSC_MSA_LDS_MAX", 0, 1, kIntMax);                          // not set = the computed budget; bytes, at least 1
     { const char* e = std::getenv("LRSC_MSA_BATCH"); t.msa_batch = !(e && e[0] == '0'); }    // on; off when the value starts with 0
     t.profile = std::getenv("LRSC_CORRECT_PROFILE") != nullptr;                              // off; on when set
     t.wp_dump = std::getenv("LRSC_WP_DUMP") != nullptr;                                      // off; on when set (with LRSC_CORRECT_PROFILE)

@@ -231,7 +231,16 @@ int WpFlow::bind_args()
     }
     // side stream: the few walks across long gaps run beside the DP stage of the bulk's failed walks instead of before it (they are
     // latency-bound on their own: a walk is a chain of dependent steps)
-    if(!sc.side) HIP_TRY(hipStreamCreateWithFlags(&sc.side, hipStreamNonBlocking));
+    // It gets the lowest stream priority.  The runtime keeps the hardware queues of each priority apart, so the side streams of two
+    // ctxs get a queue each that no other stream of the process shares: with the four queues a process has by default, streams of
+    // the default priority are dealt to them round robin, and a side stream then shares its queue with the other ctx's side stream
+    // and with MSA streams -- whatever is enqueued there after a long-gap launch waits until that launch has ended, the event
+    // that finish_long_walks() records included.  And the launch is the filler beside the DP stage, not the other way round.
+    if(!sc.side) {
+        int least = 0, greatest = 0;
+        HIP_TRY(hipDeviceGetStreamPriorityRange(&least, &greatest));
+        HIP_TRY(hipStreamCreateWithPriority(&sc.side, hipStreamNonBlocking, least));
+    }
     if(!sc.ev_ready) HIP_TRY(hipEventCreateWithFlags(&sc.ev_ready, hipEventDisableTiming));
     return LRSC_OK;
 }
@@ -291,12 +300,11 @@ int WpFlow::round_entries(Round& R, bool* done)
     a.list = nullptr; a.reqs = nullptr;
     if(R.index != 0) {
         uint32_t n_req = 0;
-        HIP_TRY(hipStreamSynchronize(ctx->stream));                      // ctx->stream is non-blocking: plain hipMemcpy does not wait for it
-        HIP_TRY(hipMemcpy(&n_req, a.n_req_out, sizeof(uint32_t), hipMemcpyDeviceToHost));
+        COPY_TRY(ctx, &n_req, a.n_req_out, sizeof(uint32_t), hipMemcpyDeviceToHost);
         if(n_req == 0) { *done = true; return LRSC_OK; }
         if(n_req > n) return fail(LRSC_ERR_LIMIT, "walk-parallel flow: request list overflow");
         hreq.resize(n_req);
-        HIP_TRY(hipMemcpy(hreq.data(), sc.d_req.p, (size_t)n_req * sizeof(WpRequest), hipMemcpyDeviceToHost));
+        COPY_TRY(ctx, hreq.data(), sc.d_req.p, (size_t)n_req * sizeof(WpRequest), hipMemcpyDeviceToHost);
         std::sort(hreq.begin(), hreq.end(), [](const WpRequest& x, const WpRequest& y) { return x.slot < y.slot; });
         hlist.resize(n_req);
         for(uint32_t i = 0; i < n_req; ++i) hlist[i] = hreq[i].slot;
@@ -381,7 +389,7 @@ hipError_t WpFlow::extend_range(WpArgs x, const uint32_t* list, const WpRequest*
     if(tn.wp_wave == 2) stride = 64;
     const WpLaneLayout LL = wp_lane_layout(lbytes, pathw);
     const uint64_t slots = tn.wp_lanes / 64;                                      // resident wavefronts of these kernels
-    const uint64_t share = side ? std::max<uint64_t>(1, slots / 2) : slots;
+    const uint64_t share = side ? wp_side_waves(tn) : slots;
     uint64_t lanes = std::min<uint64_t>(stride == 1 ? (((uint64_t)count + 63) & ~63ull) : count, share * 64 / stride);
     lanes = std::max<uint64_t>(1, std::min<uint64_t>(lanes, (tn.wp_lane_bytes / (side ? 4 : 1)) / LL.total));
     if(stride == 1) lanes = std::max<uint64_t>(64, lanes & ~63ull);
@@ -475,11 +483,11 @@ int WpFlow::start_long_walks(Round& R)
 int WpFlow::fetch_items(DevBuf<WpDpItem>& d_list, const uint32_t* d_count, uint32_t cap, Round& R, std::vector<WpDpItem>& out)
 {
     uint32_t cnt = 0;
-    HIP_TRY(hipMemcpy(&cnt, d_count, sizeof(uint32_t), hipMemcpyDeviceToHost));
+    COPY_TRY(ctx, &cnt, d_count, sizeof(uint32_t), hipMemcpyDeviceToHost);
     if(cnt > cap) return fail(LRSC_ERR_LIMIT, "walk-parallel flow: DP item list overflow");
     R.n_items += cnt;
     out.resize(cnt);
-    if(cnt) HIP_TRY(hipMemcpy(out.data(), d_list.p, (size_t)cnt * sizeof(WpDpItem), hipMemcpyDeviceToHost));
+    if(cnt) COPY_TRY(ctx, out.data(), d_list.p, (size_t)cnt * sizeof(WpDpItem), hipMemcpyDeviceToHost);
     std::sort(out.begin(), out.end(), [](const WpDpItem& x, const WpDpItem& y) { return x.slot < y.slot; });
     return LRSC_OK;
 }
@@ -534,7 +542,7 @@ int WpFlow::finish_long_walks()
     lrsc_kernel_stats& s = ctx->stats[LRSC_K_EXTEND];
     s.total_ms += ms;             // overlaps the DP stage: the stage times then add up to more than the wall time
     std::vector<DevCounters> shards(kCtrShards);
-    HIP_TRY(hipMemcpy(shards.data(), sc.d_ctr2.p, kCtrShards * sizeof(DevCounters), hipMemcpyDeviceToHost));
+    COPY_TRY(ctx, shards.data(), sc.d_ctr2.p, kCtrShards * sizeof(DevCounters), hipMemcpyDeviceToHost);
     for(const DevCounters& dcn : shards) {
         s.rank_queries += dcn.rank_queries;
         s.block_loads += dcn.block_loads;
@@ -633,10 +641,9 @@ int WpFlow::gather_results(lrsc_read_result* res, uint64_t* piece_off, uint64_t 
                            uint64_t* n_pieces_out, uint64_t* out_used)
 {
     std::vector<WpRead> ro(n);
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    HIP_TRY(hipMemcpy(ro.data(), sc.d_reads.p, (size_t)n * sizeof(WpRead), hipMemcpyDeviceToHost));
+    COPY_TRY(ctx, ro.data(), sc.d_reads.p, (size_t)n * sizeof(WpRead), hipMemcpyDeviceToHost);
     std::vector<uint32_t> pieces(std::max<uint64_t>(piece_total, 1));
-    if(piece_total) HIP_TRY(hipMemcpy(pieces.data(), sc.d_pieces.p, (size_t)piece_total * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if(piece_total) COPY_TRY(ctx, pieces.data(), sc.d_pieces.p, (size_t)piece_total * sizeof(uint32_t), hipMemcpyDeviceToHost);
     std::vector<uint64_t> dst_off(n + 1, 0);
     uint64_t n_pieces = 0;
     for(uint32_t r = 0; r < n; ++r) {

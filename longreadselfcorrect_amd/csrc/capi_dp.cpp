@@ -1,6 +1,7 @@
 // capi_dp.cpp -- the DP/MSA fallback: the align launches per staging-size class, the DP stage (seeds -> retrieve -> align -> MSA)
 // and the two entry points that expose them, lrsc_dp_align and lrsc_dp_consensus.
 #include "capi_internal.h"
+#include "dp_deal.h"
 
 using namespace lrsc;
 
@@ -128,13 +129,34 @@ DpStage::Chunk DpStage::plan_chunk(std::vector<DpRequest>& reqs, uint32_t begin,
     return ch;
 }
 
+// The LDS of a CU that an MSA launch may count on.  Two ctxs share the device, and beside a DP stage the other ctx's long-gap launch
+// (WpFlow::start_long_walks) is usually in flight: wp_side_waves() workgroups of wp_extend_wave_kernel, each with the kernel's static
+// LDS (its mask table), resident for hundreds of ms.  A launch sized for an empty CU cannot be placed beside them: its workgroups
+// wait until that launch drains.  So the budget is the CU's LDS less what those workgroups hold, each rounded up to the granule in
+// which LDS is handed out; LRSC_MSA_LDS_MAX lowers it further (a test hook: small pile-ups then cross the ceilings).
+int DpStage::msa_lds_budget(lrsc_ctx* ctx, const Tunables& tn, uint32_t* budget) const
+{
+    uint32_t wg_lds = 0;
+    HIP_TRY(wp_extend_wave_static_lds(ctx->fm.wide != 0, &wg_lds));
+    int cus = 256;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+    const uint64_t wgs_per_cu = (wp_side_waves(tn) + (uint64_t)cus - 1) / (uint64_t)cus;
+    const uint64_t held = wgs_per_cu * (((uint64_t)wg_lds + kLdsGranule - 1) / kLdsGranule * kLdsGranule);
+    uint32_t b = held < kLdsPerCu ? (uint32_t)(kLdsPerCu - held) : 0u;
+    if(tn.msa_lds_max) b = std::min(b, tn.msa_lds_max);
+    *budget = b;
+    return LRSC_OK;
+}
+
 int DpStage::run(lrsc_ctx* ctx, const Tunables& tn, const uint8_t* d_query_codes, std::vector<DpRequest>& reqs)
 {
     const uint32_t n = (uint32_t)reqs.size();
     n_strings = 0; cons_total = 0;
     if(n == 0) return LRSC_OK;
     int st = size_requests(reqs);
+    if(st == LRSC_OK) st = msa_lds_budget(ctx, tn, &lds_budget);
     if(st != LRSC_OK) return st;
+    if(tn.profile) std::fprintf(stderr, "[lrsc] msa: LDS budget per CU %u B\n", (unsigned)lds_budget);
     HIP_TRY(d_reqs.reserve(n));
     HIP_TRY(d_msa.reserve(n));
     HIP_TRY(d_cons.reserve(cons_total));
@@ -144,7 +166,7 @@ int DpStage::run(lrsc_ctx* ctx, const Tunables& tn, const uint8_t* d_query_codes
     a.row_batch = tn.msa_batch;
     st = timed_launch(ctx, LRSC_K_LF, [&]() { return launch_dp_seeds(ctx->fm, a, ctx->stream); });
     if(st != LRSC_OK) return st;
-    HIP_TRY(hipMemcpy(reqs.data(), d_reqs.p, (size_t)n * sizeof(DpRequest), hipMemcpyDeviceToHost));
+    COPY_TRY(ctx, reqs.data(), d_reqs.p, (size_t)n * sizeof(DpRequest), hipMemcpyDeviceToHost);
 
     // 8 wavefronts per SIMD hide the scan's cross-lane latency
     const uint32_t n_waves = resident_waves(ctx, 8);
@@ -236,18 +258,25 @@ int DpStage::align_chunk(lrsc_ctx* ctx, const Tunables& tn, const std::vector<Dp
 struct DpStage::MsaLaunch {
     DpPipeArgs args;
     size_t list_first;
-    bool global_ws;                        // the bucket beyond the LDS: pile-up state in d_msa_ws
+    bool global_ws;                        // the bucket beyond the LDS budget: pile-up state in d_msa_ws
+    uint64_t work;                         // sum of query length x strings over its requests (dp_deal.h)
 };
 
 // The launches for the chunk's requests `todo`, one per non-empty bucket, and their request lists back to back in `lists`; returns
-// the bytes of global workspace the last bucket's launch needs (0: none).
+// the bytes of global workspace the last bucket's launch needs (0: none).  A bucket holds the requests of which kWgsPerCu[..]
+// workgroups fit the LDS budget of a CU (lds_budget) and one more does not; what is beyond the budget goes to the global-workspace
+// variant.
 uint64_t DpStage::msa_buckets(const std::vector<DpRequest>& reqs, const Chunk& ch, const std::vector<uint32_t>& todo, bool force_global,
-                              std::vector<MsaLaunch>& launches, std::vector<uint32_t>& lists)
+                              std::vector<MsaLaunch>& launches, std::vector<uint32_t>& lists) const
 {
-    static const uint32_t kBuckets[] = {8u << 10, 12u << 10, 16u << 10, 20u << 10, 24u << 10, 32u << 10, 40u << 10, 80u << 10, 160u << 10, 0xFFFFFFFFu};
+    static const uint32_t kWgsPerCu[] = {20, 13, 10, 8, 6, 5, 4, 2, 1};
+    uint32_t buckets[sizeof(kWgsPerCu) / sizeof(kWgsPerCu[0]) + 1];
+    uint32_t nb = 0;
+    for(uint32_t w : kWgsPerCu) buckets[nb++] = (lds_budget / w) & ~15u;
+    buckets[nb++] = 0xFFFFFFFFu;
     uint32_t lo = 0;
     uint64_t ws_bytes = 0;
-    for(uint32_t bk : kBuckets) {
+    for(uint32_t bk : buckets) {
         if(force_global && bk != 0xFFFFFFFFu) continue;
         const size_t first = lists.size();
         uint32_t need_max = 0;
@@ -265,7 +294,8 @@ uint64_t DpStage::msa_buckets(const std::vector<DpRequest>& reqs, const Chunk& c
             const uint64_t wx = (uint64_t)rx.lq * rx.n_str, wy = (uint64_t)ry.lq * ry.n_str;
             return wx != wy ? wx > wy : x < y;
         });
-        MsaLaunch L{ch.args, first, bk == 0xFFFFFFFFu};
+        MsaLaunch L{ch.args, first, bk == 0xFFFFFFFFu, 0};
+        for(size_t t = first; t < lists.size(); ++t) { const DpRequest& r = reqs[ch.begin + lists[t]]; L.work += (uint64_t)r.lq * r.n_str; }
         L.args.n_list = (uint32_t)(lists.size() - first);
         L.args.lds_bytes = (need_max + 15) & ~15u;
         if(L.global_ws) {
@@ -273,16 +303,16 @@ uint64_t DpStage::msa_buckets(const std::vector<DpRequest>& reqs, const Chunk& c
             // (nothing fits the LDS, or LRSC_MSA_FORCE_GLOBAL), as many as the chunk has (dp_msa_waves counts n_reqs without a list)
             DpPipeArgs sized = L.args;
             sized.req_list = first ? d_list.p : nullptr;
-            ws_bytes = (uint64_t)L.args.lds_bytes * dp_msa_waves(sized, true);
+            ws_bytes = (uint64_t)L.args.lds_bytes * dp_msa_waves(sized, true, lds_budget);
         }
         launches.push_back(L);
     }
     return ws_bytes;
 }
 
-// Multiple alignments of the chunk: one launch per LDS-size bucket (a wide pile-up must not cut everyone's occupancy), all in
-// flight together, a global-memory variant for the few that exceed 160 KB; a pile-up that opened more gap columns than its
-// capacity is redone with twice the columns.
+// Multiple alignments of the chunk: one launch per LDS-size bucket (a wide pile-up must not cut everyone's occupancy), dealt to the
+// side streams (dp_deal.h), a global-memory variant for the few that exceed the LDS budget; a pile-up that opened more gap columns
+// than its capacity is redone with twice the columns.
 int DpStage::msa_chunk(lrsc_ctx* ctx, const Tunables& tn, std::vector<DpRequest>& reqs, const Chunk& ch)
 {
     const uint32_t nc = ch.size(), begin = ch.begin;
@@ -309,22 +339,26 @@ int DpStage::msa_chunk(lrsc_ctx* ctx, const Tunables& tn, std::vector<DpRequest>
             if(!side[i]) HIP_TRY(hipStreamCreateWithFlags(&side[i], hipStreamNonBlocking));
             if(!side_done[i]) HIP_TRY(hipEventCreateWithFlags(&side_done[i], hipEventDisableTiming));
         }
+        std::vector<DpDealLaunch> dl;
+        for(const MsaLaunch& L : launches) dl.push_back({L.work, L.global_ws ? 0u : L.args.lds_bytes});
+        const std::vector<std::vector<uint32_t>> deal = dp_deal(dl, (uint32_t)kSide);
         const int st = timed_launch(ctx, LRSC_K_MSA, [&]() -> hipError_t {
             // ctx->ev0 was just recorded on ctx->stream: the side streams start after it (and after the list upload)
             hipError_t e = hipSuccess;
-            for(size_t j = 0; j < launches.size() && e == hipSuccess; ++j) {
-                hipStream_t sj = side[j % kSide];
-                e = hipStreamWaitEvent(sj, ctx->ev0, 0);
-                if(e == hipSuccess) e = launch_dp_msa(launches[j].args, sj);
+            for(size_t i = 0; i < deal.size() && e == hipSuccess; ++i) {
+                if(deal[i].empty()) continue;
+                e = hipStreamWaitEvent(side[i], ctx->ev0, 0);
+                for(size_t t = 0; t < deal[i].size() && e == hipSuccess; ++t) e = launch_dp_msa(launches[deal[i][t]].args, lds_budget, side[i]);
+                if(e == hipSuccess) e = hipEventRecord(side_done[i], side[i]);
             }
-            for(int i = 0; i < kSide && e == hipSuccess; ++i) {
-                e = hipEventRecord(side_done[i], side[i]);
-                if(e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, side_done[i], 0);
-            }
+            // the waits after every launch: where a side stream shares its hardware queue with ctx->stream, a wait enqueued before
+            // that stream's launches would hold them back until the other streams are done
+            for(size_t i = 0; i < deal.size() && e == hipSuccess; ++i)
+                if(!deal[i].empty()) e = hipStreamWaitEvent(ctx->stream, side_done[i], 0);
             return e;
         });
         if(st != LRSC_OK) return st;
-        HIP_TRY(hipMemcpy(mo.data(), d_msa.p + begin, (size_t)nc * sizeof(DpMsaOut), hipMemcpyDeviceToHost));
+        COPY_TRY(ctx, mo.data(), d_msa.p + begin, (size_t)nc * sizeof(DpMsaOut), hipMemcpyDeviceToHost);
         redo.clear();
         for(uint32_t i : todo) {
             if(mo[i].error != 1) continue;                       // 0 = done; 2 = consensus beyond its capacity: stays an error of this request
@@ -394,8 +428,8 @@ extern "C" int lrsc_dp_align(lrsc_ctx* ctx, const char* seq, uint64_t seq_len, c
     if(st != LRSC_OK) return st;
     std::vector<DpAlignOut> out(n);
     std::vector<uint8_t> ops(ops_total);
-    HIP_TRY(hipMemcpy(out.data(), d_out.p, (size_t)n * sizeof(DpAlignOut), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(ops.data(), d_ops.p, ops_total, hipMemcpyDeviceToHost));
+    COPY_TRY(ctx, out.data(), d_out.p, (size_t)n * sizeof(DpAlignOut), hipMemcpyDeviceToHost);
+    COPY_TRY(ctx, ops.data(), d_ops.p, ops_total, hipMemcpyDeviceToHost);
     uint64_t used = 0;
     for(uint32_t i = 0; i < n; ++i) {
         const DpAlignOut& o = out[i];
@@ -440,8 +474,8 @@ extern "C" int lrsc_dp_consensus(lrsc_ctx* ctx, const char* seq, uint64_t seq_le
     if(st != LRSC_OK) return st;
     std::vector<DpMsaOut> mo(n);
     std::vector<uint8_t> cons(stage.cons_total);
-    HIP_TRY(hipMemcpy(mo.data(), stage.d_msa.p, (size_t)n * sizeof(DpMsaOut), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(cons.data(), stage.d_cons.p, stage.cons_total, hipMemcpyDeviceToHost));
+    COPY_TRY(ctx, mo.data(), stage.d_msa.p, (size_t)n * sizeof(DpMsaOut), hipMemcpyDeviceToHost);
+    COPY_TRY(ctx, cons.data(), stage.d_cons.p, stage.cons_total, hipMemcpyDeviceToHost);
     uint64_t used = 0;
     for(uint32_t i = 0; i < n; ++i) {
         if(mo[i].error) return fail(LRSC_ERR_LIMIT, "msa: column capacity exceeded");

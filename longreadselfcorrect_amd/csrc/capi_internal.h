@@ -46,12 +46,21 @@ struct DevBuf {
     T* p = nullptr;
     size_t cap = 0;
     ~DevBuf() { if(p) (void)hipFree(p); }
+    // hipFree / hipMalloc wait for every kernel on the device, those of another ctx included: a buffer that has to grow again grows by
+    // a quarter at least, so that batches that are each a little larger than the last do not pay that wait every time.  The callers'
+    // budgets bound n, not the slack: where the device cannot hold the slack the buffer gets exactly n.
     hipError_t reserve(size_t n)
     {
         if(n <= cap) return hipSuccess;
+        size_t want = cap ? std::max(n, cap + cap / 4) : n;
         if(p) { (void)hipFree(p); p = nullptr; cap = 0; }
-        hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), n * sizeof(T));
-        if(e == hipSuccess) cap = n;
+        hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), want * sizeof(T));
+        if(e != hipSuccess && want > n) {
+            (void)hipGetLastError();
+            p = nullptr; want = n;
+            e = hipMalloc(reinterpret_cast<void**>(&p), want * sizeof(T));
+        }
+        if(e == hipSuccess) cap = want; else p = nullptr;
         return e;
     }
 };
@@ -68,7 +77,7 @@ struct DevArena {
         bytes = (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255;
         while(cur < chunks.size()) {
             if(chunks[cur]->cap - off >= bytes) { *out = chunks[cur]->p + off; off += bytes; return hipSuccess; }
-            // an empty chunk that is too small is replaced rather than skipped (grow-only, few chunks)
+            // an empty chunk that is too small is replaced rather than skipped (grow-only, few chunks; DevBuf::reserve adds its quarter)
             if(off == 0) { hipError_t e = chunks[cur]->reserve(bytes + bytes / 8); if(e != hipSuccess) return e; continue; }
             ++cur; off = 0;
         }
@@ -94,6 +103,7 @@ struct Tunables {
     uint64_t dp_chunk_bytes;
     uint32_t dp_align_waves;
     bool msa_batch, msa_force_global;
+    uint32_t msa_lds_max;                  // LRSC_MSA_LDS_MAX: upper bound of the MSA launches' LDS budget per CU (0 = not set)
 };
 
 struct DeviceCopy {
@@ -122,9 +132,11 @@ struct DpStage {
     // run their DP stages on one device at the same time
     DevBuf<uint32_t> d_align_order, d_align_heads;
     uint64_t cons_total = 0, n_strings = 0;
+    // LDS per CU the MSA launches of a run() may count on (msa_lds_budget), set by run()
+    uint32_t lds_budget = 0;
     // the MSA size buckets of a round run concurrently on side streams (each bucket's launch ends with a tail of a few long
-    // pile-ups; serialised, those tails cost more than the work)
-    static constexpr int kSide = 8;
+    // pile-ups; serialised, those tails cost more than the work); dp_deal.h deals the launches to the streams
+    static constexpr int kSide = 3;
     hipStream_t side[kSide] = {};
     hipEvent_t side_done[kSide] = {};
     ~DpStage();
@@ -136,9 +148,10 @@ private:
     struct MsaLaunch;
     int size_requests(std::vector<DpRequest>& reqs);
     Chunk plan_chunk(std::vector<DpRequest>& reqs, uint32_t begin, uint64_t budget);
+    int msa_lds_budget(lrsc_ctx* ctx, const Tunables& tn, uint32_t* budget) const;
     int align_chunk(lrsc_ctx* ctx, const Tunables& tn, const std::vector<DpRequest>& reqs, const Chunk& ch, uint32_t lds_waves);
     uint64_t msa_buckets(const std::vector<DpRequest>& reqs, const Chunk& ch, const std::vector<uint32_t>& todo, bool force_global,
-                         std::vector<MsaLaunch>& launches, std::vector<uint32_t>& lists);
+                         std::vector<MsaLaunch>& launches, std::vector<uint32_t>& lists) const;
     int msa_chunk(lrsc_ctx* ctx, const Tunables& tn, std::vector<DpRequest>& reqs, const Chunk& ch);
 };
 
@@ -235,6 +248,9 @@ Tunables read_tunables(const lrsc_ctx* ctx);
 uint64_t env_bytes(const char* name, uint64_t dflt, unsigned shift);
 // wavefronts the device holds at `per_simd` per SIMD (4 SIMDs per CU)
 uint32_t resident_waves(const lrsc_ctx* ctx, uint32_t per_simd);
+// wavefronts of the long-gap walks' side launch: it shares the device with the launches on the ctx's stream and takes half of the
+// extension kernels' resident wavefronts (WpFlow::extend_range); the MSA launches leave its LDS free (DpStage::msa_lds_budget)
+inline uint64_t wp_side_waves(const Tunables& tn) { return std::max<uint64_t>(1, tn.wp_lanes / 64 / 2); }
 int check_offsets(const uint64_t* off, uint32_t n_reads);
 // the walk's -l / idmer / minimum k-mer limits (lrsc_extend_walks and lrsc_batch_correct)
 int check_walk_params(const lrsc_params& p);
@@ -272,6 +288,21 @@ int finish_index(lrsc_index* idx, int device, DeviceCopy& dc, int st, uint64_t n
 // the strands of idx's copy on `device` (LRSC_ERR_DEVICE without one)
 int resident_strands(lrsc_index* idx, int device, FmStrand fs[2], bool& wide);
 
+// A blocking copy on the ctx's own stream.  A plain hipMemcpy goes through the null stream, whose hardware queue also carries streams
+// of other contexts when the process has few queues: the copy would wait for their kernels.  Whatever the copy reads was written on
+// ctx->stream, or on a side stream whose end the host has already waited for.
+inline int copy_sync(lrsc_ctx* ctx, void* dst, const void* src, size_t bytes, hipMemcpyKind kind)
+{
+    if(bytes) HIP_TRY(hipMemcpyAsync(dst, src, bytes, kind, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return LRSC_OK;
+}
+#define COPY_TRY(ctx, dst, src, bytes, kind)                                   \
+    do {                                                                       \
+        const int _st = lrsc::copy_sync((ctx), (dst), (src), (bytes), (kind)); \
+        if(_st != LRSC_OK) return _st;                                         \
+    } while(0)
+
 // Bracket one kernel launch with HIP events on the ctx stream and fold the device counters
 // into the per-kernel stats.  `launch` enqueues on ctx->stream.
 template <class F>
@@ -286,7 +317,7 @@ int timed_launch(lrsc_ctx* ctx, int which, F&& launch)
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
     std::vector<DevCounters> shards(kCtrShards);
-    HIP_TRY(hipMemcpy(shards.data(), ctx->d_ctr, kCtrShards * sizeof(DevCounters), hipMemcpyDeviceToHost));
+    COPY_TRY(ctx, shards.data(), ctx->d_ctr, kCtrShards * sizeof(DevCounters), hipMemcpyDeviceToHost);
     DevCounters h{};
     for(const DevCounters& d : shards) { h.rank_queries += d.rank_queries; h.block_loads += d.block_loads; h.table_loads += d.table_loads; }
     lrsc_kernel_stats& s = ctx->stats[which];

@@ -113,11 +113,15 @@ hipError_t launch_dp_seeds(const FmIndexDev& fm, const DpPipeArgs& a, hipStream_
 // lane per retrieved string: LF-walk (retrieveStr), writes the string in its final orientation and its DpJob
 hipError_t launch_dp_retrieve(const FmIndexDev& fm, const DpPipeArgs& a, hipStream_t stream);
 // wavefront per request: MultipleAlignment::addOverlap for every accepted overlap + calculateBaseConsensus
-hipError_t launch_dp_msa(const DpPipeArgs& a, hipStream_t stream);
+// lds_per_cu: the LDS of a CU that the launch may count on (what other kernels in flight leave of it): sizes the grid
+hipError_t launch_dp_msa(const DpPipeArgs& a, uint32_t lds_per_cu, hipStream_t stream);
 uint32_t dp_msa_lds_bytes(uint32_t w_cols, uint32_t lq, uint32_t str_cap, uint32_t ops_cap, uint32_t n_str);
 // initial column capacity of one multiple alignment: the query plus the gap columns insertions may open
 constexpr uint32_t dp_msa_columns(uint32_t lq) { return 3 * lq + 128; }
 constexpr uint32_t dp_cons_capacity(uint32_t lq) { return 2 * lq + 128; }
-uint32_t dp_msa_waves(const DpPipeArgs& a, bool global);
+// bytes of LDS a compute unit has, and the granule in which it is handed to workgroups (gfx950: 160 KB in blocks of 320 dwords)
+constexpr uint32_t kLdsPerCu = 160u * 1024u, kLdsGranule = 1280u;
+// workgroups of an MSA launch: lds_per_cu / a.lds_bytes per CU (global: 8, they hold no LDS), at most one per request
+uint32_t dp_msa_waves(const DpPipeArgs& a, bool global, uint32_t lds_per_cu);
 
 } // namespace lrsc

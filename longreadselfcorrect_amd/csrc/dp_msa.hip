@@ -430,33 +430,33 @@ __global__ __launch_bounds__(64) void dp_msa_kernel(DpPipeArgs a)
     }
 }
 
-uint32_t dp_msa_waves(const DpPipeArgs& a, bool global)
+uint32_t dp_msa_waves(const DpPipeArgs& a, bool global, uint32_t lds_per_cu)
 {
     int cus = 256, dev = 0;
     (void)hipGetDevice(&dev);
     (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-    uint32_t per_cu = global ? 8u : (a.lds_bytes ? (160u * 1024u) / a.lds_bytes : 16u);
+    uint32_t per_cu = global ? 8u : (a.lds_bytes ? lds_per_cu / a.lds_bytes : 16u);
     per_cu = per_cu < 1 ? 1 : per_cu > 32 ? 32 : per_cu;
     uint32_t n_waves = (uint32_t)cus * per_cu;
     const uint32_t n_work = a.req_list ? a.n_list : a.n_reqs;
     return n_waves > n_work ? n_work : n_waves;
 }
 
-hipError_t launch_dp_msa(const DpPipeArgs& a, hipStream_t stream)
+hipError_t launch_dp_msa(const DpPipeArgs& a, uint32_t lds_per_cu, hipStream_t stream)
 {
     const uint32_t n_work = a.req_list ? a.n_list : a.n_reqs;
     if(n_work == 0) return hipSuccess;
     if(a.msa_ws) {                                            // global-workspace variant: a.lds_bytes = bytes per workgroup slot
-        hipLaunchKernelGGL(dp_msa_kernel<true>, dim3(dp_msa_waves(a, true)), dim3(64), 0, stream, a);
+        hipLaunchKernelGGL(dp_msa_kernel<true>, dim3(dp_msa_waves(a, true, lds_per_cu)), dim3(64), 0, stream, a);
         return hipGetLastError();
     }
-    if(a.lds_bytes > 160 * 1024) return hipErrorInvalidValue;
+    if(a.lds_bytes > kLdsPerCu) return hipErrorInvalidValue;
     if(a.lds_bytes > 64 * 1024) {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(dp_msa_kernel<false>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)a.lds_bytes);
         if(e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(dp_msa_kernel<false>, dim3(dp_msa_waves(a, false)), dim3(64), a.lds_bytes, stream, a);
+    hipLaunchKernelGGL(dp_msa_kernel<false>, dim3(dp_msa_waves(a, false, lds_per_cu)), dim3(64), a.lds_bytes, stream, a);
     return hipGetLastError();
 }
 

@@ -229,6 +229,8 @@ hipError_t launch_wp_begin(const FmIndexDev& fm, const WpArgs& a, hipStream_t st
 hipError_t launch_wp_extend(const FmIndexDev& fm, const WpArgs& a, hipStream_t stream);
 // lane_stride 64 launches with the frontier across the wavefront (wp_wave.hip): one wavefront per walk in flight (a.n_lanes of them)
 hipError_t launch_wp_extend_wave(const FmIndexDev& fm, const WpArgs& a, hipStream_t stream);
+// static LDS of one workgroup of that kernel, as the code object states it
+hipError_t wp_extend_wave_static_lds(bool wide, uint32_t* bytes);
 // -l above the narrow cap (wp_wide.hip): the slots of a.list whose walk ended with LRSC_WALK_NEEDS_WIDE, and their wide launch with
 // a.max_leaves = the true -l, one walk per wavefront (a.n_lanes of them, wp_wide_layout workspaces)
 hipError_t launch_wp_wide_collect(const WpArgs& a, uint32_t* out, uint32_t* n_out, hipStream_t stream);

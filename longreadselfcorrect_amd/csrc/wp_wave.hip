@@ -403,4 +403,13 @@ hipError_t launch_wp_extend_wave(const FmIndexDev& fm, const WpArgs& a, hipStrea
     return hipGetLastError();
 }
 
+hipError_t wp_extend_wave_static_lds(bool wide, uint32_t* bytes)
+{
+    hipFuncAttributes fa{};
+    const void* f = wide ? reinterpret_cast<const void*>(wp_extend_wave_kernel<true>) : reinterpret_cast<const void*>(wp_extend_wave_kernel<false>);
+    const hipError_t e = hipFuncGetAttributes(&fa, f);
+    if(e == hipSuccess) *bytes = (uint32_t)fa.sharedSizeBytes;
+    return e;
+}
+
 } // namespace lrsc
