@@ -287,6 +287,33 @@ int lrsc_fmwalk_merge(lrsc_ctx* ctx, const char* reads, const uint64_t* read_off
                       const lrsc_fmwalk_params* p, char* merged /* n_pairs * stride */, uint64_t stride /* >= max(max_insert + 1, min_overlap) */,
                       lrsc_fmwalk_result* out);
 
+/* ---- exact irreducible read overlaps: `stride overlap` in its default mode (StriDe/overlap.cpp:126-413 without -e; Concurrency/
+ * OverlapProcess.cpp:32-109; Algorithm/OverlapAlgorithm.cpp:22-44, 270-389, 419-487, 1043-1193, 1423-1444; Algorithm/OverlapBlock.cpp:
+ * 40-70, 128-160, 182-360; BWTAlgorithms::initIntervalPair / updateBothL / updateBothR / getExtCount) ---- */
+/* One final OverlapBlock of a read (Algorithm/OverlapBlock.h): lower..upper are the inclusive ranges.interval[0], rows of the '$'
+ * interval, i.e. places in the lexicographic order of the reads (lrsc_index_lexico_order of LRSC_BWT, or of LRSC_RBWT when
+ * target_rev); the AlignFlags; contained = the block is a containment (overlap_len is the read's length).  isTargetSubstring,
+ * which the reference leaves uninitialised on this path, is 0 and not given. */
+typedef struct lrsc_overlap_block { int64_t lower, upper; uint32_t overlap_len; uint8_t target_rev, query_rev, query_comp, contained; } lrsc_overlap_block;
+/* OverlapResult of a read (Algorithm/OverlapAlgorithm.h) and its blocks[first_block .. first_block + n_blocks), in the order of
+ * overlapReadExact's output list (OverlapAlgorithm.cpp:270-344).  status: 0, or LRSC_OVERLAP_OVERFLOW when the read's lists
+ * outgrow the kernel's workspace (n_blocks is then 0). */
+typedef struct lrsc_overlap_read { uint32_t is_substring, n_blocks, status, pad; uint64_t first_block; } lrsc_overlap_read;
+#define LRSC_OVERLAP_OVERFLOW 1
+/* The kernel's limits: LRSC_ERR_UNSUPPORTED above them. */
+#define LRSC_OVERLAP_MAX_READ 2000
+#define LRSC_OVERLAP_MAX_MIN_OVERLAP 2000
+/* OverlapAlgorithm::overlapRead (OverlapAlgorithm.cpp:22-44) in exact mode with irreducible edges only, of n_reads reads (ASCII
+ * bases back to back, n_reads + 1 offsets) against the ctx's index, which holds the same reads after `stride filter`.  A read
+ * shorter than min_overlap has no blocks and is_substring 0.  The blocks of all reads stand in `blocks` in read order.
+ * LRSC_ERR_ARG for min_overlap < 2, an empty read and a base other than A,C,G,T; LRSC_ERR_UNSUPPORTED above the limits;
+ * LRSC_ERR_FORMAT when an interval leaves the strand (an index that is no BWT of a string set): on these the outputs are
+ * untouched.  LRSC_ERR_CAPACITY when block_cap is too small: *n_blocks_out is then the number of blocks needed and nothing else
+ * is written.  n_reads == 0 launches nothing.  Two launches per workspace chunk of reads, counted under LRSC_K_FIND; an interval
+ * step is two of its rank_queries. */
+int lrsc_overlap_exact(lrsc_ctx* ctx, const char* reads, const uint64_t* read_off, uint32_t n_reads, int32_t min_overlap,
+                       lrsc_overlap_read* per_read, lrsc_overlap_block* blocks, uint64_t block_cap, uint64_t* n_blocks_out);
+
 /* ---- LongReadProbe k-mer feature grid -------------------------------------------------- */
 /* reads: concatenated ACGT bytes, read_off: n_reads+1 offsets.  ks: ascending k-mer sizes
  * (the "pool", e.g. {5,9,15,17,19}), n_k <= 8.  For read r, position p, pool slot j the record

@@ -199,6 +199,9 @@ DUP_UNIQUE, DUP_SUBSTRING, DUP_FULL_LENGTH, DUP_ABSENT = range(4)
 KCORRECT_DTYPE = np.dtype([("kmer_qc", "<u4"), ("n_changed", "<u4"), ("passes", "<u4"), ("pad", "<u4")])      # lrsc_kcorrect_result
 FMWALK_DTYPE = np.dtype([("merged", "<u4"), ("length", "<u4"), ("status", "<i4", (2,)), ("max_used_leaves", "<u4", (2,)), ("coverage", "<u8", (2,)),
                          ("trimmed_length", "<u4", (2,))], align=True)      # lrsc_fmwalk_result
+OVERLAP_READ_DTYPE = np.dtype([("is_substring", "<u4"), ("n_blocks", "<u4"), ("status", "<u4"), ("pad", "<u4"), ("first_block", "<u8")])      # lrsc_overlap_read
+OVERLAP_BLOCK_DTYPE = np.dtype([("lower", "<i8"), ("upper", "<i8"), ("overlap_len", "<u4"), ("target_rev", "u1"), ("query_rev", "u1"), ("query_comp", "u1"),
+                                ("contained", "u1")])                 # lrsc_overlap_block
 assert RANK_DTYPE.itemsize == C.sizeof(RankQuery) and BIIV_DTYPE.itemsize == C.sizeof(BiInterval)
 
 
@@ -259,6 +262,7 @@ class Lrsc:
         L.lrsc_index_remove.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]
         L.lrsc_kmer_correct.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.lrsc_fmwalk_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.lrsc_overlap_exact.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         L.lrsc_params_default.argtypes = [C.c_int, C.c_int, C.POINTER(Params)]
         L.lrsc_ctx_create.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int, C.POINTER(C.c_void_p)]
         L.lrsc_ctx_destroy.argtypes = [C.c_void_p]
@@ -558,6 +562,25 @@ class Ctx:
         out = np.zeros(n_pairs, dtype=FMWALK_DTYPE)
         self.api.check(self.api.lib.lrsc_fmwalk_merge(self.h, _ptr(bases), _ptr(off), n_pairs, _ptr(params), _ptr(merged), stride, _ptr(out)), "lrsc_fmwalk_merge")
         return merged, out
+
+    def overlap_exact(self, bases: np.ndarray, off: np.ndarray, min_overlap: int = 45, block_cap: int | None = None):
+        """lrsc_overlap_exact of the reads (ASCII bases, n + 1 offsets) -> (OVERLAP_READ_DTYPE per read, OVERLAP_BLOCK_DTYPE of all
+        reads in read order).  Without block_cap the call is made again with the size it asked for when the first guess, four
+        blocks per read, is too small; with one, LRSC_ERR_CAPACITY is raised as it comes."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        n = off.size - 1
+        per_read = np.zeros(n, dtype=OVERLAP_READ_DTYPE)
+        cap = 4 * n if block_cap is None else block_cap
+        while True:
+            blocks = np.zeros(max(cap, 1), dtype=OVERLAP_BLOCK_DTYPE)
+            used = np.zeros(1, dtype=np.uint64)
+            st = self.api.lib.lrsc_overlap_exact(self.h, _ptr(bases), _ptr(off), n, min_overlap, _ptr(per_read), _ptr(blocks), cap, _ptr(used))
+            if st == -6 and block_cap is None:  # LRSC_ERR_CAPACITY
+                cap = int(used[0])
+                continue
+            self.api.check(st, "lrsc_overlap_exact")
+            return per_read, blocks[: int(used[0])].copy()
 
     def rank(self, bases: np.ndarray, idx: np.ndarray, strand: np.ndarray | int) -> np.ndarray:
         n = len(idx)

@@ -1,5 +1,5 @@
 // fm_strand.h -- one strand of a resident index as a lane sees it: what the device index tools (RL encode, merge, locate,
-// duplicate check, removal, k-mer correction, paired-end walk) share of the rank-block layout of fm_device.h.
+// duplicate check, removal, k-mer correction, paired-end walk, overlap) share of the rank-block layout of fm_device.h.
 //
 // A strand of an index is the BWT of a string set whose sentinels sort in input order: row i < n is the suffix that is read
 // i's sentinel alone.  Its image is the rank blocks (Block32 or Block64: the A,C,G,T counts before the block and two bit planes,
@@ -17,6 +17,8 @@
 //   search    block_occ: Occ(c, p) from the rank block of p; search_first, search_step: the interval of a one-base string, and
 //             the interval [lo, hi1) narrowed by one more base.  The loop around them, how it reads its bases and what it makes
 //             of an empty interval is each tool's own.
+//   counts    OccAll, block_occ_all, interval_occ_all: Occ of every symbol at the ends of an interval, with search_step's loads, for
+//             the step that keeps the same string's interval in the other strand too (fm_overlap.h)
 //
 // All functions here are LRSC_HD and free of HIP types: the kernels call them, and the drivers under tests/host_tools compile
 // the same source for the CPU.
@@ -270,6 +272,48 @@ LRSC_HD void search_step(const StrandView<Block>& S, const uint32_t* mtab, uint3
     }
     lo = (Pos)pred + (Pos)ca;
     hi1 = (Pos)pred + (Pos)cb;
+    n_rank += 2;
+    n_blk += gu == gl ? 1u : 2u;
+}
+
+// ---- the counts of every symbol: what a step needs that keeps the same string's interval in the other strand too ----
+// Occ of '$', A, C, G, T before a position, members and not an array: an index that is known only at run time would put it in
+// scratch.  k below is a symbol's rank, '$' = 0, A..T = 1..4.
+struct OccAll {
+    uint64_t d, a, c, g, t;
+};
+LRSC_HD uint64_t occ_get(const OccAll& o, uint32_t k) { return k == 0 ? o.d : pick4(k - 1, o.a, o.c, o.g, o.t); }
+LRSC_HD uint64_t occ_less_than(const OccAll& o, uint32_t k)
+{
+    return (k > 0 ? o.d : 0) + (k > 1 ? o.a : 0) + (k > 2 ? o.c : 0) + (k > 3 ? o.g : 0);
+}
+LRSC_HD OccAll occ_diff(const OccAll& u, const OccAll& l) { return OccAll{u.d - l.d, u.a - l.a, u.c - l.c, u.g - l.g, u.t - l.t}; }
+// the counts before offset `off` of block g, held in b: block_occ of the four bases and dollar_rank
+template <class Block>
+LRSC_HD OccAll block_occ_all(const StrandView<Block>& S, const Block& b, uint64_t g, uint32_t off, const uint32_t* mtab)
+{
+    OccAll o;
+    o.d = dollar_rank(S.dollars, S.n_dollars, S.dollar_dir, g, g * Block::kSyms + off);
+    o.a = block_occ(S, b, g, off, 0u, mtab);
+    o.c = block_occ(S, b, g, off, 1u, mtab);
+    o.g = block_occ(S, b, g, off, 2u, mtab);
+    o.t = block_occ(S, b, g, off, 3u, mtab);
+    return o;
+}
+// The counts at both ends of an interval of the strand, lo <= hi1 <= S.N, with search_step's loads: one rank block when both
+// ends lie in one.  search_step's new interval with `code` is strand_pred(S, code) + the base's member of l and of u.
+template <class Block>
+LRSC_HD void interval_occ_all(const StrandView<Block>& S, const uint32_t* mtab, uint64_t lo, uint64_t hi1, OccAll& l, OccAll& u, uint32_t& n_rank, uint32_t& n_blk)
+{
+    using P = typename BlockLay<Block>::pos_t;
+    const uint64_t gl = block_of<Block>((P)lo), gu = block_of<Block>((P)hi1);
+    const Block bl = S.blocks[gl];
+    l = block_occ_all(S, bl, gl, (uint32_t)((P)lo - (P)(gl * Block::kSyms)), mtab);
+    if(gu == gl) u = block_occ_all(S, bl, gl, (uint32_t)((P)hi1 - (P)(gl * Block::kSyms)), mtab);
+    else {
+        const Block bu = S.blocks[gu];
+        u = block_occ_all(S, bu, gu, (uint32_t)((P)hi1 - (P)(gu * Block::kSyms)), mtab);
+    }
     n_rank += 2;
     n_blk += gu == gl ? 1u : 2u;
 }

@@ -131,6 +131,22 @@ hipError_t launch_fmwalk_trim(const FmIndexDev& fm, const uint8_t* codes, const 
 hipError_t launch_fmwalk_walks(const FmIndexDev& fm, const uint64_t* read_off, uint32_t n_pairs, const FwParams& p, const uint8_t* strs, const uint32_t* trimmed,
                                uint32_t groups, uint8_t* ws, uint64_t ws_slice, uint8_t* best, uint64_t stride, FwWalkOut* outs, uint32_t* broken, DevCounters* ctr,
                                hipStream_t stream);
+// The exact irreducible overlaps of n_reads reads (fm_overlap.hip), codes / read_off as above, no read longer than p.max_len.
+// launch_overlap_collect, a lane per chain and four chains per read: heads[4 r + c] and chain_blocks + (4 r + c) * ov_slots(p) =
+// what chain c of read r found.  launch_overlap_reduce, a wavefront per read: `groups` workgroups of kOvThreads, every wavefront
+// with its own ws_slice >= ov_workspace_bytes(p) bytes of ws, take the reads in turn; outs[r] = the read's result, its final
+// blocks at pool + outs[r].first_block, a place taken from *pool_used (the caller zeroes it; pool_cap >= n_reads * kOvOutCap).
+// *broken is set to 1 when an interval leaves the strand.
+struct OvParams;
+struct OvChainHead;
+struct OvBlock;
+struct OvOutRead;
+struct OvOutBlock;
+hipError_t launch_overlap_collect(const FmIndexDev& fm, const uint8_t* codes, const uint64_t* read_off, uint32_t n_reads, const OvParams& p, uint32_t groups,
+                                  OvChainHead* heads, OvBlock* chain_blocks, uint32_t* broken, DevCounters* ctr, hipStream_t stream);
+hipError_t launch_overlap_reduce(const FmIndexDev& fm, const uint64_t* read_off, uint32_t n_reads, const OvParams& p, const OvChainHead* heads, const OvBlock* chain_blocks,
+                                 uint32_t groups, uint8_t* ws, uint64_t ws_slice, OvOutRead* outs, OvOutBlock* pool, uint64_t pool_cap, unsigned long long* pool_used,
+                                 uint32_t* broken, DevCounters* ctr, hipStream_t stream);
 hipError_t launch_bwt_chars(const FmIndexDev& fm, int strand, const uint64_t* idx, uint64_t n, char* out,
                             hipStream_t stream);
 hipError_t launch_find_kmers(const FmIndexDev& fm, const uint8_t* kmer_codes, uint32_t k, uint64_t n,

@@ -1,5 +1,5 @@
 // stride_main.cpp -- `stride pbcorrect` (a.k.a. PacBioSelfCorrection), `stride index`, `stride merge`, `stride sai`,
-// `stride grep`, `stride filter`, `stride correct` and `stride fmwalk` on the MI355X back end.  Option surface, defaults, validation messages and exit codes follow the reference's
+// `stride grep`, `stride filter`, `stride correct`, `stride fmwalk` and `stride overlap` on the MI355X back end.  Option surface, defaults, validation messages and exit codes follow the reference's
 // StriDe/PacBioSelfCorrection.cpp:32-140,262-434 and StriDe/StriDe.cpp:62-126; extra flags: --devices, --batch.
 #include <getopt.h>
 
@@ -19,6 +19,7 @@
 #include "ErrorCorrectProcess.h"
 #include "FMIndexWalkProcess.h"
 #include "LexicoOrder.h"
+#include "OverlapProcess.h"
 #include "PacBioSelfCorrectionProcess.h"
 #include "QCProcess.h"
 #include "SequenceProcessFramework.h"
@@ -1115,13 +1116,185 @@ static int fmwalkMain(int argc, char** argv)
     return 0;
 }
 
+// `stride overlap READSFILE`: the reference's overlap (StriDe/overlap.cpp:126-413) in its default mode, errorRate = -1: the exact
+// algorithm, irreducible edges only, the output of -t 1.  The overlap blocks come from the device, a batch of reads per
+// lrsc_overlap_exact call (OverlapProcess.h); the lexicographic order of the reads comes from the index, not from .sai / .rsai.
+// -e, -a, -l and -f are not built.  Not taken over: the time stamps.
+static const char* OVERLAP_USAGE_MESSAGE =
+    "Usage: " PACKAGE_NAME " overlap [OPTION] ... READSFILE\n"
+    "Compute pairwise overlap between all the sequences in READS\n"
+    "\n"
+    "      --help                           display this help and exit\n"
+    "      -v, --verbose                    display verbose output\n"
+    "      -t, --threads=NUM                use NUM worker threads to compute the overlaps (default: 1)\n"
+    "      -e, --error-rate                 the maximum error rate allowed to consider two sequences aligned (default: 0)\n"
+    "      -m, --min-overlap=LEN            minimum overlap required between two reads (default: 45)\n"
+    "      -f, --target-file=FILE           perform the overlap queries against the reads in FILE\n"
+    "      -a, --algorithm=STR              LSSF: locality-sensitive search by FM-index (default);\n"
+    "                                       ADPF: approximate dynamic programming by FM-index\n"
+    "      -x, --exhaustive                 output all overlaps, including transitive edges (default if e>0)\n"
+    "          --exact                      output irreducible overlaps (default if e=0)\n"
+    "      -l, --maxindel                   maximum indels allowed during inexact overlap computation\n"
+    "      -p, --prefix=PREFIX              use PREFIX for the names of the index files (default: prefix of the input file)\n"
+    "      -o, --outfile=FILE               write the graph to FILE (default: READSFILE.asqg.gz)\n"
+    "      --build-index                    index READSFILE in memory on the device instead of loading PREFIX.bwt/.rbwt\n"
+    "      --load-on-device                 decode PREFIX.bwt/.rbwt on the device (what loading does here; accepted for symmetry)\n"
+    "      --device=N                       HIP device to work on (default: 0)\n"
+    "\nReport bugs to " PACKAGE_BUGREPORT "\n\n";
+
+namespace overlapopt {
+static unsigned int verbose = 0;
+static int numThreads = 1, sampleRate = 128, device = 0;
+static unsigned int minOverlap = 45;
+static std::string prefix, readsFile, outFile;
+static bool buildIndex = false;
+static const size_t batch = 100000;                             // reads per device call
+}
+
+static void parseOverlapOptions(int argc, char** argv)
+{
+    enum { O_HELP = 1, O_VERSION, O_EXACT, O_DEVICE, O_BUILDINDEX, O_LOADONDEVICE };
+    static const struct option overlap_longopts[] = {
+        {"verbose", no_argument, nullptr, 'v'},               {"threads", required_argument, nullptr, 't'},
+        {"min-overlap", required_argument, nullptr, 'm'},     {"sample-rate", required_argument, nullptr, 'd'},
+        {"outfile", required_argument, nullptr, 'o'},         {"target-file", required_argument, nullptr, 'f'},
+        {"prefix", required_argument, nullptr, 'p'},          {"error-rate", required_argument, nullptr, 'e'},
+        {"maxindel", required_argument, nullptr, 'l'},        {"algorithm", required_argument, nullptr, 'a'},
+        {"exhaustive", no_argument, nullptr, 'x'},            {"exact", no_argument, nullptr, O_EXACT},
+        {"help", no_argument, nullptr, O_HELP},               {"version", no_argument, nullptr, O_VERSION},
+        {"device", required_argument, nullptr, O_DEVICE},     {"build-index", no_argument, nullptr, O_BUILDINDEX},
+        {"load-on-device", no_argument, nullptr, O_LOADONDEVICE},
+        {nullptr, 0, nullptr, 0}};
+    optind = 1;
+    bool die = false;
+    for(int c; (c = getopt_long(argc, argv, "m:d:e:t:l:o:f:a:p:vx", overlap_longopts, nullptr)) != -1;) {
+        std::istringstream arg(optarg != nullptr ? optarg : "");
+        switch(c) {
+            case 'm': arg >> overlapopt::minOverlap; break;
+            case 'o': arg >> overlapopt::outFile; break;
+            case 'p': arg >> overlapopt::prefix; break;
+            case 't': arg >> overlapopt::numThreads; break;
+            case 'd': arg >> overlapopt::sampleRate; break;
+            case 'v': overlapopt::verbose++; break;
+            // errorRate stays -1, where the reference turns irreducible-only back on whatever -x said; --exact sets a flag it never reads
+            case 'x': case O_EXACT: case O_LOADONDEVICE: break;
+            case 'e': case 'a': case 'l': case 'f':
+                std::cerr << "overlap: -" << (char)c << " is not built here: only the exact overlap of a reads file with itself is\n";
+                die = true;
+                break;
+            case O_DEVICE: arg >> overlapopt::device; break;
+            case O_BUILDINDEX: overlapopt::buildIndex = true; break;
+            case O_HELP: std::cout << OVERLAP_USAGE_MESSAGE; exit(EXIT_SUCCESS);
+            case O_VERSION: std::cout << "overlap Version " PACKAGE_VERSION " (MI355X back end)\n"; exit(EXIT_SUCCESS);
+            default: die = true; break;
+        }
+    }
+    if(argc - optind < 1) { std::cerr << "overlap: missing arguments\n"; die = true; }
+    else if(argc - optind > 1) { std::cerr << "overlap: too many arguments\n"; die = true; }
+    if(overlapopt::numThreads <= 0) { std::cerr << "overlap: invalid number of threads: " << overlapopt::numThreads << "\n"; die = true; }
+    if((overlapopt::sampleRate & (overlapopt::sampleRate - 1)) != 0) {
+        std::cerr << "overlap: invalid parameter to -d/--sample-rate, must be power of 2. got: " << overlapopt::sampleRate << "\n";
+        die = true;
+    }
+    if(die) { std::cout << "\n" << OVERLAP_USAGE_MESSAGE; exit(EXIT_FAILURE); }
+    overlapopt::readsFile = argv[optind++];
+    if(overlapopt::prefix.empty()) overlapopt::prefix = getFilename(overlapopt::readsFile);
+    if(overlapopt::outFile.empty()) overlapopt::outFile = getFilename(overlapopt::readsFile) + ".asqg.gz";
+}
+
+static int overlapMain(int argc, char** argv)
+{
+    parseOverlapOptions(argc, argv);
+    const int device = overlapopt::device;
+    // ReadInfoTable: the id and the length of every read of the file
+    std::vector<std::string> ids;
+    std::vector<uint32_t> lengths;
+    {
+        SeqReader reader(overlapopt::readsFile, true);
+        SeqRecord r;
+        while(reader.get(r)) { ids.push_back(r.id); lengths.push_back((uint32_t)r.seq.size()); }
+    }
+    lrsc_index* idx = nullptr;
+    if(overlapopt::buildIndex) {
+        std::string bases;
+        std::vector<uint64_t> off;
+        loadReads(overlapopt::readsFile, bases, off);
+        lrscOrDie(lrsc_index_build(bases.data(), off.data(), (uint32_t)(off.size() - 1), device, &idx), "lrsc_index_build");
+    } else {
+        std::cout << std::endl << "Loading BWT: " << overlapopt::prefix + BWT_EXT << "\n";
+        std::cout << "Loading RBWT: " << overlapopt::prefix + RBWT_EXT << "\n";
+        lrscOrDie(lrsc_index_open_device((overlapopt::prefix + BWT_EXT).c_str(), (overlapopt::prefix + RBWT_EXT).c_str(), device, &idx), "lrsc_index_open_device");
+    }
+    lrsc_index_info info;
+    lrscOrDie(lrsc_index_info_get(idx, &info), "lrsc_index_info_get");
+    if(info.num_strings != ids.size()) {
+        std::cerr << "overlap: " << overlapopt::readsFile << " holds " << ids.size() << " reads, the index " << info.num_strings << ": the index is not that of these reads\n";
+        lrsc_index_close(idx);
+        return EXIT_FAILURE;
+    }
+    std::vector<uint32_t> order[2];
+    for(int rev = 0; rev < 2; ++rev) {
+        order[rev].resize(ids.size());
+        lrscOrDie(lrsc_index_lexico_order(idx, rev ? LRSC_RBWT : LRSC_BWT, device, order[rev].data(), nullptr), "lrsc_index_lexico_order");
+    }
+    lrsc_ctx* ctx = nullptr;
+    lrscOrDie(lrsc_ctx_create(idx, nullptr, device, &ctx), "lrsc_ctx_create");
+
+    const std::string edgesFile = getFilename(overlapopt::readsFile) + "-thread0.edges.gz";
+    gzFile asqg = gzopen(overlapopt::outFile.c_str(), "wb"), edges = gzopen(edgesFile.c_str(), "wb");
+    if(!asqg || !edges) { std::cerr << "Error: could not open " << (asqg ? edgesFile : overlapopt::outFile) << " for write\n"; return EXIT_FAILURE; }
+    {
+        std::ostringstream header;                                // HeaderRecord::write
+        header << "HT\tVN:i:1\tER:f:-1\tOL:i:" << overlapopt::minOverlap << "\tIN:Z:" << overlapopt::readsFile << "\tCN:i:1\tTE:i:0\n";
+        if(!gzPut(asqg, header.str())) { std::cerr << "Error: could not write " << overlapopt::outFile << "\n"; return EXIT_FAILURE; }
+    }
+    std::cout << "StriDe overlap computation using min overlap: " << overlapopt::minOverlap << "\n"
+              << "Error Rate: -1\n"
+              << "Max Indel: 0\n"
+              << "Transitive reduction: 1\n"
+              << "Algorithm: LSSF\n";
+    OverlapParameters params;
+    params.ctx = ctx;
+    params.minOverlap = (int)overlapopt::minOverlap;
+    params.order[0] = &order[0];
+    params.order[1] = &order[1];
+    params.ids = &ids;
+    params.lengths = &lengths;
+    bool ok = true;
+    {
+        OverlapProcess processor(params, edges);
+        OverlapPostProcess post(asqg);
+        SeqReader reader(overlapopt::readsFile, true);
+        WorkItemGenerator<SequenceWorkItem> generator(&reader);
+        std::vector<SequenceWorkItem> items;
+        std::vector<OverlapResult> results;
+        for(bool more = true; more && ok;) {
+            items.clear();
+            SequenceWorkItem item;
+            while(items.size() < overlapopt::batch && (more = generator.generate(item))) items.push_back(item);
+            ok = processor.process_batch(items, results);
+            for(size_t i = 0; ok && i < items.size(); ++i) ok = post.process(items[i], results[i]);
+        }
+    }
+    ok = (gzclose(asqg) == Z_OK) && ok;
+    ok = (gzclose(edges) == Z_OK) && ok;
+    std::cout.flush();
+    lrsc_ctx_destroy(ctx);
+    lrsc_index_close(idx);
+    if(!ok) {
+        std::cerr << "overlap: the run ended early: " << overlapopt::outFile << " and " << edgesFile << " are not complete\n";
+        return EXIT_FAILURE;
+    }
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
     // several workers on one device (--devices 0,0) only overlap if their streams get hardware queues of their own (default: 4)
     setenv("GPU_MAX_HW_QUEUES", "16", 0);
-    if(argc <= 1) { std::cerr << "Usage: " PACKAGE_NAME " <command> [options]\nCommands: index, merge, sai, grep, filter, correct, pbcorrect, kmerfreq, kmercheck\n          and fmwalk\n"; return EXIT_FAILURE; }
+    if(argc <= 1) { std::cerr << "Usage: " PACKAGE_NAME " <command> [options]\nCommands: index, merge, sai, grep, filter, correct, pbcorrect, kmerfreq, kmercheck\n          and fmwalk\n          and overlap\n"; return EXIT_FAILURE; }
     const std::string command(argv[1]);
-    if(command == "help" || command == "--help") { std::cout << "Usage: " PACKAGE_NAME " <command> [options]\nCommands: index, merge, sai, grep, filter, correct, pbcorrect, kmerfreq, kmercheck\n          and fmwalk\n"; return 0; }
+    if(command == "help" || command == "--help") { std::cout << "Usage: " PACKAGE_NAME " <command> [options]\nCommands: index, merge, sai, grep, filter, correct, pbcorrect, kmerfreq, kmercheck\n          and fmwalk\n          and overlap\n"; return 0; }
     if(command == "pbcorrect" || command == SUBPROGRAM) return PacBioSelfCorrectionMain(argc - 1, argv + 1);
     if(command == "index") return indexMain(argc - 1, argv + 1);
     if(command == "merge") return mergeMain(argc - 1, argv + 1);
@@ -1130,6 +1303,7 @@ int main(int argc, char** argv)
     if(command == "filter") return filterMain(argc - 1, argv + 1);
     if(command == "correct") return correctMain(argc - 1, argv + 1);
     if(command == "fmwalk") return fmwalkMain(argc - 1, argv + 1);
+    if(command == "overlap") return overlapMain(argc - 1, argv + 1);
     if(command == "kmerfreq") return kmerfreqMain(argc - 1, argv + 1);
     if(command == "kmercheck") return kmercheckMain(argc - 1, argv + 1);
     std::cerr << "Unrecognized command: " << command << "\n";
