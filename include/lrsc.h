@@ -287,6 +287,56 @@ int lrsc_fmwalk_merge(lrsc_ctx* ctx, const char* reads, const uint64_t* read_off
                       const lrsc_fmwalk_params* p, char* merged /* n_pairs * stride */, uint64_t stride /* >= max(max_insert + 1, min_overlap) */,
                       lrsc_fmwalk_result* out);
 
+/* ---- fmwalk's hybrid and kmerize algorithms: reads cut at their unreliable k-mers (FMIndexWalk/FMIndexWalkProcess.cpp:29-150,
+ * 229-267, 394-477, 555-609, 855-881; FMIndexWalkProcess.h:61-130) and the sampled k-mer counts that hybrid's repeat gate reads
+ * (StriDe/FMIndexWalk.cpp:147-154; SuffixTools/BWTAlgorithms.cpp:135-141, 396-402, 454-469, 527-539) ---------------------------- */
+/* One piece of a read (an element of splitRead's kmerReads): read[start .. start + length) of the untrimmed read; kept = 0 when
+ * hybrid's isLowComplexity or maxCon filter drops it. */
+typedef struct lrsc_fmwalk_piece { uint32_t start, length, kept; } lrsc_fmwalk_piece;
+/* What the algorithms leave of one read: kmerize (FMIndexWalkResult::kmerize or kmerize2); the trimmed read is read[head .. head
+ * + length) (hybrid; kmerize does not trim: 0 and the read's length, or 0 and 0 for a read shorter than kmer_length); its
+ * n_pieces pieces in read order; main_piece = splitRead's mainSeedIdx, -1 for none; whole = the [k, m] length gate has set
+ * correctSequence to the whole trimmed read.  correctSequence is the main piece when there is one and it is kept, else the
+ * trimmed read when whole, else empty; kmerizedReads are the other kept pieces in order. */
+typedef struct lrsc_fmwalk_read_result { uint32_t kmerize; int32_t head; uint32_t length, n_pieces; int32_t main_piece; uint32_t whole; } lrsc_fmwalk_read_result;
+typedef struct lrsc_fmwalk_hybrid_result { lrsc_fmwalk_result walk; lrsc_fmwalk_read_result read[2]; } lrsc_fmwalk_hybrid_result;
+#define LRSC_KMER_SAMPLE_MAX_LENGTH 4096
+/* BWTAlgorithms::sampleKmerCounts (BWTAlgorithms.cpp:527-539) without its rand(): for each of the n rows, rows[i] < the index's
+ * strings, extractString(pRBWT, rows[i], len) (454-469: up to len LF steps from the '$' row, ending at '$') and
+ * countSequenceOccurrences of that string in .rbwt (135-141), to counts[i] (saturating at 2^32 - 1).  LRSC_ERR_ARG for len == 0 or
+ * a row that is none of the '$' rows, LRSC_ERR_UNSUPPORTED for len above LRSC_KMER_SAMPLE_MAX_LENGTH; on an error counts is
+ * untouched.  n == 0 does nothing.  The launch is counted under LRSC_K_FIND. */
+int lrsc_kmer_sample_counts(lrsc_ctx* ctx, const uint64_t* rows, uint32_t n, uint32_t len, uint32_t* counts);
+/* FMIndexWalkProcess::KmerizeReads (FMIndexWalkProcess.cpp:229-267) for n_reads single reads: no trim, no filters.  A read is cut
+ * (splitRead(KmerContext&), 555-609) at every boundary between two k-mers that are not both solid (kmer_threshold occurrences
+ * in .bwt or more of the k-mer and as many of its reverse complement) and whose link is not simple (isSimple, 873-881: exactly
+ * one base extends the left k-mer to the right and exactly one the right k-mer to the left, counted on both strands together with
+ * a threshold of 1).  The main piece is the first of the pieces with the most k-mers among those that hold a solid k-mer and have
+ * more than one k-mer.  Read i's
+ * pieces stand from pieces[slot_i] on, slot_i = the sum over the reads j < i of max(len_j - kmer_length + 1, 0); n_piece_slots
+ * is the size of pieces and at least that sum over all reads (LRSC_ERR_ARG below it).  A read shorter than kmer_length gives
+ * nothing (kmerize 0).  Errors as lrsc_fmwalk_merge; on an error out and pieces are untouched; entries of pieces beyond a read's
+ * n_pieces are never written. */
+int lrsc_fmwalk_kmerize(lrsc_ctx* ctx, const char* reads, const uint64_t* read_off, uint32_t n_reads, int32_t kmer_length, int32_t kmer_threshold,
+                        lrsc_fmwalk_read_result* out, lrsc_fmwalk_piece* pieces, uint64_t n_piece_slots);
+/* FMIndexWalkProcess::MergeAndKmerize (FMIndexWalkProcess.cpp:29-150) for n_pairs pairs, reads and merged as lrsc_fmwalk_merge's.
+ * Both reads are trimmed; when a trimmed length lies in [kmer_length, min_overlap] both reads are marked kmerized with their
+ * whole trimmed reads, and the pair goes on; otherwise a pair with a trimmed read shorter than kmer_length ends there.  The pair
+ * is walked (isSuitableForFMWalk, 394-415) when both trimmed reads reach min_overlap and the first min_overlap-mer of each occurs
+ * fewer than repeat_kmer_freq times in .bwt on both strands together; the walks are lrsc_fmwalk_merge's with the constructor's
+ * default threshold of 3 whatever kmer_threshold says, and max_overlap -1 standing for 0.95 of the mean untrimmed length.  It is
+ * merged when one walk alone has a string and neither used more than one leaf, or both have one and one is the other's reverse
+ * complement (then walk 0's if its coverage is greater).  Otherwise both trimmed reads of kmer_length bases or more are split as
+ * by lrsc_fmwalk_kmerize, with the pieces' filters: isLowComplexity (418-445: a base makes up 0.9 of the piece or more, as a float
+ * quotient against the double 0.9, so exactly nine tenths is kept) and maxCon(piece) * 3 > length (448-477).
+ * out[i].walk is lrsc_fmwalk_merge's record (status 0 for a pair that is not walked); out[i].read[] as above, kmerize and whole as
+ * the gate left them even when the pair is merged.  The pieces' slots are computed from the untrimmed lengths.  A read shorter than
+ * kmer_length, on which the reference throws, counts as trimmed to nothing.  Errors as lrsc_fmwalk_merge; on an error merged, out
+ * and pieces are untouched. */
+int lrsc_fmwalk_hybrid(lrsc_ctx* ctx, const char* reads, const uint64_t* read_off, uint32_t n_pairs /* reads 2i, 2i+1 */, const lrsc_fmwalk_params* p,
+                       uint64_t repeat_kmer_freq, char* merged /* n_pairs * stride */, uint64_t stride, lrsc_fmwalk_hybrid_result* out,
+                       lrsc_fmwalk_piece* pieces, uint64_t n_piece_slots);
+
 /* ---- exact irreducible read overlaps: `stride overlap` in its default mode (StriDe/overlap.cpp:126-413 without -e; Concurrency/
  * OverlapProcess.cpp:32-109; Algorithm/OverlapAlgorithm.cpp:22-44, 270-389, 419-487, 1043-1193, 1423-1444; Algorithm/OverlapBlock.cpp:
  * 40-70, 128-160, 182-360; BWTAlgorithms::initIntervalPair / updateBothL / updateBothR / getExtCount) ---- */

@@ -199,10 +199,19 @@ DUP_UNIQUE, DUP_SUBSTRING, DUP_FULL_LENGTH, DUP_ABSENT = range(4)
 KCORRECT_DTYPE = np.dtype([("kmer_qc", "<u4"), ("n_changed", "<u4"), ("passes", "<u4"), ("pad", "<u4")])      # lrsc_kcorrect_result
 FMWALK_DTYPE = np.dtype([("merged", "<u4"), ("length", "<u4"), ("status", "<i4", (2,)), ("max_used_leaves", "<u4", (2,)), ("coverage", "<u8", (2,)),
                          ("trimmed_length", "<u4", (2,))], align=True)      # lrsc_fmwalk_result
+FMWALK_PIECE_DTYPE = np.dtype([("start", "<u4"), ("length", "<u4"), ("kept", "<u4")])      # lrsc_fmwalk_piece
+FMWALK_READ_DTYPE = np.dtype([("kmerize", "<u4"), ("head", "<i4"), ("length", "<u4"), ("n_pieces", "<u4"), ("main_piece", "<i4"), ("whole", "<u4")])      # lrsc_fmwalk_read_result
+FMWALK_HYBRID_DTYPE = np.dtype([("walk", FMWALK_DTYPE), ("read", FMWALK_READ_DTYPE, (2,))], align=True)      # lrsc_fmwalk_hybrid_result
 OVERLAP_READ_DTYPE = np.dtype([("is_substring", "<u4"), ("n_blocks", "<u4"), ("status", "<u4"), ("pad", "<u4"), ("first_block", "<u8")])      # lrsc_overlap_read
 OVERLAP_BLOCK_DTYPE = np.dtype([("lower", "<i8"), ("upper", "<i8"), ("overlap_len", "<u4"), ("target_rev", "u1"), ("query_rev", "u1"), ("query_comp", "u1"),
                                 ("contained", "u1")])                 # lrsc_overlap_block
 assert RANK_DTYPE.itemsize == C.sizeof(RankQuery) and BIIV_DTYPE.itemsize == C.sizeof(BiInterval)
+
+
+def piece_slots(off: np.ndarray, kmer_length: int) -> np.ndarray:
+    """the first piece slot of every read and, last, the number of slots: the running sum of max(len - kmer_length + 1, 0)"""
+    lens = np.diff(np.asarray(off, dtype=np.int64))
+    return np.concatenate([[0], np.cumsum(np.maximum(lens - max(kmer_length, 1) + 1, 0))]).astype(np.uint64)
 
 
 def declared_symbols(header: Path | None = None) -> list[str]:
@@ -262,6 +271,10 @@ class Lrsc:
         L.lrsc_index_remove.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_void_p)]
         L.lrsc_kmer_correct.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.lrsc_fmwalk_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.lrsc_kmer_sample_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        L.lrsc_fmwalk_kmerize.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64]
+        L.lrsc_fmwalk_hybrid.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                         C.c_uint64]
         L.lrsc_overlap_exact.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         L.lrsc_params_default.argtypes = [C.c_int, C.c_int, C.POINTER(Params)]
         L.lrsc_ctx_create.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int, C.POINTER(C.c_void_p)]
@@ -562,6 +575,45 @@ class Ctx:
         out = np.zeros(n_pairs, dtype=FMWALK_DTYPE)
         self.api.check(self.api.lib.lrsc_fmwalk_merge(self.h, _ptr(bases), _ptr(off), n_pairs, _ptr(params), _ptr(merged), stride, _ptr(out)), "lrsc_fmwalk_merge")
         return merged, out
+
+    def kmer_sample_counts(self, rows: np.ndarray, length: int) -> np.ndarray:
+        """lrsc_kmer_sample_counts: for each '$' row of .rbwt the occurrences, on both strands, of the up to `length` bases before it"""
+        rows = np.ascontiguousarray(rows, dtype=np.uint64)
+        counts = np.zeros(rows.size, dtype=np.uint32)
+        self.api.check(self.api.lib.lrsc_kmer_sample_counts(self.h, _ptr(rows), rows.size, length, _ptr(counts)), "lrsc_kmer_sample_counts")
+        return counts
+
+    def fmwalk_kmerize(self, bases: np.ndarray, off: np.ndarray, kmer_length: int = 31, kmer_threshold: int = 3):
+        """lrsc_fmwalk_kmerize of the reads (ASCII bases, n + 1 offsets) -> (FMWALK_READ_DTYPE per read, FMWALK_PIECE_DTYPE of all
+        slots, the reads' first slots: read i's pieces are pieces[slots[i] : slots[i] + n_pieces])."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        n = off.size - 1
+        slots = piece_slots(off, kmer_length)
+        out = np.zeros(n, dtype=FMWALK_READ_DTYPE)
+        pieces = np.zeros(max(int(slots[-1]), 1), dtype=FMWALK_PIECE_DTYPE)
+        self.api.check(self.api.lib.lrsc_fmwalk_kmerize(self.h, _ptr(bases), _ptr(off), n, kmer_length, kmer_threshold, _ptr(out), _ptr(pieces), int(slots[-1])),
+                       "lrsc_fmwalk_kmerize")
+        return out, pieces, slots
+
+    def fmwalk_hybrid(self, bases: np.ndarray, off: np.ndarray, repeat_kmer_freq: int, kmer_length: int = 31, kmer_threshold: int = 3, min_overlap: int = 81,
+                      max_overlap: int = -1, max_insert: int = 400, max_leaves: int = 32, stride: int | None = None):
+        """lrsc_fmwalk_hybrid of the pairs (as fmwalk_merge's) -> (the merged strings, one row of `stride` bytes per pair;
+        FMWALK_HYBRID_DTYPE per pair; FMWALK_PIECE_DTYPE of all slots; the reads' first slots)."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        assert off.size % 2 == 1
+        n_pairs = (off.size - 1) // 2
+        if stride is None:
+            stride = max(max_insert + 1, min_overlap, 1)
+        params = np.array([kmer_length, kmer_threshold, min_overlap, max_overlap, max_insert, max_leaves], dtype=np.int32)
+        slots = piece_slots(off, kmer_length)
+        merged = np.zeros((n_pairs, stride), dtype=np.uint8)
+        out = np.zeros(n_pairs, dtype=FMWALK_HYBRID_DTYPE)
+        pieces = np.zeros(max(int(slots[-1]), 1), dtype=FMWALK_PIECE_DTYPE)
+        self.api.check(self.api.lib.lrsc_fmwalk_hybrid(self.h, _ptr(bases), _ptr(off), n_pairs, _ptr(params), repeat_kmer_freq, _ptr(merged), stride, _ptr(out),
+                                                       _ptr(pieces), int(slots[-1])), "lrsc_fmwalk_hybrid")
+        return merged, out, pieces, slots
 
     def overlap_exact(self, bases: np.ndarray, off: np.ndarray, min_overlap: int = 45, block_cap: int | None = None):
         """lrsc_overlap_exact of the reads (ASCII bases, n + 1 offsets) -> (OVERLAP_READ_DTYPE per read, OVERLAP_BLOCK_DTYPE of all

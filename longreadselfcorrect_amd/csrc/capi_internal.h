@@ -198,6 +198,9 @@ struct lrsc_ctx {
     // lrsc_fmwalk_merge's: the wavefronts' workspace, the walks' start and end strings, their strings, the trimmed lengths
     lrsc::DevBuf<uint8_t> fw_ws, fw_strs, fw_best, fw_outs;
     lrsc::DevBuf<uint32_t> fw_trimmed;
+    // lrsc_fmwalk_hybrid's, lrsc_fmwalk_kmerize's and lrsc_kmer_sample_counts': the splits' workspace, jobs, pieces and results, the
+    // pairs' gates, the samples' rows and counts
+    lrsc::DevBuf<uint8_t> km_ws, km_jobs, km_pieces, km_outs, km_gates, km_rows, km_counts;
     // lrsc_overlap_exact's: the wavefronts' workspace, the chains' heads and blocks, the reads' results, the pool of final blocks
     // behind its 8-byte counter
     lrsc::DevBuf<uint8_t> ov_ws, ov_heads, ov_chain, ov_outs, ov_pool;

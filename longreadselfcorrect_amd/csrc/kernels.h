@@ -131,6 +131,30 @@ hipError_t launch_fmwalk_trim(const FmIndexDev& fm, const uint8_t* codes, const 
 hipError_t launch_fmwalk_walks(const FmIndexDev& fm, const uint64_t* read_off, uint32_t n_pairs, const FwParams& p, const uint8_t* strs, const uint32_t* trimmed,
                                uint32_t groups, uint8_t* ws, uint64_t ws_slice, uint8_t* best, uint64_t stride, FwWalkOut* outs, uint32_t* broken, DevCounters* ctr,
                                hipStream_t stream);
+// The hybrid and kmerize algorithms of fmwalk and the sampled k-mer counts (fm_kmerize.hip), codes / read_off as above.
+// launch_kmerize_split, a wavefront per job: `groups` workgroups of kKmThreads, every wavefront with its own ws_slice >=
+// km_workspace_bytes(longest job) bytes of ws, take the jobs in turn; outs[job] = the pieces' number and the main one,
+// pieces + jobs[job].slot = the pieces, of which a job needs len - k + 1 slots at the most.
+// launch_hybrid_gate, a wavefront per pair: gates[i] = the trims and what MergeAndKmerize decides before its walks, and for a
+// pair that is to be walked strs + i * 4 * m4 = the four strings of its walks.  launch_hybrid_walks: launch_fmwalk_walks for the
+// pairs whose gate says so, with MergeAndKmerize's maxOverlap.
+// launch_kmer_sample, a lane per sample: counts[i] = the occurrences in .rbwt, on both strands, of the up to `len` bases before
+// '$' row rows[i] < the index's strings; ws holds n * len bytes.
+// *broken is set to 1 when an interval leaves the strand.
+struct KmJob;
+struct KmJobOut;
+struct KmPiece;
+struct KmGate;
+hipError_t launch_kmerize_split(const FmIndexDev& fm, const uint8_t* codes, const uint64_t* read_off, const KmJob* jobs, uint32_t n_jobs, uint32_t k, uint32_t threshold,
+                                bool filters, uint32_t groups, uint8_t* ws, uint64_t ws_slice, uint32_t longest, KmPiece* pieces, KmJobOut* outs, uint32_t* broken,
+                                DevCounters* ctr, hipStream_t stream);
+hipError_t launch_hybrid_gate(const FmIndexDev& fm, const uint8_t* codes, const uint64_t* read_off, uint32_t n_pairs, const FwParams& p, uint64_t repeat_kmer_freq,
+                              uint8_t* strs, KmGate* gates, uint32_t* broken, DevCounters* ctr, hipStream_t stream);
+hipError_t launch_hybrid_walks(const FmIndexDev& fm, const uint64_t* read_off, uint32_t n_pairs, const FwParams& p, const uint8_t* strs, const KmGate* gates,
+                               uint32_t groups, uint8_t* ws, uint64_t ws_slice, uint8_t* best, uint64_t stride, FwWalkOut* outs, uint32_t* broken, DevCounters* ctr,
+                               hipStream_t stream);
+hipError_t launch_kmer_sample(const FmIndexDev& fm, const uint64_t* rows, uint32_t n, uint32_t len, uint8_t* ws, uint32_t* counts, uint32_t* broken, DevCounters* ctr,
+                              hipStream_t stream);
 // The exact irreducible overlaps of n_reads reads (fm_overlap.hip), codes / read_off as above, no read longer than p.max_len.
 // launch_overlap_collect, a lane per chain and four chains per read: heads[4 r + c] and chain_blocks + (4 r + c) * ov_slots(p) =
 // what chain c of read r found.  launch_overlap_reduce, a wavefront per read: `groups` workgroups of kOvThreads, every wavefront

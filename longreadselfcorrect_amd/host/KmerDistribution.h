@@ -1,6 +1,7 @@
 // KmerDistribution.h -- histogram of k-mer frequencies with the five-number summary `stride kmercheck` prints
 // (the part of the reference's Util/KmerDistribution.{h,cpp}:25-31,86-153 that kmercheck uses: add, +=, computeKDAttributes,
-// operator<<, compare).
+// operator<<, compare) and what `stride fmwalk --hybrid` prints of its sample (getQuartile, getSdv, getCutoffForProportion,
+// getRepeatKmerCutoff: KmerDistribution.cpp:38-49, 64-82, 129).
 #pragma once
 #include <cmath>
 #include <map>
@@ -17,6 +18,20 @@ public:
         m_total += other.m_total;
     }
     int getTotalKmers() const { return m_total; }
+    int getQuartile(int n) const { return n == 1 ? m_q1 : n == 2 ? m_q2 : m_q3; }
+    double getSdv() const { return m_sdv; }
+    int getRepeatKmerCutoff() const { return m_repeatKmerCutoff; }
+    // the first frequency at which the cumulative proportion exceeds p, the largest when none does
+    int getCutoffForProportion(double p) const
+    {
+        int kmerFreq = 0, cumulativeSum = 0;
+        for(const auto& kv : m_data) {
+            kmerFreq = kv.first;
+            cumulativeSum += kv.second;
+            if((double)cumulativeSum / m_total > p) break;
+        }
+        return kmerFreq;
+    }
 
     // Quartiles by cumulative count (a quartile is the LAST frequency whose [before, after] count range contains the rank, so
     // ties move it up), whiskers at 1.5 IQR (min: first frequency >= q1 - 1.5 IQR, taken only while still 0; max: the
@@ -47,6 +62,7 @@ public:
         int sqsum = 0;
         for(const auto& kv : m_data) sqsum += kv.second * std::pow((kv.first - m_q2), 2);      // int += double, truncating each time
         m_sdv = std::sqrt((double)sqsum / (m_total - 1));
+        m_repeatKmerCutoff = m_q2 * 1.3;                          // int <- double
     }
 
     friend std::ostream& operator<<(std::ostream& out, const KmerDistribution& o)
@@ -67,7 +83,7 @@ public:
 
 private:
     std::map<int, int> m_data;
-    int m_total = 0, m_q1 = 0, m_q2 = 0, m_q3 = 0, m_min = 0, m_max = 0, m_mode = 0;
+    int m_total = 0, m_q1 = 0, m_q2 = 0, m_q3 = 0, m_min = 0, m_max = 0, m_mode = 0, m_repeatKmerCutoff = 0;
     double m_sdv = 0;
 };
 

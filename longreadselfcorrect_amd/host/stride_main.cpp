@@ -18,6 +18,7 @@
 #include "BCode.h"
 #include "ErrorCorrectProcess.h"
 #include "FMIndexWalkProcess.h"
+#include "KmerDistribution.h"
 #include "LexicoOrder.h"
 #include "OverlapProcess.h"
 #include "PacBioSelfCorrectionProcess.h"
@@ -961,9 +962,14 @@ static int correctMain(int argc, char** argv)
 }
 
 // `stride fmwalk -a merge READSFILE`: the reference's FMIndexWalk (StriDe/FMIndexWalk.cpp:40-58,112-238,244-362) with the merge
-// algorithm (FMIndexWalkProcess::MergePairedReads) run on the device, a batch of pairs per lrsc_fmwalk_merge call.  The kmerize,
-// validate and hybrid algorithms are not built.  Not taken over: the empty kmerized.fa that the reference opens and never writes
-// in merge mode, and the `Median kmer frequency` line, which comes from 100000 rand() samples that merge mode does not use.
+// algorithm (FMIndexWalkProcess::MergePairedReads) run on the device, a batch of pairs per lrsc_fmwalk_merge call.  Not taken over
+// in merge mode: the empty kmerized.fa that the reference opens and never writes, and the `Median kmer frequency` line, which comes
+// from 100000 rand() samples that merge mode does not use.
+// `stride fmwalk --hybrid PAIRS` and `--kmerize READS` run the reference's hybrid (MergeAndKmerize) and kmerize (KmerizeReads)
+// algorithms the same way, lrsc_fmwalk_hybrid and lrsc_fmwalk_kmerize per batch; hybrid draws its 100000 sample rows as the
+// reference does (rand() % the index's strings, unseeded) and takes their counts from lrsc_kmer_sample_counts.  `-a hybrid`, `-a
+// kmerize` and an omitted -a are still refused: the two long options are how these modes are reached.  The validate algorithm is
+// not built.
 static const char* FMWALK_USAGE_MESSAGE =
     "Usage: " PACKAGE_NAME " FMIndexWalk [OPTION] ... READSFILE\n"
     "Merge paired end reads into long reads via FM-index walk\n"
@@ -977,6 +983,8 @@ static const char* FMWALK_USAGE_MESSAGE =
     "      -t, --threads=NUM                use NUM threads for the computation (default: 1)\n"
     "      -a, --algorithm=STR              specify the walking algorithm (hybrid (default), merge, kmerize, or validate)\n"
     "      --device=N                       HIP device to work on (default: 0)\n"
+    "      --hybrid                         READSFILE holds pairs: merge them or cut them at unreliable kmers (no -a; --repeat-cutoff=N skips the sampling)\n"
+    "      --kmerize                        READSFILE holds single reads: cut them at unreliable kmers (no -a)\n"
     "\nAlgorithm parameters:\n"
     "      -k, --kmer-size=N                The length of the kmer to use. (default: 31)\n"
     "      -x, --kmer-threshold=N           Attempt to correct kmers that are seen less than N times. (default: 3)\n"
@@ -989,14 +997,15 @@ static const char* FMWALK_USAGE_MESSAGE =
 namespace fmwalkopt {
 static unsigned int verbose = 0;
 static int numThreads = 1, kmerLength = 31, kmerThreshold = 3, maxLeaves = 32, maxInsertSize = 400, minOverlap = 81, maxOverlap = -1, device = 0;
-static std::string prefix, readsFile, outFile;
-static bool buildIndex = false;
+static std::string prefix, readsFile, outFile, discardFile;
+static bool buildIndex = false, hybrid = false, kmerize = false;
+static long long repeatCutoff = -1;                             // --repeat-cutoff: -1, from the sample
 static const size_t batch = 100000;                             // pairs per device call
 }
 
 static void parseFMWalkOptions(int argc, char** argv)
 {
-    enum { F_HELP = 1, F_VERSION, F_METRICS, F_DISCARD, F_LEARN, F_DEVICE, F_BUILDINDEX, F_LOADONDEVICE };
+    enum { F_HELP = 1, F_VERSION, F_METRICS, F_DISCARD, F_LEARN, F_DEVICE, F_BUILDINDEX, F_LOADONDEVICE, F_HYBRID, F_KMERIZE, F_REPEATCUTOFF };
     static const struct option fmwalk_longopts[] = {
         {"verbose", no_argument, nullptr, 'v'},               {"threads", required_argument, nullptr, 't'},
         {"outfile", required_argument, nullptr, 'o'},         {"prefix", required_argument, nullptr, 'p'},
@@ -1008,6 +1017,8 @@ static void parseFMWalkOptions(int argc, char** argv)
         {"help", no_argument, nullptr, F_HELP},               {"version", no_argument, nullptr, F_VERSION},
         {"metrics", required_argument, nullptr, F_METRICS},   {"device", required_argument, nullptr, F_DEVICE},
         {"build-index", no_argument, nullptr, F_BUILDINDEX},  {"load-on-device", no_argument, nullptr, F_LOADONDEVICE},
+        {"hybrid", no_argument, nullptr, F_HYBRID},           {"kmerize", no_argument, nullptr, F_KMERIZE},
+        {"repeat-cutoff", required_argument, nullptr, F_REPEATCUTOFF},
         {nullptr, 0, nullptr, 0}};
     optind = 1;
     std::string algo_str;
@@ -1029,6 +1040,9 @@ static void parseFMWalkOptions(int argc, char** argv)
             case F_LEARN: case F_DISCARD: case F_METRICS: case F_LOADONDEVICE: break;     // read and not used, as in the reference
             case F_DEVICE: arg >> fmwalkopt::device; break;
             case F_BUILDINDEX: fmwalkopt::buildIndex = true; break;
+            case F_HYBRID: fmwalkopt::hybrid = true; break;
+            case F_KMERIZE: fmwalkopt::kmerize = true; break;
+            case F_REPEATCUTOFF: arg >> fmwalkopt::repeatCutoff; break;
             case F_HELP: std::cout << FMWALK_USAGE_MESSAGE; exit(EXIT_SUCCESS);
             case F_VERSION: std::cout << "FMIndexWalk Version " PACKAGE_VERSION " (MI355X back end)\n"; exit(EXIT_SUCCESS);
             default: die = true; break;
@@ -1039,7 +1053,14 @@ static void parseFMWalkOptions(int argc, char** argv)
     if(fmwalkopt::numThreads <= 0) { std::cerr << "FMIndexWalk: invalid number of threads: " << fmwalkopt::numThreads << "\n"; die = true; }
     if(fmwalkopt::kmerLength <= 0) { std::cerr << "FMIndexWalk: invalid kmer length: " << fmwalkopt::kmerLength << ", must be greater than zero\n"; die = true; }
     if(fmwalkopt::kmerThreshold <= 0) { std::cerr << "FMIndexWalk: invalid kmer threshold: " << fmwalkopt::kmerThreshold << ", must be greater than zero\n"; die = true; }
-    if(algo_str.empty()) {
+    if(fmwalkopt::hybrid || fmwalkopt::kmerize) {
+        if(fmwalkopt::hybrid && fmwalkopt::kmerize) { std::cerr << "FMIndexWalk: --hybrid and --kmerize are two algorithms: give one\n"; die = true; }
+        else if(!algo_str.empty()) {
+            std::cerr << "FMIndexWalk: -a is not given together with " << (fmwalkopt::hybrid ? "--hybrid" : "--kmerize") << "\n";
+            die = true;
+        }
+        if(fmwalkopt::repeatCutoff < -1) { std::cerr << "FMIndexWalk: invalid repeat cutoff: " << fmwalkopt::repeatCutoff << "\n"; die = true; }
+    } else if(algo_str.empty()) {
         std::cerr << "FMIndexWalk: without -a the reference runs its hybrid algorithm, which is not built here: say -a merge\n";
         die = true;
     } else if(algo_str == "hybrid" || algo_str == "kmerize" || algo_str == "validate") {
@@ -1052,7 +1073,28 @@ static void parseFMWalkOptions(int argc, char** argv)
     if(die) { std::cout << "\n" << FMWALK_USAGE_MESSAGE; exit(EXIT_FAILURE); }
     fmwalkopt::readsFile = argv[optind++];
     if(fmwalkopt::prefix.empty()) fmwalkopt::prefix = getFilename(fmwalkopt::readsFile);
-    if(fmwalkopt::outFile.empty()) fmwalkopt::outFile = getFilename(fmwalkopt::readsFile) + ".merge.fa";
+    // StriDe/FMIndexWalk.cpp:346-361
+    if(fmwalkopt::outFile.empty()) fmwalkopt::outFile = getFilename(fmwalkopt::readsFile) + (fmwalkopt::kmerize ? ".origin.fa" : ".merge.fa");
+    if(fmwalkopt::hybrid || fmwalkopt::kmerize) fmwalkopt::discardFile = getFilename(fmwalkopt::readsFile) + ".kmerized.fa";
+}
+
+// StriDe/FMIndexWalk.cpp:147-154: the 100000 sampled counts of min-overlap-mers from .rbwt, the line about them, and
+// isSuitableForFMWalk's cutoff.  rand() is the reference's: unseeded, % the index's strings.
+static size_t fmwalkRepeatCutoff(lrsc_index* idx, lrsc_ctx* ctx)
+{
+    lrsc_index_info info;
+    lrscOrDie(lrsc_index_info_get(idx, &info), "lrsc_index_info_get");
+    const uint32_t samples = 100000;
+    std::vector<uint64_t> rows(samples);
+    for(uint32_t i = 0; i < samples; ++i) rows[i] = (uint64_t)rand() % info.num_strings;
+    std::vector<uint32_t> counts(samples);
+    lrscOrDie(lrsc_kmer_sample_counts(ctx, rows.data(), samples, (uint32_t)fmwalkopt::minOverlap, counts.data()), "lrsc_kmer_sample_counts");
+    KmerDistribution kd;
+    for(uint32_t i = 0; i < samples; ++i) kd.add((int)counts[i]);
+    kd.computeKDAttributes();
+    std::cout << "Median kmer frequency: " << kd.getQuartile(2) << "\t Std: " << kd.getSdv() << "\t 95% kmer frequency: " << kd.getCutoffForProportion(0.95)
+              << "\t Repeat frequency cutoff: " << kd.getRepeatKmerCutoff() << "\n";
+    return (size_t)(kd.getQuartile(2) * 1.3);
 }
 
 static int fmwalkMain(int argc, char** argv)
@@ -1081,10 +1123,20 @@ static int fmwalkMain(int argc, char** argv)
     params.maxInsertSize = fmwalkopt::maxInsertSize;
     params.minOverlap = fmwalkopt::minOverlap;
     params.maxOverlap = fmwalkopt::maxOverlap;
+    params.algorithm = fmwalkopt::hybrid ? FMW_HYBRID : fmwalkopt::kmerize ? FMW_KMERIZE : FMW_MERGE;
+    if(fmwalkopt::hybrid) {
+        if(fmwalkopt::minOverlap <= 0) { std::cerr << "FMIndexWalk: invalid min overlap: " << fmwalkopt::minOverlap << "\n"; return EXIT_FAILURE; }
+        params.repeatKmerFreq = fmwalkopt::repeatCutoff >= 0 ? (size_t)fmwalkopt::repeatCutoff : fmwalkRepeatCutoff(idx, ctx);
+    }
     bool odd = false;
     {
         std::ofstream writer(fmwalkopt::outFile.c_str());
         if(!writer) { std::cerr << "Error: could not open " << fmwalkopt::outFile << " for write\n"; return EXIT_FAILURE; }
+        std::ofstream discard;
+        if(!fmwalkopt::discardFile.empty()) {
+            discard.open(fmwalkopt::discardFile.c_str());
+            if(!discard) { std::cerr << "Error: could not open " << fmwalkopt::discardFile << " for write\n"; return EXIT_FAILURE; }
+        }
         std::cout << "Merge paired end reads into long reads for " << fmwalkopt::readsFile << " using \n"
                   << "min overlap=" << params.minOverlap << "\t"
                   << "max overlap=" << params.maxOverlap << "\t"
@@ -1092,11 +1144,21 @@ static int fmwalkMain(int argc, char** argv)
                   << "max Insert size=" << params.maxInsertSize << "\t"
                   << "kmer size=" << params.kmerLength << "\n\n";
         FMIndexWalkProcess processor(params);
-        FMIndexWalkPostProcess post(&writer);
+        FMIndexWalkPostProcess post(&writer, fmwalkopt::discardFile.empty() ? nullptr : &discard, params.algorithm);
         SeqReader reader(fmwalkopt::readsFile, true);
         WorkItemGenerator<SequenceWorkItem> generator(&reader);
+        if(fmwalkopt::kmerize) {
+            std::vector<SequenceWorkItem> reads;
+            for(bool more = true; more;) {
+                reads.clear();
+                SequenceWorkItem item;
+                while(reads.size() < 2 * fmwalkopt::batch && (more = generator.generate(item))) reads.push_back(item);
+                const std::vector<FMIndexWalkResult> results = processor.process_batch(reads);
+                for(size_t i = 0; i < reads.size(); ++i) post.process(reads[i], results[i]);
+            }
+        }
         std::vector<SequenceWorkItemPair> pairs;
-        for(bool more = true; more;) {
+        for(bool more = !fmwalkopt::kmerize; more;) {
             pairs.clear();
             SequenceWorkItemPair pair;
             while(pairs.size() < fmwalkopt::batch && (more = generator.generate(pair, &odd))) pairs.push_back(pair);
@@ -1111,6 +1173,7 @@ static int fmwalkMain(int argc, char** argv)
     if(odd) {                                                     // the reference asserts
         std::cerr << "FMIndexWalk: " << fmwalkopt::readsFile << " holds an odd number of records: the reads of a pair follow one another\n";
         std::remove(fmwalkopt::outFile.c_str());
+        if(!fmwalkopt::discardFile.empty()) std::remove(fmwalkopt::discardFile.c_str());
         return EXIT_FAILURE;
     }
     return 0;

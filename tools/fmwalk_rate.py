@@ -11,7 +11,13 @@
   3. the share of pairs merged, the share of merged strings that are the fragment (on either strand), and the walks' return codes.
 
 Prints profiles/kmer_correct.json's LF steps per second beside the result: the k-mer corrector's chains are the same backward
-search, a lane each with no frontier to keep.  Writes profiles/fmwalk_merge.json (or --out)."""
+search, a lane each with no frontier to keep.  Writes profiles/fmwalk_merge.json (or --out).
+
+--algorithm hybrid runs lrsc_fmwalk_hybrid (csrc/fm_kmerize.hip) over the same pairs, its repeat cutoff from 100 000 sampled rows
+through lrsc_kmer_sample_counts as `stride fmwalk --hybrid` takes it (the rows from a seeded generator here), and merge mode
+alongside in the same session: three runs of each, alternating, and hybrid's ratio to merge.  --algorithm kmerize runs
+lrsc_fmwalk_kmerize over the pairs' reads as single reads.  Both add the k-mers whose two single-strand counts a split takes
+(KmerContext) per second.  They write profiles/fmwalk_hybrid.json and profiles/fmwalk_kmerize.json."""
 from __future__ import annotations
 
 import argparse
@@ -76,18 +82,114 @@ def one_run(ctx, bases, off):
                                        "block_loads_per_lf_step": s.block_loads / lf}
 
 
+def _rates(ctx, wall, units, name, context_kmers):
+    s = ctx.stats(capi.K_FIND)
+    lf = s.rank_queries / 2
+    return {"wall_s": wall, f"{name}_per_s": units / wall, "kernel_ms": s.total_ms, "launches": s.launches, "lf_steps": lf,
+            "lf_steps_per_s": lf / (s.total_ms / 1e3), "block_loads_per_lf_step": s.block_loads / lf, "context_kmers": context_kmers,
+            "context_kmers_per_s": context_kmers / wall}
+
+
+def hybrid_run(ctx, bases, off, repeat):
+    n_pairs = (off.size - 1) // 2
+    ctx.stats_reset()
+    res, kmers = np.zeros(n_pairs, dtype=capi.FMWALK_HYBRID_DTYPE), 0
+    t = time.perf_counter()
+    for a in range(0, n_pairs, BATCH):
+        b = min(a + BATCH, n_pairs)
+        lo, hi = int(off[2 * a]), int(off[2 * b])
+        _, res[a:b], _, _ = ctx.fmwalk_hybrid(bases[lo:hi], off[2 * a: 2 * b + 1] - off[2 * a], repeat, **OPTIONS)
+    wall = time.perf_counter() - t
+    split = res["read"]["n_pieces"] > 0
+    kmers = int((res["read"]["length"][split].astype(np.int64) - OPTIONS["kmer_length"] + 1).sum())
+    return res, _rates(ctx, wall, n_pairs, "pairs", kmers)
+
+
+def kmerize_run(ctx, bases, off):
+    n = off.size - 1
+    ctx.stats_reset()
+    res = np.zeros(n, dtype=capi.FMWALK_READ_DTYPE)
+    t = time.perf_counter()
+    for a in range(0, n, 2 * BATCH):
+        b = min(a + 2 * BATCH, n)
+        res[a:b], _, _ = ctx.fmwalk_kmerize(bases[int(off[a]): int(off[b])], off[a: b + 1] - off[a], OPTIONS["kmer_length"], OPTIONS["kmer_threshold"])
+    wall = time.perf_counter() - t
+    kmers = int((res["length"][res["n_pieces"] > 0].astype(np.int64) - OPTIONS["kmer_length"] + 1).sum())
+    return res, _rates(ctx, wall, n, "reads", kmers)
+
+
+def _median(runs):
+    return {k: statistics.median(r[k] for r in runs) for k in runs[0] if k != "launches"}
+
+
+def other_algorithms(args, api, ctx, bases, off, workload_info):
+    """--algorithm hybrid and kmerize"""
+    out = Path(args.out) if args.out else REPO / "profiles" / f"fmwalk_{args.algorithm}.json"
+    result = {"workload": workload_info}
+    if args.algorithm == "kmerize":
+        kmerize_run(ctx, bases, off)                                   # warm-up
+        runs = []
+        for _ in range(3):
+            res, r = kmerize_run(ctx, bases, off)
+            runs.append(r)
+            print(r, flush=True)
+        pieces = res["n_pieces"][res["n_pieces"] > 0]
+        result.update(runs=runs, median=_median(runs),
+                      outcome={"reads_kmerized_share": float((res["kmerize"] != 0).mean()), "reads_in_one_piece_share": float((pieces == 1).mean()),
+                               "pieces_per_read_mean": float(pieces.mean()), "reads_with_a_main_piece_share": float((res["main_piece"] >= 0).mean())})
+    else:
+        rows = np.random.default_rng(0xC0FFEE).integers(0, off.size - 1, size=100000).astype(np.uint64)
+        ctx.stats_reset()
+        t = time.perf_counter()
+        counts = ctx.kmer_sample_counts(rows, OPTIONS["min_overlap"])
+        sample = {"wall_s": time.perf_counter() - t, "kernel_ms": ctx.stats(capi.K_FIND).total_ms, "samples": int(rows.size)}
+        q2 = int(np.sort(counts)[counts.size // 2])
+        repeat = int(q2 * 1.3)
+        hybrid_run(ctx, bases, off, repeat)                                # warm-up
+        one_run(ctx, bases, off)
+        hybrid, merge = [], []
+        for _ in range(3):                                                 # alternating, one session
+            res, r = hybrid_run(ctx, bases, off, repeat)
+            hybrid.append(r)
+            print("hybrid", r, flush=True)
+            _, mres, r = one_run(ctx, bases, off)
+            merge.append(r)
+            print("merge", r, flush=True)
+        hm, mm = _median(hybrid), _median(merge)
+        merged = res["walk"]["merged"] != 0
+        result.update(sample=sample, median_count=q2, repeat_kmer_freq=repeat, runs=hybrid, median=hm, merge_mode_runs=merge, merge_mode_median=mm,
+                      hybrid_to_merge={"wall": hm["wall_s"] / mm["wall_s"], "kernel_ms": hm["kernel_ms"] / mm["kernel_ms"]},
+                      outcome={"pairs_merged_share": float(merged.mean()), "merge_mode_pairs_merged_share": float((mres["merged"] != 0).mean()),
+                               "pairs_walked_share": float((res["walk"]["status"][:, 0] != 0).mean()),
+                               "reads_kmerized_share": float((res["read"]["kmerize"] != 0).mean()), "reads_split_share": float((res["read"]["n_pieces"] > 0).mean()),
+                               "pieces_per_split_read_mean": float(res["read"]["n_pieces"][res["read"]["n_pieces"] > 0].mean())})
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text(json.dumps(result, indent=1) + "\n")
+    print(json.dumps(result))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--genome-mb", type=float, default=1.0)
     ap.add_argument("--substitution-rate", type=float, default=P_SUB, help="0: reads as `stride correct` would leave them")
-    ap.add_argument("--out", default=str(REPO / "profiles" / "fmwalk_merge.json"))
+    ap.add_argument("--algorithm", choices=["merge", "hybrid", "kmerize"], default="merge")
+    ap.add_argument("--out", default=None, help="default: profiles/fmwalk_<algorithm>.json")
     args = ap.parse_args()
+    if args.algorithm == "merge" and args.out is None:
+        args.out = str(REPO / "profiles" / "fmwalk_merge.json")
     api = Lrsc()
     bases, off, fragments = workload(api, args.genome_mb, args.substitution_rate)
     t = time.perf_counter()
     index = api.index_build(bases, off, 0)
     build_s = time.perf_counter() - t
     ctx = index.ctx(api.params_default(5, 90), 0)
+    if args.algorithm != "merge":
+        other_algorithms(args, api, ctx, bases, off, {"genome_mb": args.genome_mb, "pairs": (off.size - 1) // 2, "read_length": READ_LEN,
+                                                      "fragment_bases": [FRAG_MIN, FRAG_MAX], "coverage": COVERAGE, "substitution_rate": args.substitution_rate,
+                                                      "bases": int(bases.size), "batch": BATCH, **OPTIONS, "index_build_s": build_s})
+        ctx.close()
+        index.close()
+        return
     one_run(ctx, bases, off)                                           # warm-up: buffers, code objects
     runs = []
     for _ in range(3):
