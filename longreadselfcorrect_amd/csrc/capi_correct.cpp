@@ -628,9 +628,9 @@ int WpFlow::print_extension_profile()
         if(pr[10] == 0) continue;
         const double all = (double)pr[10], st = (double)std::max<unsigned long long>(pr[11], 1);
         std::fprintf(stderr, "[lrsc] wp extension kernel (%s), lane wall ticks: %.3g total, %.0f per step over %.3g steps; extendLeaves %.1f%% (refine %.1f%%, attempToExtend %.1f%% of which "
-                             "getFMIndexExtensions %.1f%%), PrunedBySeedSupport %.1f%%, materialise+commit %.1f%%, isTerminated %.1f%%, refill %.1f%%, finish %.1f%%; single-leaf fast steps %.1f%% of the steps in %.1f%% of the ticks\n",
+                             "getFMIndexExtensions %.1f%%; SelectFreqsOfrange %.1f%%), PrunedBySeedSupport %.1f%%, materialise+commit %.1f%%, isTerminated %.1f%%, refill %.1f%%, finish %.1f%%; single-leaf fast steps %.1f%% of the steps in %.1f%% of the ticks\n",
                      part ? "long-gap walks, one per wavefront" : "bulk and later rounds",
-                     all, all / st, st, 100 * pr[0] / all, 100 * pr[1] / all, 100 * pr[2] / all, 100 * pr[3] / all, 100 * pr[4] / all, 100 * pr[5] / all, 100 * pr[6] / all,
+                     all, all / st, st, 100 * pr[0] / all, 100 * pr[1] / all, 100 * pr[2] / all, 100 * pr[3] / all, 100 * pr[13] / all, 100 * pr[4] / all, 100 * pr[5] / all, 100 * pr[6] / all,
                      100 * pr[8] / all, 100 * pr[9] / all, 100 * pr[12] / st, 100 * pr[7] / all);
     }
     return LRSC_OK;

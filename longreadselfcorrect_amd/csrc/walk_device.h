@@ -18,6 +18,12 @@
 #ifndef LRSC_WALK_FN
 #define LRSC_WALK_FN __device__
 #endif
+// Test hook: tests/host_walk_groups defines LRSC_WALK_TRACE(kind, a, b) to learn which shapes of the general step its inputs have
+// reached (kind 0: a step with a leaves; 1: extendLeaves made a children; 2: the threshold retry taken for leaf a of b; 3:
+// SelectFreqsOfrange over a leaves; 4: the children overflowed).  Empty in the product and in every other build.
+#ifndef LRSC_WALK_TRACE
+#define LRSC_WALK_TRACE(kind, a, b)
+#endif
 
 namespace lrsc {
 
@@ -435,6 +441,7 @@ struct Walk : WalkCap<BIG> {
     }
     LRSC_WALK_FN LRSC_WALK_NOINLINE uint64_t SelectFreqsOfrange(uint64_t LowerBound, uint64_t UpperBound, Leaf<P>* leaves, uint32_t n)
     {
+        LRSC_WALK_TRACE(3, n, 0);
         int tempmaxfmfreqs = 0;
         const uint32_t U = (uint32_t)UpperBound, Lw = (uint32_t)LowerBound;
         for(uint32_t j = 0; j < n; ++j) {
@@ -600,6 +607,9 @@ struct Walk : WalkCap<BIG> {
 
         n_highfreq = 0;
         const int highfreqThreshold = PBcoverage > 60 ? (int)((uint64_t)(PBcoverage / 60) * 3) : 3;
+        // (One leaf at a time on purpose.  Loading the next leaf's interval ends while this one is worked on, so that its rank
+        //  blocks and the leaf itself come in one wait, was measured: 13 more VGPR spills and a bulk launch 24 ms LONGER than
+        //  without it -- DESIGN 4b, "Leaf groups in the general step".)
         for(uint32_t i = 0; i < n_cur; ++i) {
             const Leaf<P> par = cur[i];                          // one burst of loads: the leaf in registers
             Ext ext[4];
@@ -607,6 +617,7 @@ struct Walk : WalkCap<BIG> {
             int count = 0;
             while(count < 2) {
                 if(count == 1 && !(par.localErr == minimumErrorRate && n_cur > 1)) break;
+                if(count == 1) { LRSC_WALK_TRACE(2, i, n_cur); }
                 uint64_t tc;
                 const uint64_t tg = tick();
                 mask = getFMIndexExtensions_v(par.flo, par.fhi, par.rlo, par.rhi, par.tailLetterCount, par.suf_lo, ext, tc);
@@ -620,7 +631,7 @@ struct Walk : WalkCap<BIG> {
             // updateLeaves: children in base order; leafInfo(child) fields (LongReadCorrectByOverlap.h:172-203)
             for(uint32_t b = 0; b < 4; ++b) {
                 if(!(mask & (1u << b))) continue;
-                if(n_nxt >= max_children()) { error = LRSC_WALK_ERR_CHILDREN; return; }
+                if(n_nxt >= max_children()) { LRSC_WALK_TRACE(4, n_nxt, i); error = LRSC_WALK_ERR_CHILDREN; return; }
                 const Leaf<P> ch = make_child(par, i, b, ext[b]);
                 if(ch.kmerFrequency > highfreqThreshold) n_highfreq++;      // for isInsufficientFreqs, which looks at exactly these values
                 nxt[n_nxt++] = ch;
@@ -658,7 +669,9 @@ struct Walk : WalkCap<BIG> {
         if(error) return;
         if(n_nxt == 0) {                                    // level 1: reduce the k-mer size
             const uint64_t LowerBound = (currentKmerSize - 2) > minOverlap ? (currentKmerSize - 2) : minOverlap;
+            const uint64_t ts = tick();
             const uint64_t ReduceSize = SelectFreqsOfrange(LowerBound, currentKmerSize, cur, n_cur);
+            tock(8, ts);
             refineSAInterval(cur, n_cur, ReduceSize);
             attempToExtend();
             if(error) return;
@@ -674,7 +687,9 @@ struct Walk : WalkCap<BIG> {
             currentKmerSize++;
             if(isInsufficientFreqs(n_highfreq, n_nxt)) {    // frequencies are low: relax the k-mer size
                 const uint64_t LowerBound = (currentKmerSize - 2) > minOverlap ? (currentKmerSize - 2) : minOverlap;
+                const uint64_t ts = tick();
                 const uint64_t ReduceSize = SelectFreqsOfrange(LowerBound, currentKmerSize, nxt, n_nxt);
+                tock(8, ts);
                 refineSAInterval(nxt, n_nxt, ReduceSize);
             }
         }
@@ -777,6 +792,13 @@ struct Walk : WalkCap<BIG> {
         const double currErrorRate = computeErrorRate(leaf, pring);
         if(currErrorRate > errorRate) leaf.alive = 0;
     }
+    // Group sizes of the general step's per-leaf and per-child loops, by measurement ("Leaf groups in the general
+    // step"): the kernel is compiled at its register limit, and a wider group spills what it keeps in flight.  Children of
+    // PrunedBySeedSupport: 1 -> 598 ms, 2 -> 593 ms, 4 -> 649 ms per bulk launch (parent 630 ms).  Commit: 2 and 4 within the
+    // spread of each other.  The isTerminated loop keeps one 8-byte suffix per leaf.
+    static constexpr uint32_t kPruneGroup = 2;
+    static constexpr uint32_t kCommitGroup = 2;
+    static constexpr uint32_t kTermGroup = 4;
     LRSC_WALK_FN void PrunedBySeedSupport()
     {
         const uint64_t currSeedIdx = currentLength - seedSize;
@@ -785,13 +807,143 @@ struct Walk : WalkCap<BIG> {
         const uint64_t largeSeedIdx = (currSeedIdx + indelOffset) >= (Lq - seedSize) ? (Lq - seedSize) : currSeedIdx + indelOffset;
         alive_lo = 0; alive_hi = 0; has_child = 0;
         if constexpr(BIG) { bits_clear_all(this->alive_bits, n_nxt); bits_clear_all(this->child_bits, n_cur); }
-        for(uint32_t c = 0; c < n_nxt; ++c) {
-            Leaf<P> leaf = nxt[c];                               // in registers for the whole evaluation, one burst each way
-            // createChild copied the parent's ring id into the child: cur[leaf.parent].ring == leaf.ring until the commit
-            prune_leaf<true>(leaf, rings + (uint64_t)leaf.ring * 100, currSeedIdx, smallSeedIdx, largeSeedIdx);
-            nxt[c] = leaf;
-            if constexpr(BIG) { if(leaf.alive) { bits_set(this->alive_bits, c); bits_set(this->child_bits, leaf.parent); } }
-            else if(leaf.alive) { if(c < 64) alive_lo |= 1ull << c; else alive_hi |= 1ull << (c - 64); has_child |= 1u << leaf.parent; }
+        // prune_leaf for kPruneGroup children side by side.  Why the order inside a group cannot be observed: a child's evaluation
+        // reads its own fields, the walk's tables (head9 / it9 / next9: fixed since begin_static) and one slot of its parent's ring
+        // (rings are written by the commit only), and writes its own fields; the frontier's bit sets are set afterwards, per child
+        // in child order.  So what differs from the loop of prune_leaf calls is only when the loads are issued: a group's fields
+        // (the part of a leaf the evaluation touches, not the whole leaf), then its bucket heads and ring slots, then the chain
+        // entries of all its cursors (two strands per child) step by step, each step one wait for the lane instead of one per
+        // entry, strand and child.  An entry comes with its successor's index, so a skipped entry and a hit cost the same.
+        // The arithmetic is prune_leaf's, seed_support_core's and computeErrorRate's, statement for statement.
+        constexpr uint32_t G = kPruneGroup;
+        constexpr uint32_t NIL = 0xFFFFu;
+        const uint32_t mask9 = seedSize >= 16 ? 0xFFFFFFFFu : ((1u << (2 * seedSize)) - 1u);
+        for(uint32_t c0 = 0; c0 < n_nxt; c0 += G) {
+            const uint32_t g = n_nxt - c0 < G ? n_nxt - c0 : G;
+            uint64_t lastSeedIdx[G], lastOverlapLen[G], totalSeeds[G], currOverlapLen[G], numOfErrors[G], queryOverlapLen[G];
+            double numRedeemSeed[G];
+            uint32_t hist_size[G], code9[G], ring[G], parent[G];
+            int32_t lastSeedIdxOffset[G];
+            bool fv[G], rv[G];
+#pragma unroll
+            for(uint32_t j = 0; j < G; ++j) {                    // a short group is padded with its first child (nothing of it is kept)
+                const Leaf<P>& lf = nxt[c0 + (j < g ? j : 0)];
+                lastSeedIdx[j] = lf.lastSeedIdx; lastOverlapLen[j] = lf.lastOverlapLen; totalSeeds[j] = lf.totalSeeds;
+                currOverlapLen[j] = lf.currOverlapLen; numOfErrors[j] = lf.numOfErrors; queryOverlapLen[j] = lf.queryOverlapLen;
+                numRedeemSeed[j] = lf.numRedeemSeed; hist_size[j] = lf.hist_size; lastSeedIdxOffset[j] = lf.lastSeedIdxOffset;
+                code9[j] = (uint32_t)lf.suf_lo & mask9; ring[j] = lf.ring; parent[j] = lf.parent;
+                fv[j] = lf.flo <= lf.fhi; rv[j] = lf.rlo <= lf.rhi;
+            }
+            // bucket heads and the ring slot computeErrorRate reads (slot 0, unused, while the history is shorter than localK).
+            // createChild copied the parent's ring id into the child: cur[parent].ring == the child's ring until the commit
+            bool need[G];
+            uint64_t preSeedIdx[G], startSeedIdx[G];
+            uint32_t jf[G], jr[G];
+            double old[G];
+#pragma unroll
+            for(uint32_t j = 0; j < G; ++j) {
+                const uint64_t d = currentLength - lastOverlapLen[j];
+                need[j] = j < g && (d > seedSize || d <= 1);
+                preSeedIdx[j] = lastSeedIdx[j];
+                const uint64_t seedIdxOffset = lastOverlapLen[j] < currentLength - seedSize ? (uint64_t)seedSize : currentLength - lastOverlapLen[j];
+                const uint64_t cand = lastSeedIdx[j] + seedIdxOffset;
+                startSeedIdx[j] = smallSeedIdx > cand ? smallSeedIdx : cand;
+                const uint32_t hb = (code9[j] ^ (code9[j] >> 9)) & 255u;
+                jf[j] = head9f[hb]; jr[j] = head9r[hb];
+                const uint32_t totalsize = hist_size[j] + 1;
+                old[j] = rings[(uint64_t)ring[j] * 100 + (totalsize >= localK ? (totalsize - localK) % 100 : 0)];
+            }
+            // the hit lists in post-sort order (seed_support_core): per child and strand a cursor along the bucket's chain; mf / mr:
+            // the cursor stands behind an entry of the child's k-mer that has not been consumed yet (its offset in vf / vr)
+            bool mf[G], mr[G], found[G];
+            uint32_t vf[G], vr[G];
+            int minIdxDiff[G];
+#pragma unroll
+            for(uint32_t j = 0; j < G; ++j) {
+                if(!(need[j] && fv[j])) jf[j] = NIL;
+                if(!(need[j] && rv[j])) jr[j] = NIL;
+                mf[j] = false; mr[j] = false; found[j] = false; vf[j] = 0; vr[j] = 0; minIdxDiff[j] = 10000;
+            }
+            while(true) {
+                bool seek = false;
+#pragma unroll
+                for(uint32_t j = 0; j < G; ++j) seek = seek || (!mf[j] && jf[j] != NIL) || (!mr[j] && jr[j] != NIL);
+                if(seek) {
+                    // one chain step for every cursor that is looking for its next entry; a cursor at rest loads entry 0 for nothing
+                    uint32_t pf[G], pr_[G], wf[G], wr[G], nf[G], nr[G];
+#pragma unroll
+                    for(uint32_t j = 0; j < G; ++j) {
+                        const uint32_t a = (!mf[j] && jf[j] != NIL) ? jf[j] : 0u, b = (!mr[j] && jr[j] != NIL) ? jr[j] : 0u;
+                        pf[j] = it9f[a].pad; wf[j] = it9f[a].val; nf[j] = next9f[a];
+                        pr_[j] = it9r[b].pad; wr[j] = it9r[b].val; nr[j] = next9r[b];
+                    }
+#pragma unroll
+                    for(uint32_t j = 0; j < G; ++j) {
+                        if(!mf[j] && jf[j] != NIL) { if(pf[j] == code9[j]) { mf[j] = true; vf[j] = wf[j]; } jf[j] = nf[j]; }
+                        if(!mr[j] && jr[j] != NIL) { if(pr_[j] == code9[j]) { mr[j] = true; vr[j] = wr[j]; } jr[j] = nr[j]; }
+                    }
+                    continue;
+                }
+                // every cursor has its next entry or is at its chain's end: one round of isSupportedByNewSeed's loop per child
+                bool any = false;
+#pragma unroll
+                for(uint32_t j = 0; j < G; ++j) {
+                    if(!(mf[j] || mr[j])) continue;
+                    any = true;
+                    const uint64_t f = vf[j], r = vr[j];
+                    if(mf[j] && f >= startSeedIdx[j] && f <= largeSeedIdx) {
+                        const int d = abs((int)f - (int)currSeedIdx);
+                        if(d < minIdxDiff[j]) { lastSeedIdx[j] = f; queryOverlapLen[j] = f + seedSize; minIdxDiff[j] = d; }
+                        lastOverlapLen[j] = currentLength;
+                        currOverlapLen[j] = currentLength;
+                        found[j] = true;
+                    } else if(mr[j] && r >= startSeedIdx[j] && r <= largeSeedIdx) {
+                        const int d = abs((int)currSeedIdx - (int)r);
+                        if(d < minIdxDiff[j]) { lastSeedIdx[j] = r; queryOverlapLen[j] = r + seedSize; minIdxDiff[j] = d; }
+                        lastOverlapLen[j] = currentLength;
+                        currOverlapLen[j] = currentLength;
+                        found[j] = true;
+                    }
+                    mf[j] = false; mr[j] = false;
+                }
+                if(!any) break;
+            }
+            // the rest of prune_leaf, computeErrorRate, the stores and the frontier's bit sets: per child, in child order
+#pragma unroll
+            for(uint32_t j = 0; j < G; ++j) {
+                if(j >= g) continue;
+                const uint32_t c = c0 + j;
+                if(need[j]) {
+                    if(found[j]) {
+                        totalSeeds[j]++;
+                        if(currSeedIdx + (uint64_t)(int64_t)lastSeedIdxOffset[j] - preSeedIdx[j] > seedSize)
+                            numRedeemSeed[j] += (seedSize - 1) * PacBioErrorRate;
+                        lastSeedIdxOffset[j] = (int)lastSeedIdx[j] - (int)currSeedIdx;
+                    } else {
+                        const uint64_t v = currSeedIdx + (uint64_t)(int64_t)lastSeedIdxOffset[j] - lastSeedIdx[j];
+                        if(v % seedSize == 1) numOfErrors[j]++;
+                        else if(v > (uint64_t)seedSize - 1) numRedeemSeed[j] += 1 - PacBioErrorRate;
+                    }
+                } else
+                    numRedeemSeed[j] += 1 - PacBioErrorRate;
+                double matchedLen = (double)totalSeeds[j] + seedSize - 1;
+                matchedLen += numRedeemSeed[j];
+                const double totalLen = (double)currOverlapLen[j];
+                const double unmatchedLen = totalLen - matchedLen;
+                double currErrorRate = unmatchedLen / totalLen;
+                const double globalErr = currErrorRate;
+                const uint32_t totalsize = hist_size[j] + 1;          // after the push_back
+                if(totalsize >= localK) currErrorRate = (currErrorRate * totalLen - old[j] * (totalLen - localK)) / localK;
+                const bool alive = !(currErrorRate > errorRate);
+                Leaf<P>& lf = nxt[c];
+                lf.lastSeedIdx = lastSeedIdx[j]; lf.lastOverlapLen = lastOverlapLen[j]; lf.totalSeeds = totalSeeds[j];
+                lf.currOverlapLen = currOverlapLen[j]; lf.numOfErrors = numOfErrors[j]; lf.queryOverlapLen = queryOverlapLen[j];
+                lf.numRedeemSeed = numRedeemSeed[j]; lf.localErr = currErrorRate; lf.globalErr = globalErr;
+                lf.hist_size = totalsize; lf.lastSeedIdxOffset = lastSeedIdxOffset[j];
+                if(!alive) lf.alive = 0;                             // createChild left it 1
+                if constexpr(BIG) { if(alive) { bits_set(this->alive_bits, c); bits_set(this->child_bits, parent[j]); } }
+                else if(alive) { if(c < 64) alive_lo |= 1ull << c; else alive_hi |= 1ull << (c - 64); has_child |= 1u << parent[j]; }
+            }
         }
     }
 
@@ -808,6 +960,17 @@ struct Walk : WalkCap<BIG> {
         lf.res_second = hit;
         term_store(lf, hit, pw, plen, extra);
     }
+    // term_scan's filter: false = no target minOverlap-mer hashes like the last characters of the leaf's suffix
+    LRSC_WALK_FN __forceinline__ bool term_may_hit(uint64_t suf_lo) const
+    {
+        if(currentKmerSize >= minOverlap) {
+            const uint32_t L = minOverlap < 16 ? (uint32_t)minOverlap : 16u;
+            const uint32_t code = (uint32_t)(suf_lo & (L >= 16 ? 0xFFFFFFFFull : ((1ull << (2 * L)) - 1ull)));
+            const uint32_t h = (code * 0x9E3779B1u) >> 25;
+            if((((h < 64 ? tmask0 : tmask1) >> (h & 63u)) & 1ull) == 0) return false;
+        }
+        return true;
+    }
     // the scan: the last target offset whose minOverlap-mer interval contains the leaf's (either strand), -1 if none
     LRSC_WALK_FN __forceinline__ int term_scan(const Leaf<P>& lf) const
     {
@@ -815,12 +978,7 @@ struct Walk : WalkCap<BIG> {
         // A non-empty interval of a k-mer K lies inside the interval of a k-mer w with |w| <= |K| only if K ends with w (fwd strand:
         // reverse(w) is a prefix of reverse(K); rvc strand: revcomp(w) is a prefix of revcomp(K)).  So if no target minOverlap-mer
         // hashes like the leaf's last characters, the scan below cannot hit: skip its loads.
-        if(currentKmerSize >= minOverlap) {
-            const uint32_t L = minOverlap < 16 ? (uint32_t)minOverlap : 16u;
-            const uint32_t code = (uint32_t)(lf.suf_lo & (L >= 16 ? 0xFFFFFFFFull : ((1ull << (2 * L)) - 1ull)));
-            const uint32_t h = (code * 0x9E3779B1u) >> 25;
-            if((((h < 64 ? tmask0 : tmask1) >> (h & 63u)) & 1ull) == 0) return -1;
-        }
+        if(!term_may_hit(lf.suf_lo)) return -1;
         const uint64_t i0 = (uint64_t)(lf.res_second > 0 ? lf.res_second : 0);
         int hit = -1;
         for(uint64_t i = i0; i <= (uint64_t)trg_len - (int)minOverlap; i++) {
@@ -1128,9 +1286,11 @@ struct Walk : WalkCap<BIG> {
     {
         {
             uint64_t t = tick();
+            LRSC_WALK_TRACE(0, n_cur, 0);
             extendLeaves();
             tock(0, t);
             if(error) return;
+            LRSC_WALK_TRACE(1, n_nxt, 0);
             t = tick();
             PrunedBySeedSupport();
             tock(4, t);
@@ -1161,46 +1321,81 @@ struct Walk : WalkCap<BIG> {
             // has_child (from PrunedBySeedSupport): bit i = leaf i of cur[] has a surviving child (n_cur <= 32)
             if constexpr(BIG) { for(uint32_t i = 0; i < n_cur; ++i) if(!bits_get(this->child_bits, i)) free_leaf_slots(cur[i]); }
             else for(uint32_t i = 0; i < n_cur; ++i) if(!((has_child >> i) & 1u)) free_leaf_slots(cur[i]);
-            const bool want_term = currentLength >= minLength;
+            // The survivors a group at a time.  A survivor's materialisation needs seven of its fields (a child still carries its
+            // parent's ring / path ids and path length: createChild copied them), one path word, and the whole leaf only where the
+            // compaction moves it.  The fields of kCommitGroup consecutive children are loaded together, then -- in child order,
+            // as before -- the slots are handed out and a further child's ring and path copied, then the group's path words are
+            // loaded together, and the pushes, path appends and the compaction follow in child order.  Why the loads may go ahead
+            // of the stores of earlier children of the group:
+            //  * fields: the compaction writes nxt[w] with w below the child it moves, never a later child's leaf;
+            //  * path words: every survivor appends to a path slot of its own (the parent's for its first survivor, a fresh one
+            //    for each further survivor), so no word is another survivor's;
+            //  * a further child's copies read the parent's ring and path, to which the parent's in-place child -- an earlier
+            //    child, possibly of the same group -- appends.  Whether that append comes before or after the copy, the copy's
+            //    only slot and only two path bits that could differ are the ones the further child overwrites with its own push
+            //    and its own character (see the note on the ring below; the path append changes two bits of one word).
+            constexpr uint32_t G = kCommitGroup;
             uint32_t seen = 0, w = 0;
             if constexpr(BIG) bits_clear_all(this->seen_bits, n_cur);
-            for(uint32_t c = 0; c < n_nxt; ++c) {
-                if(!is_alive(c)) continue;
-                Leaf<P> ch = nxt[c];                             // registers: one burst in, one out
-                bool further;
-                if constexpr(BIG) further = bits_get(this->seen_bits, ch.parent); else further = ((seen >> ch.parent) & 1u) != 0;
-                if(further) {
-                    // a further child of this parent: copies of the ring and of the path as they are BEFORE this step's appends
-                    // (the in-place child of the parent has only written slots the copies do not read: see below)
-                    const uint16_t pr = ch.ring, pp = ch.path;
-                    if constexpr(BIG) {                                                  // survivors <= cap slots: never empty here
-                        ch.ring = (uint16_t)bits_take_lowest(this->ring_bits, this->cap);
-                        ch.path = (uint16_t)bits_take_lowest(this->path_bits, this->cap);
-                    } else {
-                        ch.ring = (uint16_t)__builtin_ctz(ring_free); ring_free &= ring_free - 1u;     // survivors <= 32 slots: never empty here
-                        ch.path = (uint16_t)__builtin_ctz(path_free); path_free &= path_free - 1u;
-                    }
-                    // The ring: only the slots the lineage has pushed so far.  The parent has made hist_size - 1 pushes (its
-                    // hist_size is this child's minus the push of this step), into slots 0, 1, ... in turn, wrapping at 100.
-                    // computeErrorRate is the only reader of a slot: it reads (totalsize - localK) % 100 once totalsize >=
-                    // localK = 100, the slot written 100 pushes earlier on the same lineage.  So a slot at or beyond the
-                    // number of pushes is never read before it has been written, and need not be copied.  The count is
-                    // rounded up to whole bursts (a row is 10 of them): what that copies beyond the live slots is the
-                    // child's own slot -- as the parent's in-place child may already have written it -- which the push
-                    // below overwrites, and slots of the never-read kind.
-                    const uint32_t live = ch.hist_size - 1 < 100 ? ch.hist_size - 1 : 100;
-                    const uint32_t nburst = (live * 8 + kCopyChunk16 * 16 - 1) / (kCopyChunk16 * 16);
-                    burst_copy16(rings + (uint64_t)ch.ring * 100, rings + (uint64_t)pr * 100, nburst);
-                    burst_copy4(paths + (uint64_t)ch.path * pathw, paths + (uint64_t)pp * pathw, (ch.path_len + 16) >> 4);
+            for(uint32_t c0 = 0; c0 < n_nxt; c0 += G) {
+                bool live[G];
+                uint32_t parent[G], ring[G], path[G], hist_size[G], plen[G], ext[G];
+                double globalErr[G];
+                bool anylive = false;
+#pragma unroll
+                for(uint32_t j = 0; j < G; ++j) { live[j] = c0 + j < n_nxt && is_alive(c0 + j); anylive = anylive || live[j]; }
+                if(!anylive) continue;
+#pragma unroll
+                for(uint32_t j = 0; j < G; ++j) {                // a dead or missing child's slot reads child c0 for nothing
+                    const Leaf<P>& lf = nxt[live[j] ? c0 + j : c0];
+                    parent[j] = lf.parent; ring[j] = lf.ring; path[j] = lf.path; hist_size[j] = lf.hist_size; plen[j] = lf.path_len;
+                    ext[j] = lf.ext; globalErr[j] = lf.globalErr;
                 }
-                if constexpr(BIG) bits_set(this->seen_bits, ch.parent); else seen |= 1u << ch.parent;
-                rings[(uint64_t)ch.ring * 100 + (ch.hist_size - 1) % 100] = ch.globalErr;     // GlobalErrorRateRecord.push_back
-                path_set(paths + (uint64_t)ch.path * pathw, ch.path_len, ch.ext);
-                ch.path_len++;
-                nxt[w] = ch;                                       // compaction
-                ++w;
+#pragma unroll
+                for(uint32_t j = 0; j < G; ++j) {
+                    if(!live[j]) continue;
+                    bool further;
+                    if constexpr(BIG) further = bits_get(this->seen_bits, parent[j]); else further = ((seen >> parent[j]) & 1u) != 0;
+                    if(further) {
+                        // a further child of this parent: copies of the ring and of the path as they are BEFORE this step's appends
+                        // (the in-place child of the parent has only written slots the copies do not read: see below)
+                        const uint32_t pr = ring[j], pp = path[j];
+                        if constexpr(BIG) {                                                  // survivors <= cap slots: never empty here
+                            ring[j] = bits_take_lowest(this->ring_bits, this->cap);
+                            path[j] = bits_take_lowest(this->path_bits, this->cap);
+                        } else {
+                            ring[j] = (uint32_t)__builtin_ctz(ring_free); ring_free &= ring_free - 1u;     // survivors <= 32 slots: never empty here
+                            path[j] = (uint32_t)__builtin_ctz(path_free); path_free &= path_free - 1u;
+                        }
+                        // The ring: only the slots the lineage has pushed so far.  The parent has made hist_size - 1 pushes (its
+                        // hist_size is this child's minus the push of this step), into slots 0, 1, ... in turn, wrapping at 100.
+                        // computeErrorRate is the only reader of a slot: it reads (totalsize - localK) % 100 once totalsize >=
+                        // localK = 100, the slot written 100 pushes earlier on the same lineage.  So a slot at or beyond the
+                        // number of pushes is never read before it has been written, and need not be copied.  The count is
+                        // rounded up to whole bursts (a row is 10 of them): what that copies beyond the live slots is the
+                        // child's own slot -- as the parent's in-place child may or may not have written it yet -- which the
+                        // push below overwrites, and slots of the never-read kind.
+                        const uint32_t nlive = hist_size[j] - 1 < 100 ? hist_size[j] - 1 : 100;
+                        const uint32_t nburst = (nlive * 8 + kCopyChunk16 * 16 - 1) / (kCopyChunk16 * 16);
+                        burst_copy16(rings + (uint64_t)ring[j] * 100, rings + (uint64_t)pr * 100, nburst);
+                        burst_copy4(paths + (uint64_t)path[j] * pathw, paths + (uint64_t)pp * pathw, (plen[j] + 16) >> 4);
+                    }
+                    if constexpr(BIG) bits_set(this->seen_bits, parent[j]); else seen |= 1u << parent[j];
+                }
+                uint32_t word[G];
+#pragma unroll
+                for(uint32_t j = 0; j < G; ++j) word[j] = paths[(uint64_t)path[j] * pathw + (plen[j] >> 4)];
+#pragma unroll
+                for(uint32_t j = 0; j < G; ++j) {
+                    if(!live[j]) continue;
+                    rings[(uint64_t)ring[j] * 100 + (hist_size[j] - 1) % 100] = globalErr[j];     // GlobalErrorRateRecord.push_back
+                    const uint32_t sh = 2 * (plen[j] & 15u);                                     // path_set
+                    paths[(uint64_t)path[j] * pathw + (plen[j] >> 4)] = (word[j] & ~(3u << sh)) | (ext[j] << sh);
+                    if(w != c0 + j) leaf_move(&nxt[w], &nxt[c0 + j]);  // compaction
+                    nxt[w].ring = (uint16_t)ring[j]; nxt[w].path = (uint16_t)path[j]; nxt[w].path_len = plen[j] + 1;
+                    ++w;
+                }
             }
-            (void)want_term;
             // m_leaves = newLeaves: the two leaf buffers trade places when the old `cur` region (32 or kMaxChildren slots) can take
             // the next step's children (4 per survivor); otherwise the survivors are copied down as before
             if(4u * w <= (cur == leaf_small ? small_cap() : max_children())) { Leaf<P>* t2 = cur; cur = nxt; nxt = t2; }
@@ -1208,10 +1403,23 @@ struct Walk : WalkCap<BIG> {
             n_cur = w;
             tock(5, t);
             t = tick();
+            // isTerminated over the new frontier.  term_scan starts with a filter on the leaf's last characters that rules most
+            // leaves out; it is a function of suf_lo and of the walk's constants alone, and terminated_leaf writes nothing but its
+            // own leaf's result index, the result slots and `error`.  So the suffixes of kTermGroup leaves are loaded together and
+            // a leaf the filter rules out is passed over without its own round trip; the others go through terminated_leaf in
+            // leaf order, with the same stop at the first error.
             if(currentLength >= minLength)
-                for(uint32_t i = 0; i < n_cur; ++i) {
-                    terminated_leaf(cur[i], paths + (uint64_t)cur[i].path * pathw, cur[i].path_len, -1);
-                    if(error) return;
+                for(uint32_t i0 = 0; i0 < n_cur; i0 += kTermGroup) {
+                    uint64_t slo[kTermGroup];
+#pragma unroll
+                    for(uint32_t j = 0; j < kTermGroup; ++j) slo[j] = cur[i0 + j < n_cur ? i0 + j : i0].suf_lo;
+#pragma unroll
+                    for(uint32_t j = 0; j < kTermGroup; ++j) {
+                        const uint32_t i = i0 + j;
+                        if(i >= n_cur || !term_may_hit(slo[j])) continue;
+                        terminated_leaf(cur[i], paths + (uint64_t)cur[i].path * pathw, cur[i].path_len, -1);
+                        if(error) return;
+                    }
                 }
             tock(6, t);
         }

@@ -361,8 +361,9 @@ __global__ __launch_bounds__(64, LRSC_WP_EXTEND_OCC) void wp_extend_kernel(FmInd
     bool fast = false;
     uint32_t gen_wait = 0;
     bool want_gen = false;
-    // profiling (a.prof): per-lane wall ticks inside the step's regions (Walk::tock slots 0-6), 8 = refill, 9 = finish, 10 = whole loop
-    uint64_t pr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    // profiling (a.prof): per-lane wall ticks inside the step's regions (Walk::tock slots 0-6, 7 = fast steps, 8 = SelectFreqsOfrange,
+    // which goes to a.prof[13]); a.prof[8] = refill, 9 = finish, 10 = whole loop
+    uint64_t pr[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint64_t t_refill = 0, t_finish = 0, n_fast = 0;
     const bool prof = a.prof != nullptr;
     if(prof) W.prof = pr;
@@ -418,6 +419,7 @@ __global__ __launch_bounds__(64, LRSC_WP_EXTEND_OCC) void wp_extend_kernel(FmInd
         atomicAdd(&a.prof[10], (unsigned long long)(__builtin_readcyclecounter() - t_loop0));
         atomicAdd(&a.prof[11], (unsigned long long)W.steps);
         atomicAdd(&a.prof[12], (unsigned long long)n_fast);
+        atomicAdd(&a.prof[13], (unsigned long long)pr[8]);
     }
     flush_counters(a.ctr, W.n_rank, W.n_blk);
 }
