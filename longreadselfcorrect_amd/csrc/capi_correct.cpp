@@ -224,10 +224,11 @@ int WpFlow::bind_args()
         b->walk_log_done = false;
     }
     if(tn.profile) {
-        HIP_TRY(sc.d_prof.reserve(36));                                      // [16..32): the long-gap walks' side launch on its own
-        HIP_TRY(hipMemsetAsync(sc.d_prof.p, 0, 36 * sizeof(unsigned long long), ctx->stream));
+        HIP_TRY(sc.d_prof.reserve(kWpProfWords));                              // [16..32): the long-gap walks' side launch on its own
+        HIP_TRY(hipMemsetAsync(sc.d_prof.p, 0, kWpProfWords * sizeof(unsigned long long), ctx->stream));
         a.prof = sc.d_prof.p;
         a.begin_stats = sc.d_prof.p + 32;                                    // [32..36): wp_begin's interval lists, zeroed every round
+                                                                             // [36..46): WpArgs::gen_stats of round 0's bulk launch
     }
     // side stream: the few walks across long gaps run beside the DP stage of the bulk's failed walks instead of before it (they are
     // latency-bound on their own: a walk is a chain of dependent steps)
@@ -382,6 +383,8 @@ int WpFlow::launch_order(Round& R)
 // until it ends.
 // LRSC_WP_WAVE, one-walk-per-wavefront launches: 1 = the frontier across the wavefront (wp_extend_wave_kernel), 0 = lane 0 walks alone
 // (wp_extend_kernel); 2 = test hook: every extension launch goes through wp_extend_wave_kernel at stride 64
+// LRSC_WP_DEAL, lane-per-walk launches: 1 = extendLeaves' per-leaf work dealt across the wavefront (wp_extend_deal_kernel), 0 = the
+// serial step (wp_extend_kernel)
 hipError_t WpFlow::extend_range(WpArgs x, const uint32_t* list, const WpRequest* rq, uint32_t count, uint32_t pathw, hipStream_t st,
                                 bool side, uint32_t stride)
 {
@@ -402,6 +405,7 @@ hipError_t WpFlow::extend_range(WpArgs x, const uint32_t* list, const WpRequest*
     e = hipMemsetAsync(x.queue, 0, sizeof(uint32_t), st);
     if(e != hipSuccess) return e;
     if(stride == 64 && tn.wp_wave != 0) return launch_wp_extend_wave(ctx->fm, x, st);
+    if(stride == 1 && tn.wp_deal != 0) return launch_wp_extend_deal(ctx->fm, x, st);
     return launch_wp_extend(ctx->fm, x, st);
 }
 
@@ -417,7 +421,9 @@ int WpFlow::extension_launches(Round& R)
             return extend_range(a, a.list, a.reqs, R.n_ent, std::max(R.stats[2], 1u), ctx->stream, false,
                                 R.n_ent <= 16384 ? 64u : R.n_ent <= 65536 ? 16u : 1u);
         // round 0: the bulk, one walk per lane
-        e = extend_range(a, R.ext_list + R.n_mid, nullptr, R.n_ent - R.n_mid, std::min(R.stats[2], kWpPathwSmall), ctx->stream, false, 1);
+        WpArgs xb = a;
+        if(a.prof) xb.gen_stats = a.prof + 36;
+        e = extend_range(xb, R.ext_list + R.n_mid, nullptr, R.n_ent - R.n_mid, std::min(R.stats[2], kWpPathwSmall), ctx->stream, false, 1);
         if(e != hipSuccess || R.n_mid == 0) return e;
         // then the walks across long gaps (the first n_mid of the launch order), one walk per wavefront: a lane-per-walk wavefront
         // advances at the pace of its slowest lane, and these are thousands of wide steps long.  With --nodp, or escalating (the
@@ -619,7 +625,7 @@ void WpFlow::print_round(const Round& R) const
 // per-region lane ticks of the extension kernels over the whole call
 int WpFlow::print_extension_profile()
 {
-    unsigned long long prs[32];
+    unsigned long long prs[kWpProfWords];
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     HIP_TRY(hipStreamSynchronize(sc.side));
     HIP_TRY(hipMemcpy(prs, sc.d_prof.p, sizeof(prs), hipMemcpyDeviceToHost));
@@ -632,6 +638,18 @@ int WpFlow::print_extension_profile()
                      part ? "long-gap walks, one per wavefront" : "bulk and later rounds",
                      all, all / st, st, 100 * pr[0] / all, 100 * pr[1] / all, 100 * pr[2] / all, 100 * pr[3] / all, 100 * pr[13] / all, 100 * pr[4] / all, 100 * pr[5] / all, 100 * pr[6] / all,
                      100 * pr[8] / all, 100 * pr[9] / all, 100 * pr[12] / st, 100 * pr[7] / all);
+    }
+    // what a general step of a lane-per-walk wavefront costs against the work in it: the serial step lasts as long as the widest
+    // frontier among the lanes taking part, so it pays (maximum x lanes) leaf passes for (sum) leaves
+    const unsigned long long* g = prs + 36;
+    if(g[0]) {
+        const double s = (double)g[0];
+        std::fprintf(stderr, "[lrsc] wp bulk launches, general steps of a wavefront: %llu, %.1f lanes taking part; leaves per step %.1f in all, %.2f per lane, %.2f in the widest "
+                             "(widest x lanes / all = %.2f; %.2f passes of 64 lanes); children after extendLeaves %.1f in all, %.2f per lane, %.2f in the widest "
+                             "(%.2f; %.2f passes); counters %llu %llu %llu %llu %llu %llu %llu %llu %llu %llu\n",
+                     g[0], g[1] / s, g[2] / s, (double)g[2] / std::max(g[1], 1ull), g[3] / s, (double)g[6] / std::max(g[2], 1ull), g[8] / s,
+                     g[4] / s, (double)g[4] / std::max(g[1], 1ull), g[5] / s, (double)g[7] / std::max(g[4], 1ull), g[9] / s,
+                     g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], g[9]);
     }
     return LRSC_OK;
 }

@@ -96,7 +96,7 @@ struct DevArena {
 // (read_tunables, capi_core.cpp; the tests change them between calls of one process, so never cached)
 struct Tunables {
     bool profile, wp_dump, dp_debug;
-    uint32_t wp_wide_cap, wp_wave, wp_lanes;
+    uint32_t wp_wide_cap, wp_wave, wp_deal, wp_lanes;
     bool wp_begin_sort;
     uint64_t wp_prep_bytes, wp_lane_bytes;
     uint32_t wp_gen_quorum, wp_gen_wait;

@@ -20,7 +20,10 @@
 #endif
 // Test hook: tests/host_walk_groups defines LRSC_WALK_TRACE(kind, a, b) to learn which shapes of the general step its inputs have
 // reached (kind 0: a step with a leaves; 1: extendLeaves made a children; 2: the threshold retry taken for leaf a of b; 3:
-// SelectFreqsOfrange over a leaves; 4: the children overflowed).  Empty in the product and in every other build.
+// SelectFreqsOfrange over a leaves; 4: the children overflowed; 5 / 6: extendLeaves' level-1 / level-2 retry over a leaves; 7: the
+// isInsufficientFreqs refine of a children; 8: the trim removed a leaves; 9: a further child of parent a gets ring and path copies;
+// 10: the overflow branch with a survivors; 11: a hit stored in result slot a).  tests/host_walk_deal uses it too.  Empty in the
+// product and in every other build.
 #ifndef LRSC_WALK_TRACE
 #define LRSC_WALK_TRACE(kind, a, b)
 #endif
@@ -603,6 +606,7 @@ struct Walk : WalkCap<BIG> {
             if(w != i) leaf_move(&cur[w], &cur[i]);
             ++w;
         }
+        if(w != n_cur) { LRSC_WALK_TRACE(8, n_cur - w, w); }
         n_cur = w;
 
         n_highfreq = 0;
@@ -668,6 +672,7 @@ struct Walk : WalkCap<BIG> {
         tock(2, t);
         if(error) return;
         if(n_nxt == 0) {                                    // level 1: reduce the k-mer size
+            LRSC_WALK_TRACE(5, n_cur, 0);
             const uint64_t LowerBound = (currentKmerSize - 2) > minOverlap ? (currentKmerSize - 2) : minOverlap;
             const uint64_t ts = tick();
             const uint64_t ReduceSize = SelectFreqsOfrange(LowerBound, currentKmerSize, cur, n_cur);
@@ -676,6 +681,7 @@ struct Walk : WalkCap<BIG> {
             attempToExtend();
             if(error) return;
             if(n_nxt == 0) {                                // level 2: reduce the threshold
+                LRSC_WALK_TRACE(6, n_cur, 0);
                 min_SA_threshold--;
                 attempToExtend();
                 min_SA_threshold++;
@@ -686,6 +692,7 @@ struct Walk : WalkCap<BIG> {
             currentLength++;
             currentKmerSize++;
             if(isInsufficientFreqs(n_highfreq, n_nxt)) {    // frequencies are low: relax the k-mer size
+                LRSC_WALK_TRACE(7, n_nxt, 0);
                 const uint64_t LowerBound = (currentKmerSize - 2) > minOverlap ? (currentKmerSize - 2) : minOverlap;
                 const uint64_t ts = tick();
                 const uint64_t ReduceSize = SelectFreqsOfrange(LowerBound, currentKmerSize, nxt, n_nxt);
@@ -958,6 +965,7 @@ struct Walk : WalkCap<BIG> {
             lf.res_first = (int)n_results;
         }
         lf.res_second = hit;
+        LRSC_WALK_TRACE(11, lf.res_first, 0);
         term_store(lf, hit, pw, plen, extra);
     }
     // term_scan's filter: false = no target minOverlap-mer hashes like the last characters of the leaf's suffix
@@ -1291,7 +1299,15 @@ struct Walk : WalkCap<BIG> {
             tock(0, t);
             if(error) return;
             LRSC_WALK_TRACE(1, n_nxt, 0);
-            t = tick();
+        }
+        step_after_extend();
+    }
+
+    // the step from PrunedBySeedSupport on: what follows extendLeaves (or its dealt form, wp_deal.hip) in the walk's own lane
+    LRSC_WALK_FN void step_after_extend()
+    {
+        {
+            uint64_t t = tick();
             PrunedBySeedSupport();
             tock(4, t);
             t = tick();
@@ -1303,6 +1319,7 @@ struct Walk : WalkCap<BIG> {
             };
             ++steps;
             if(survivors > maxLeaves) {
+                LRSC_WALK_TRACE(10, survivors, 0);
                 // the frontier overflows: the loop ends after this isTerminated, no leaf state is needed any more
                 if(currentLength >= minLength)
                     for(uint32_t c = 0; c < n_nxt; ++c) {
@@ -1357,6 +1374,7 @@ struct Walk : WalkCap<BIG> {
                     bool further;
                     if constexpr(BIG) further = bits_get(this->seen_bits, parent[j]); else further = ((seen >> parent[j]) & 1u) != 0;
                     if(further) {
+                        LRSC_WALK_TRACE(9, parent[j], 0);
                         // a further child of this parent: copies of the ring and of the path as they are BEFORE this step's appends
                         // (the in-place child of the parent has only written slots the copies do not read: see below)
                         const uint32_t pr = ring[j], pp = path[j];

@@ -198,7 +198,13 @@ struct WpArgs {
     uint32_t* n_sort9;
     uint32_t begin_sort;
     unsigned long long* begin_stats; // LRSC_CORRECT_PROFILE: lists, lists with a repeated code, entries of the lists without / with one
+    // LRSC_CORRECT_PROFILE, round 0's bulk launch only (nullptr elsewhere): over the general steps its wavefronts take, [0] steps,
+    // [1] lanes taking part, [2] sum and [3] sum of the per-step maximum of their n_cur, [4] / [5] the same of n_nxt after extendLeaves,
+    // [6] / [7] sum of (maximum x lanes taking part) for n_cur / n_nxt, [8] / [9] sum of ceil(sum / 64): the passes of 64 lanes that
+    // the step's leaves / children fill
+    unsigned long long* gen_stats;
 };
+constexpr uint32_t kWpProfWords = 46;        // WpArgs::prof [0, 32), begin_stats [32, 36), gen_stats [36, 46)
 
 constexpr uint32_t kWpPathwSmall = 64, kWpPathwMid = 256;
 
@@ -227,6 +233,8 @@ hipError_t launch_wp_prepare(const FmIndexDev& fm, const WpArgs& a, hipStream_t 
 // two launches: the tables of every walk without the sort, then the sort for the lists that pass 1 put on a.sort9
 hipError_t launch_wp_begin(const FmIndexDev& fm, const WpArgs& a, hipStream_t stream);
 hipError_t launch_wp_extend(const FmIndexDev& fm, const WpArgs& a, hipStream_t stream);
+// lane_stride 1 launches with extendLeaves' per-leaf work dealt across the wavefront (wp_deal.hip)
+hipError_t launch_wp_extend_deal(const FmIndexDev& fm, const WpArgs& a, hipStream_t stream);
 // lane_stride 64 launches with the frontier across the wavefront (wp_wave.hip): one wavefront per walk in flight (a.n_lanes of them)
 hipError_t launch_wp_extend_wave(const FmIndexDev& fm, const WpArgs& a, hipStream_t stream);
 // static LDS of one workgroup of that kernel, as the code object states it

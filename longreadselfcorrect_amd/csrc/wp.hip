@@ -404,7 +404,9 @@ __global__ __launch_bounds__(64, LRSC_WP_EXTEND_OCC) void wp_extend_kernel(FmInd
             const bool waited = __ballot(gen_wait >= a.general_max_wait) != 0;
             if(n_need * 100u < n_busy * a.general_quorum_pct && !waited) { ++gen_wait; want_gen = true; continue; }
             gen_wait = 0; want_gen = false;
+            const uint32_t n_cur0 = W.n_cur;
             r = W.step() ? 1 : 0;
+            if(a.gen_stats) wp_gen_count(a.gen_stats, r == 1, n_cur0, W.n_nxt);
         }
         if(r == 1) continue;
         in_walk = false;

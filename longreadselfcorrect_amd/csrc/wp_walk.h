@@ -42,6 +42,38 @@ __device__ __forceinline__ void wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
+// a.gen_stats: one general step of a lane-per-walk wavefront.  Called by the lanes that went into the step together; `took` = the
+// lane's Walk::step() ran its body.  Sums and maxima over those lanes a bit plane at a time (ballots only: nothing crosses a lane
+// that is not here), added by the first of them.
+__device__ __forceinline__ void wp_gen_count(unsigned long long* g, bool took, uint32_t n_cur, uint32_t n_nxt)
+{
+    const uint64_t m = __ballot(took);
+    if(m == 0) return;
+    uint32_t sum[2], mx[2];
+    for(int k = 0; k < 2; ++k) {
+        const uint32_t v = k ? n_nxt : n_cur;
+        bool cand = took;
+        sum[k] = 0; mx[k] = 0;
+        for(int b = 15; b >= 0; --b) {
+            const bool bit = took && ((v >> b) & 1u);
+            sum[k] += (uint32_t)__builtin_popcountll(__ballot(bit)) << b;
+            if(__ballot(cand && bit)) { mx[k] |= 1u << b; cand = cand && bit; }
+        }
+    }
+    if(threadIdx.x == (uint32_t)__builtin_ctzll(m)) {
+        atomicAdd(&g[0], 1ull);
+        atomicAdd(&g[1], (unsigned long long)__builtin_popcountll(m));
+        atomicAdd(&g[2], (unsigned long long)sum[0]); atomicAdd(&g[3], (unsigned long long)mx[0]);
+        atomicAdd(&g[4], (unsigned long long)sum[1]); atomicAdd(&g[5], (unsigned long long)mx[1]);
+        // what the serial step pays for, in leaf passes: every lane taking part waits for the widest one
+        atomicAdd(&g[6], (unsigned long long)mx[0] * (unsigned long long)__builtin_popcountll(m));
+        atomicAdd(&g[7], (unsigned long long)mx[1] * (unsigned long long)__builtin_popcountll(m));
+        // ... and what the same leaves are in passes of 64 lanes
+        atomicAdd(&g[8], (unsigned long long)((sum[0] + 63u) / 64u));
+        atomicAdd(&g[9], (unsigned long long)((sum[1] + 63u) / 64u));
+    }
+}
+
 // ---- a walk's slot: setup and finish ----------------------------------------------------------------------------------------
 // the walk's fixed inputs: the query and the tables wp_prepare_kernel / wp_begin_kernel built in the slot's prepared workspace
 template <bool WIDE, bool BIG>
