@@ -364,6 +364,53 @@ typedef struct lrsc_overlap_read { uint32_t is_substring, n_blocks, status, pad;
 int lrsc_overlap_exact(lrsc_ctx* ctx, const char* reads, const uint64_t* read_off, uint32_t n_reads, int32_t min_overlap,
                        lrsc_overlap_read* per_read, lrsc_overlap_block* blocks, uint64_t block_cap, uint64_t* n_blocks_out);
 
+/* ---- unambiguous read merging: `stride fm-merge` (StriDe/fm-merge.cpp:60-221; Algorithm/FMMergeProcess.cpp:30-230 process, 233-251
+ * checkCandidate, 253-310 addCandidates, 313-329 FMMergePostProcess; Algorithm/OverlapBlock.cpp:119-160 getEdgeDir, toOverlap;
+ * Bigraph/Bigraph.cpp:162-220 merge, 452-524 simplify; Bigraph/Vertex.cpp:30-75 Vertex::merge) ---- */
+/* A read's place: sequence `seq` holds it at `offset`, as its reverse complement when LRSC_FMMERGE_REVERSED.  A read with
+ * LRSC_FMMERGE_DROPPED is used by sequence `seq` but absent from it (below), its offset is 0.  LRSC_FMMERGE_SELF_LINK: the only
+ * block on one of its ends is the read itself, where the reference asserts; that end has no link. */
+typedef struct lrsc_fmmerge_read { uint32_t seq, flags; uint64_t offset; } lrsc_fmmerge_read;
+#define LRSC_FMMERGE_REVERSED 1
+#define LRSC_FMMERGE_DROPPED 2
+#define LRSC_FMMERGE_SELF_LINK 4
+/* Sequence i, "merged-i": bases[offset .. offset + length), made of n_reads reads, on the forward strand of read `root`. */
+typedef struct lrsc_fmmerge_seq { uint64_t offset, length; uint32_t n_reads, root, circular, pad; } lrsc_fmmerge_seq;
+/* lrsc_fmmerge refuses more reads (LRSC_ERR_UNSUPPORTED): a node, 2 * read + end, is a 32-bit number.  Distances are 64 bits. */
+#define LRSC_FMMERGE_MAX_READS 0x7FFFFFFFu
+/* FMMergeProcess::process over all reads of the ctx's index at once: every run of reads that overlap unambiguously becomes one
+ * sequence.  An end of a read (ED_SENSE for query_rev == 0, ED_ANTISENSE for query_rev == 1) has a link when exactly one final
+ * non-containment block of lrsc_overlap_exact stands on it; the link is mutual when the target's end has exactly one block and
+ * that block leads back.  Reads joined by mutual links form chains, paths or cycles, and a chain is merged along its overlaps.
+ * Three things the reference leaves to the iteration order of a hash map, or to an assertion, are decided here:
+ *   - a sequence reads on the forward strand of `root`, the chain's lowest-numbered read that is in the sequence; a cycle starts
+ *     with that read whole and runs towards its sense end, once round, so it ends with the closing overlap (circular = 1).
+ *     Sequences come in the order of their lowest-numbered used read.
+ *   - a candidate that checkCandidate refuses stays red although the other arm of the search accepted it: where the end of a
+ *     path links to the other end Q of the same path and Q's end there has several blocks (a cycle with a read leading into it
+ *     at Q), Q is used but absent from the output: LRSC_FMMERGE_DROPPED.
+ *   - an end whose only block is the read itself has no link: LRSC_FMMERGE_SELF_LINK.
+ * n_reads must be the index's num_strings and the reads those of the index (LRSC_ERR_ARG); the lexicographic orders are
+ * prepared as by lrsc_index_locate_prepare(rate 0) when the device has none.  LRSC_ERR_ARG "fm-merge requires `stride filter`
+ * first" with the first such read when a block or a read's own interval has more than one row or a read is a substring;
+ * LRSC_ERR_ARG when a read's own row is not in its interval (another index); LRSC_ERR_LIMIT when a read's overlap status is
+ * LRSC_OVERLAP_OVERFLOW; LRSC_ERR_FORMAT when a read's blocks lie outside the pool; otherwise the errors of lrsc_overlap_exact.  On
+ * all of these the outputs are untouched.  The four above show in a read's final blocks, so after the three launches of its chunk:
+ * the call ends with the first chunk that shows one, without the overlap of the chunks behind it.  Everything else is refused before
+ * the first launch.
+ * LRSC_ERR_CAPACITY when bases_cap is too small: *n_bases_out is then the bases needed and nothing else is written.
+ * per_read and seqs hold n_reads records.  n_reads == 0 launches nothing.
+ * Launches, all counted under LRSC_K_FIND: 3 per chunk of reads (the overlap's two and the links), the chunk being
+ * min(32768, 2^28 / (4 * (48 * (longest read - min_overlap) + 64)) rounded down to a multiple of 16) reads; then, with
+ * R = ceil(log2(2 n)), the chain phase's 2 * (1 + R) + 1 (two rankings by pointer doubling over the 2 n (read, exit end) nodes, the
+ * cut of cycles and dropped reads between them), 2 for the placement, 3 for the prefix sums and 1 for the bases: together
+ * 3 * chunks + 2 * R + 9 (the last two are not made when bases_cap is too small).  No launch walks a chain link by link; the state
+ * on the device is O(n_reads) beside the bases.  With LRSC_FMMERGE_PROFILE set in the environment the entry prints one line to
+ * stderr, the kernels' milliseconds by phase (overlap, links, chains, place, assemble), as LRSC_BWT_PROFILE does for the index
+ * entries; tools/fm_merge_rate.py reads it. */
+int lrsc_fmmerge(lrsc_ctx* ctx, const char* reads, const uint64_t* read_off, uint32_t n_reads, int32_t min_overlap, lrsc_fmmerge_read* per_read,
+                 lrsc_fmmerge_seq* seqs, uint32_t* n_seqs_out, char* bases, uint64_t bases_cap, uint64_t* n_bases_out);
+
 /* ---- LongReadProbe k-mer feature grid -------------------------------------------------- */
 /* reads: concatenated ACGT bytes, read_off: n_reads+1 offsets.  ks: ascending k-mer sizes
  * (the "pool", e.g. {5,9,15,17,19}), n_k <= 8.  For read r, position p, pool slot j the record

@@ -205,6 +205,8 @@ FMWALK_HYBRID_DTYPE = np.dtype([("walk", FMWALK_DTYPE), ("read", FMWALK_READ_DTY
 OVERLAP_READ_DTYPE = np.dtype([("is_substring", "<u4"), ("n_blocks", "<u4"), ("status", "<u4"), ("pad", "<u4"), ("first_block", "<u8")])      # lrsc_overlap_read
 OVERLAP_BLOCK_DTYPE = np.dtype([("lower", "<i8"), ("upper", "<i8"), ("overlap_len", "<u4"), ("target_rev", "u1"), ("query_rev", "u1"), ("query_comp", "u1"),
                                 ("contained", "u1")])                 # lrsc_overlap_block
+FMMERGE_READ_DTYPE = np.dtype([("seq", "<u4"), ("flags", "<u4"), ("offset", "<u8")])                                                           # lrsc_fmmerge_read
+FMMERGE_SEQ_DTYPE = np.dtype([("offset", "<u8"), ("length", "<u8"), ("n_reads", "<u4"), ("root", "<u4"), ("circular", "<u4"), ("pad", "<u4")])  # lrsc_fmmerge_seq
 assert RANK_DTYPE.itemsize == C.sizeof(RankQuery) and BIIV_DTYPE.itemsize == C.sizeof(BiInterval)
 
 
@@ -276,6 +278,7 @@ class Lrsc:
         L.lrsc_fmwalk_hybrid.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                          C.c_uint64]
         L.lrsc_overlap_exact.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+        L.lrsc_fmmerge.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         L.lrsc_params_default.argtypes = [C.c_int, C.c_int, C.POINTER(Params)]
         L.lrsc_ctx_create.argtypes = [C.c_void_p, C.POINTER(Params), C.c_int, C.POINTER(C.c_void_p)]
         L.lrsc_ctx_destroy.argtypes = [C.c_void_p]
@@ -633,6 +636,21 @@ class Ctx:
                 continue
             self.api.check(st, "lrsc_overlap_exact")
             return per_read, blocks[: int(used[0])].copy()
+
+    def fmmerge(self, bases: np.ndarray, off: np.ndarray, min_overlap: int = 45):
+        """lrsc_fmmerge of all reads of the index (ASCII bases, n + 1 offsets) -> (FMMERGE_READ_DTYPE per read, FMMERGE_SEQ_DTYPE per
+        sequence, the sequences' bases back to back as bytes).  The merged bases are never more than the reads'."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        n = off.size - 1
+        per_read = np.zeros(n, dtype=FMMERGE_READ_DTYPE)
+        seqs = np.zeros(max(n, 1), dtype=FMMERGE_SEQ_DTYPE)
+        out = np.zeros(max(int(bases.size), 1), dtype=np.uint8)
+        n_seqs = np.zeros(1, dtype=np.uint32)
+        n_bases = np.zeros(1, dtype=np.uint64)
+        self.api.check(self.api.lib.lrsc_fmmerge(self.h, _ptr(bases), _ptr(off), n, min_overlap, _ptr(per_read), _ptr(seqs), _ptr(n_seqs), _ptr(out), int(bases.size),
+                                                 _ptr(n_bases)), "lrsc_fmmerge")
+        return per_read, seqs[: int(n_seqs[0])].copy(), out[: int(n_bases[0])].tobytes()
 
     def rank(self, bases: np.ndarray, idx: np.ndarray, strand: np.ndarray | int) -> np.ndarray:
         n = len(idx)

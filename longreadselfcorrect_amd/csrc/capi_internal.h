@@ -204,6 +204,8 @@ struct lrsc_ctx {
     // lrsc_overlap_exact's: the wavefronts' workspace, the chains' heads and blocks, the reads' results, the pool of final blocks
     // behind its 8-byte counter
     lrsc::DevBuf<uint8_t> ov_ws, ov_heads, ov_chain, ov_outs, ov_pool;
+    // lrsc_fmmerge's: the links, the two node buffers, the words and the 64-bit words of the state, the records, the bases
+    lrsc::DevBuf<uint8_t> fm_links, fm_nodes, fm_words, fm_longs, fm_recs, fm_bases;
     ~lrsc_ctx();                                        // drains the stream, then frees cs and the ctx's own objects (capi_correct.cpp)
 };
 
@@ -270,6 +272,15 @@ int upload_and_encode(lrsc_ctx* ctx, const char* ascii, uint64_t n, uint8_t* d_c
 // checked, every read has a base and fewer than 2^limit_log2 ("<tool>: read i is empty", "<tool>: a read of 2^K bases or more");
 // then s_codes = the reads' codes with `slack` bytes behind them, s_off = their offsets, s_flag = 0, on the ctx's device.
 int stage_reads(lrsc_ctx* ctx, const char* tool, unsigned limit_log2, const char* reads, const uint64_t* read_off, uint32_t n_reads, uint64_t slack);
+
+// the exact overlap of a batch of reads chunk by chunk, for lrsc_overlap_exact and lrsc_fmmerge (capi_overlap.cpp)
+struct OverlapPlan {
+    uint32_t min_overlap, max_len, collect_groups, reduce_groups;
+    uint64_t chunk, slice, pool_cap;                              // reads per chunk, a wavefront's workspace, blocks the pool holds
+};
+int overlap_check_min(int32_t min_overlap);
+int overlap_plan(lrsc_ctx* ctx, const char* reads, const uint64_t* read_off, uint32_t n_reads, int32_t min_overlap, OverlapPlan& plan);
+int overlap_chunk(lrsc_ctx* ctx, const OverlapPlan& plan, uint64_t r0, uint32_t n);
 
 // what the entries that make an index on the device share (capi_index.cpp)
 void free_device_copy(DeviceCopy& dc);

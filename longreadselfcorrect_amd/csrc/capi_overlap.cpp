@@ -15,17 +15,18 @@ constexpr uint64_t kOvWorkspaceBytes = 1ull << 30;
 constexpr uint64_t kOvChainBytes = 256ull << 20;
 constexpr uint64_t kOvChunkReads = 1ull << 15;
 
-// OverlapAlgorithm::overlapRead in exact mode, irreducible edges only (Algorithm/OverlapAlgorithm.cpp:22-44, 270-344)
-extern "C" int lrsc_overlap_exact(lrsc_ctx* ctx, const char* reads, const uint64_t* read_off, uint32_t n_reads, int32_t min_overlap, lrsc_overlap_read* per_read,
-                                  lrsc_overlap_block* blocks, uint64_t block_cap, uint64_t* n_blocks_out)
+// min_overlap within 2 .. the kernel's limit: both entries ask before anything else, an empty batch included
+int lrsc::overlap_check_min(int32_t min_overlap)
 {
-    if(!ctx || !n_blocks_out || (n_reads && (!reads || !read_off || !per_read)) || (block_cap && !blocks)) return fail(LRSC_ERR_ARG, "null");
     if(min_overlap < 2) return fail(LRSC_ERR_ARG, "overlap: invalid min overlap: " + std::to_string(min_overlap));
     if((uint32_t)min_overlap > kOvMaxMinOverlap) return fail(LRSC_ERR_UNSUPPORTED, "overlap: above the kernel's limits (min overlap 2000, read length 2000)");
-    if(n_reads == 0) {
-        *n_blocks_out = 0;
-        return LRSC_OK;
-    }
+    return LRSC_OK;
+}
+
+// What lrsc_overlap_exact and lrsc_fmmerge do before their first launch, after overlap_check_min: the reads' checks, the reads
+// staged, the chunk and the grids sized, the ctx's overlap buffers reserved.  n_reads != 0.
+int lrsc::overlap_plan(lrsc_ctx* ctx, const char* reads, const uint64_t* read_off, uint32_t n_reads, int32_t min_overlap, OverlapPlan& plan)
+{
     int st = check_offsets(read_off, n_reads);
     if(st != LRSC_OK) return st;
     OvParams p{(uint32_t)min_overlap, 0u};
@@ -51,9 +52,45 @@ extern "C" int lrsc_overlap_exact(lrsc_ctx* ctx, const char* reads, const uint64
     HIP_TRY(ctx->ov_chain.reserve(std::max<uint64_t>(1, chunk * kOvChains * slots) * sizeof(OvBlock)));
     HIP_TRY(ctx->ov_outs.reserve(chunk * sizeof(OvOutRead)));
     HIP_TRY(ctx->ov_pool.reserve(8 + pool_cap * sizeof(OvOutBlock)));
+    plan = OverlapPlan{p.min_overlap, p.max_len, (uint32_t)collect_groups, (uint32_t)reduce_groups, chunk, slice, pool_cap};
+    return LRSC_OK;
+}
+
+// The collect and the reduce of the reads [r0, r0 + n), n <= plan.chunk: their results in ov_outs, their final blocks in ov_pool
+// behind its counter, their chains' heads in ov_heads, all on the ctx's stream
+int lrsc::overlap_chunk(lrsc_ctx* ctx, const OverlapPlan& plan, uint64_t r0, uint32_t n)
+{
+    const OvParams p{plan.min_overlap, plan.max_len};
     uint32_t* d_broken = reinterpret_cast<uint32_t*>(ctx->s_flag.p);
     OvChainHead* d_heads = reinterpret_cast<OvChainHead*>(ctx->ov_heads.p);
     OvBlock* d_chain = reinterpret_cast<OvBlock*>(ctx->ov_chain.p);
+    unsigned long long* d_used = reinterpret_cast<unsigned long long*>(ctx->ov_pool.p);
+    HIP_TRY(hipMemsetAsync(d_used, 0, 8, ctx->stream));
+    int st = timed_launch(ctx, LRSC_K_FIND, [&]() {
+        return launch_overlap_collect(ctx->fm, ctx->s_codes.p, ctx->s_off.p + r0, n, p, plan.collect_groups, d_heads, d_chain, d_broken, ctx->d_ctr, ctx->stream);
+    });
+    if(st != LRSC_OK) return st;
+    return timed_launch(ctx, LRSC_K_FIND, [&]() {
+        return launch_overlap_reduce(ctx->fm, ctx->s_off.p + r0, n, p, d_heads, d_chain, plan.reduce_groups, ctx->ov_ws.p, plan.slice, reinterpret_cast<OvOutRead*>(ctx->ov_outs.p),
+                                     reinterpret_cast<OvOutBlock*>(ctx->ov_pool.p + 8), plan.pool_cap, d_used, d_broken, ctx->d_ctr, ctx->stream);
+    });
+}
+
+// OverlapAlgorithm::overlapRead in exact mode, irreducible edges only (Algorithm/OverlapAlgorithm.cpp:22-44, 270-344)
+extern "C" int lrsc_overlap_exact(lrsc_ctx* ctx, const char* reads, const uint64_t* read_off, uint32_t n_reads, int32_t min_overlap, lrsc_overlap_read* per_read,
+                                  lrsc_overlap_block* blocks, uint64_t block_cap, uint64_t* n_blocks_out)
+{
+    if(!ctx || !n_blocks_out || (n_reads && (!reads || !read_off || !per_read)) || (block_cap && !blocks)) return fail(LRSC_ERR_ARG, "null");
+    int st = overlap_check_min(min_overlap);
+    if(st != LRSC_OK) return st;
+    if(n_reads == 0) {
+        *n_blocks_out = 0;
+        return LRSC_OK;
+    }
+    OverlapPlan plan;
+    st = overlap_plan(ctx, reads, read_off, n_reads, min_overlap, plan);
+    if(st != LRSC_OK) return st;
+    const uint64_t chunk = plan.chunk, pool_cap = plan.pool_cap;
     OvOutRead* d_outs = reinterpret_cast<OvOutRead*>(ctx->ov_outs.p);
     unsigned long long* d_used = reinterpret_cast<unsigned long long*>(ctx->ov_pool.p);
     OvOutBlock* d_pool = reinterpret_cast<OvOutBlock*>(ctx->ov_pool.p + 8);
@@ -63,15 +100,7 @@ extern "C" int lrsc_overlap_exact(lrsc_ctx* ctx, const char* reads, const uint64
     std::vector<OvOutBlock> pool;
     for(uint64_t r0 = 0; r0 < n_reads; r0 += chunk) {
         const uint32_t n = (uint32_t)std::min<uint64_t>(chunk, n_reads - r0);
-        HIP_TRY(hipMemsetAsync(d_used, 0, 8, ctx->stream));
-        st = timed_launch(ctx, LRSC_K_FIND, [&]() {
-            return launch_overlap_collect(ctx->fm, ctx->s_codes.p, ctx->s_off.p + r0, n, p, (uint32_t)collect_groups, d_heads, d_chain, d_broken, ctx->d_ctr, ctx->stream);
-        });
-        if(st != LRSC_OK) return st;
-        st = timed_launch(ctx, LRSC_K_FIND, [&]() {
-            return launch_overlap_reduce(ctx->fm, ctx->s_off.p + r0, n, p, d_heads, d_chain, (uint32_t)reduce_groups, ctx->ov_ws.p, slice, d_outs, d_pool, pool_cap, d_used,
-                                         d_broken, ctx->d_ctr, ctx->stream);
-        });
+        st = overlap_chunk(ctx, plan, r0, n);
         if(st != LRSC_OK) return st;
         int broken = 0;
         unsigned long long used = 0;

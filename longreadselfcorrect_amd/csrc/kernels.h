@@ -171,6 +171,29 @@ hipError_t launch_overlap_collect(const FmIndexDev& fm, const uint8_t* codes, co
 hipError_t launch_overlap_reduce(const FmIndexDev& fm, const uint64_t* read_off, uint32_t n_reads, const OvParams& p, const OvChainHead* heads, const OvBlock* chain_blocks,
                                  uint32_t groups, uint8_t* ws, uint64_t ws_slice, OvOutRead* outs, OvOutBlock* pool, uint64_t pool_cap, unsigned long long* pool_used,
                                  uint32_t* broken, DevCounters* ctr, hipStream_t stream);
+// The merge of unambiguously overlapping reads (fm_fmmerge.hip) on the state s of fm_fmmerge.h, every array on the device.
+// launch_fmmerge_links, a lane per read of the chunk [first, first + n_chunk) after its overlap launches: outs, pool, *pool_used
+// and heads are that chunk's, order0 / order1 the strands' lexicographic orders; the reads' links and their words of the state;
+// first_bad[kFmmBad...] = the lowest read that shows what the entry refuses (the caller sets them to kFmmNone).
+// launch_fmmerge_init / _round / _cut, a lane per node: the nodes before the first round, a round of doubling from `in` to `out`,
+// the cuts after the first ranking.  launch_fmmerge_place, a lane per read, after the second.  launch_fmmerge_scan, steps 0, 1,
+// 2: the prefix sums over the keys, tile_seqs and tile_bases holding fmmerge_scan_tiles(n) words, totals two (sequences, bases).
+// launch_fmmerge_finish: the records.  launch_fmmerge_assemble: the bases as characters, none at or behind n_bases.
+struct FmmState;
+struct FmmNode;
+struct FmmOutRead;
+struct FmmOutSeq;
+hipError_t launch_fmmerge_links(const FmmState& s, uint32_t first, uint32_t n_chunk, uint32_t min_overlap, const OvOutRead* outs, const OvOutBlock* pool,
+                                const unsigned long long* pool_used, const OvChainHead* heads, const uint32_t* order0, const uint32_t* order1, uint32_t* first_bad,
+                                hipStream_t stream);
+hipError_t launch_fmmerge_init(const FmmState& s, FmmNode* nodes, hipStream_t stream);
+hipError_t launch_fmmerge_round(const FmmState& s, const FmmNode* in, FmmNode* out, hipStream_t stream);
+hipError_t launch_fmmerge_cut(const FmmState& s, const FmmNode* nodes, hipStream_t stream);
+hipError_t launch_fmmerge_place(const FmmState& s, const FmmNode* nodes, hipStream_t stream);
+uint32_t fmmerge_scan_tiles(uint32_t n);
+hipError_t launch_fmmerge_scan(const FmmState& s, int step, uint32_t* tile_seqs, unsigned long long* tile_bases, unsigned long long* totals, hipStream_t stream);
+hipError_t launch_fmmerge_finish(const FmmState& s, FmmOutRead* per_read, FmmOutSeq* seqs, hipStream_t stream);
+hipError_t launch_fmmerge_assemble(const FmmState& s, const uint8_t* codes, char* bases, uint64_t n_bases, hipStream_t stream);
 hipError_t launch_bwt_chars(const FmIndexDev& fm, int strand, const uint64_t* idx, uint64_t n, char* out,
                             hipStream_t stream);
 hipError_t launch_find_kmers(const FmIndexDev& fm, const uint8_t* kmer_codes, uint32_t k, uint64_t n,

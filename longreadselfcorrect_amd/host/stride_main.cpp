@@ -1,5 +1,5 @@
 // stride_main.cpp -- `stride pbcorrect` (a.k.a. PacBioSelfCorrection), `stride index`, `stride merge`, `stride sai`,
-// `stride grep`, `stride filter`, `stride correct`, `stride fmwalk` and `stride overlap` on the MI355X back end.  Option surface, defaults, validation messages and exit codes follow the reference's
+// `stride grep`, `stride filter`, `stride correct`, `stride fmwalk`, `stride overlap` and `stride fm-merge` on the MI355X back end.  Option surface, defaults, validation messages and exit codes follow the reference's
 // StriDe/PacBioSelfCorrection.cpp:32-140,262-434 and StriDe/StriDe.cpp:62-126; extra flags: --devices, --batch.
 #include <getopt.h>
 
@@ -18,6 +18,7 @@
 #include "BCode.h"
 #include "ErrorCorrectProcess.h"
 #include "FMIndexWalkProcess.h"
+#include "FMMergeProcess.h"
 #include "KmerDistribution.h"
 #include "LexicoOrder.h"
 #include "OverlapProcess.h"
@@ -1351,13 +1352,130 @@ static int overlapMain(int argc, char** argv)
     return 0;
 }
 
+// `stride fm-merge READSFILE`: the reference's fm-merge (StriDe/fm-merge.cpp:83-220).  Every run of reads that overlap each other
+// unambiguously becomes one sequence of PREFIX.merged.fa, all reads in one lrsc_fmmerge call (FMMergeProcess.h).  -t is accepted:
+// the device does the work.  Not taken over: the time stamp, printInfo, and the per-graph "<Simplify>" lines.
+static const char* FMMERGE_USAGE_MESSAGE =
+    "Usage: " PACKAGE_NAME " fm-merge [OPTION] ... READSFILE\n"
+    "Merge unambiguously sequences from the READSFILE using the FM-index.\n"
+    "This program requires rmdup to be run before it.\n"
+    "\n"
+    "      --help                           display this help and exit\n"
+    "      -v, --verbose                    display verbose output\n"
+    "      -p, --prefix=PREFIX              use PREFIX for the names of the index files (default: prefix of the input file)\n"
+    "      -t, --threads=NUM                use NUM worker threads (default: no threading)\n"
+    "      -m, --min-overlap=LEN            minimum overlap required between two reads to merge (default: 45)\n"
+    "      -o, --outfile=FILE               write the merged sequences to FILE (default: basename.merged.fa)\n"
+    "      --build-index                    index READSFILE in memory on the device instead of loading PREFIX.bwt/.rbwt\n"
+    "      --load-on-device                 decode PREFIX.bwt/.rbwt on the device (what loading does here; accepted for symmetry)\n"
+    "      --device=N                       HIP device to work on (default: 0)\n"
+    "\nReport bugs to " PACKAGE_BUGREPORT "\n\n";
+
+namespace fmmergeopt {
+static unsigned int verbose = 0;
+static int numThreads = 1, device = 0;
+static unsigned int minOverlap = 45;
+static std::string prefix, readsFile, outFile;
+static bool buildIndex = false;
+}
+
+static void parseFMMergeOptions(int argc, char** argv)
+{
+    enum { O_HELP = 1, O_VERSION, O_DEVICE, O_BUILDINDEX, O_LOADONDEVICE };
+    static const struct option fmmerge_longopts[] = {
+        {"prefix", required_argument, nullptr, 'p'},          {"verbose", no_argument, nullptr, 'v'},
+        {"threads", required_argument, nullptr, 't'},         {"min-overlap", required_argument, nullptr, 'm'},
+        {"outfile", required_argument, nullptr, 'o'},         {"help", no_argument, nullptr, O_HELP},
+        {"version", no_argument, nullptr, O_VERSION},         {"device", required_argument, nullptr, O_DEVICE},
+        {"build-index", no_argument, nullptr, O_BUILDINDEX},  {"load-on-device", no_argument, nullptr, O_LOADONDEVICE},
+        {nullptr, 0, nullptr, 0}};
+    optind = 1;
+    bool die = false;
+    for(int c; (c = getopt_long(argc, argv, "p:m:d:e:t:l:s:o:vix", fmmerge_longopts, nullptr)) != -1;) {
+        std::istringstream arg(optarg != nullptr ? optarg : "");
+        switch(c) {
+            case 'm': arg >> fmmergeopt::minOverlap; break;
+            case 'p': arg >> fmmergeopt::prefix; break;
+            case 'o': arg >> fmmergeopt::outFile; break;
+            case 't': arg >> fmmergeopt::numThreads; break;
+            case '?': die = true; break;
+            case 'v': fmmergeopt::verbose++; break;
+            case O_DEVICE: arg >> fmmergeopt::device; break;
+            case O_BUILDINDEX: fmmergeopt::buildIndex = true; break;
+            case O_LOADONDEVICE: break;
+            case O_HELP: std::cout << FMMERGE_USAGE_MESSAGE; exit(EXIT_SUCCESS);
+            case O_VERSION: std::cout << "fm-merge Version " PACKAGE_VERSION " (MI355X back end)\n"; exit(EXIT_SUCCESS);
+            default: break;                                       // d, e, l, s, i, x: in the reference's option string, read by nothing
+        }
+    }
+    if(argc - optind < 1) { std::cerr << "fm-merge: missing arguments\n"; die = true; }
+    else if(argc - optind > 1) { std::cerr << "fm-merge: too many arguments\n"; die = true; }
+    if(fmmergeopt::numThreads <= 0) { std::cerr << "fm-merge: invalid number of threads: " << fmmergeopt::numThreads << "\n"; die = true; }
+    if(die) { std::cout << "\n" << FMMERGE_USAGE_MESSAGE; exit(EXIT_FAILURE); }
+    fmmergeopt::readsFile = argv[optind++];
+    if(fmmergeopt::prefix.empty()) fmmergeopt::prefix = getFilename(fmmergeopt::readsFile);
+    if(fmmergeopt::outFile.empty()) fmmergeopt::outFile = fmmergeopt::prefix + ".merged.fa";
+}
+
+static int fmmergeMain(int argc, char** argv)
+{
+    parseFMMergeOptions(argc, argv);
+    const int device = fmmergeopt::device;
+    std::string bases;
+    std::vector<uint64_t> off;
+    loadReads(fmmergeopt::readsFile, bases, off);
+    const size_t numReads = off.size() - 1;
+    lrsc_index* idx = nullptr;
+    if(fmmergeopt::buildIndex) {
+        lrscOrDie(lrsc_index_build(bases.data(), off.data(), (uint32_t)numReads, device, &idx), "lrsc_index_build");
+    } else {
+        std::cout << std::endl << "Loading BWT: " << fmmergeopt::prefix + BWT_EXT << "\n";
+        std::cout << "Loading RBWT: " << fmmergeopt::prefix + RBWT_EXT << "\n";
+        lrscOrDie(lrsc_index_open_device((fmmergeopt::prefix + BWT_EXT).c_str(), (fmmergeopt::prefix + RBWT_EXT).c_str(), device, &idx), "lrsc_index_open_device");
+    }
+    lrsc_index_info info;
+    lrscOrDie(lrsc_index_info_get(idx, &info), "lrsc_index_info_get");
+    if(info.num_strings != numReads) {
+        std::cerr << "fm-merge: " << fmmergeopt::readsFile << " holds " << numReads << " reads, the index " << info.num_strings << ": the index is not that of these reads\n";
+        lrsc_index_close(idx);
+        return EXIT_FAILURE;
+    }
+    lrsc_ctx* ctx = nullptr;
+    lrscOrDie(lrsc_ctx_create(idx, nullptr, device, &ctx), "lrsc_ctx_create");
+    printf("[%s::fm-merge] starting read merging on device %d\n", PACKAGE_NAME, device);
+    bool ok = true;
+    {
+        stride::FMMergeProcess processor(ctx, (int)fmmergeopt::minOverlap);
+        stride::FMMergeResult result;
+        ok = processor.process(bases, off, result);
+        if(ok) {
+            std::ofstream writer(fmmergeopt::outFile.c_str());
+            if(!writer) { std::cerr << "Error: could not open " << fmmergeopt::outFile << " for write\n"; ok = false; }
+            else {
+                stride::FMMergePostProcess post(&writer);
+                ok = post.process(result);
+                writer.flush();
+                ok = ok && (bool)writer;
+            }
+        }
+    }
+    fflush(stdout);
+    lrsc_ctx_destroy(ctx);
+    lrsc_index_close(idx);
+    if(!ok) {
+        std::cerr << "fm-merge: the run ended early: " << fmmergeopt::outFile << " is not complete\n";
+        return EXIT_FAILURE;
+    }
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
     // several workers on one device (--devices 0,0) only overlap if their streams get hardware queues of their own (default: 4)
     setenv("GPU_MAX_HW_QUEUES", "16", 0);
-    if(argc <= 1) { std::cerr << "Usage: " PACKAGE_NAME " <command> [options]\nCommands: index, merge, sai, grep, filter, correct, pbcorrect, kmerfreq, kmercheck\n          and fmwalk\n          and overlap\n"; return EXIT_FAILURE; }
+    if(argc <= 1) { std::cerr << "Usage: " PACKAGE_NAME " <command> [options]\nCommands: index, merge, sai, grep, filter, correct, pbcorrect, kmerfreq, kmercheck\n          and fmwalk\n          and overlap\n          and fm-merge\n"; return EXIT_FAILURE; }
     const std::string command(argv[1]);
-    if(command == "help" || command == "--help") { std::cout << "Usage: " PACKAGE_NAME " <command> [options]\nCommands: index, merge, sai, grep, filter, correct, pbcorrect, kmerfreq, kmercheck\n          and fmwalk\n          and overlap\n"; return 0; }
+    if(command == "help" || command == "--help") { std::cout << "Usage: " PACKAGE_NAME " <command> [options]\nCommands: index, merge, sai, grep, filter, correct, pbcorrect, kmerfreq, kmercheck\n          and fmwalk\n          and overlap\n          and fm-merge\n"; return 0; }
     if(command == "pbcorrect" || command == SUBPROGRAM) return PacBioSelfCorrectionMain(argc - 1, argv + 1);
     if(command == "index") return indexMain(argc - 1, argv + 1);
     if(command == "merge") return mergeMain(argc - 1, argv + 1);
@@ -1367,6 +1485,7 @@ int main(int argc, char** argv)
     if(command == "correct") return correctMain(argc - 1, argv + 1);
     if(command == "fmwalk") return fmwalkMain(argc - 1, argv + 1);
     if(command == "overlap") return overlapMain(argc - 1, argv + 1);
+    if(command == "fm-merge") return fmmergeMain(argc - 1, argv + 1);
     if(command == "kmerfreq") return kmerfreqMain(argc - 1, argv + 1);
     if(command == "kmercheck") return kmercheckMain(argc - 1, argv + 1);
     std::cerr << "Unrecognized command: " << command << "\n";
