@@ -337,6 +337,47 @@ int lrsc_fmwalk_hybrid(lrsc_ctx* ctx, const char* reads, const uint64_t* read_of
                        uint64_t repeat_kmer_freq, char* merged /* n_pairs * stride */, uint64_t stride, lrsc_fmwalk_hybrid_result* out,
                        lrsc_fmwalk_piece* pieces, uint64_t n_piece_slots);
 
+/* ---- fmwalk's validate algorithm: single reads validated by walks inside them (FMIndexWalk/FMIndexWalkProcess.cpp:269-391
+ * ValidateReads, 613-722 splitRead(std::string&), 418-445 and 855-881 isLowComplexity, numNextKmer, isSimple; FMIndexWalk/
+ * SAIntervalTree.cpp:59-94 the single-read constructor, 173-237 validate(), 248-350 and 397-507 what they call) ------------------- */
+/* What validate leaves of one read: merged (FMIndexWalkResult::merge) and, when it is set, the sequence's length; per walk status,
+ * max_used_leaves and coverage as lrsc_fmwalk_result's and walk_length, the length of the walk's string (0: none); chosen = the
+ * walk whose string is the sequence, or -1 when the sequence is the read itself or the read is not merged; read = kmerize, the
+ * pieces and the main one as lrsc_fmwalk_kmerize leaves them (head 0, length the read's), whole = correctSequence is the read. */
+typedef struct lrsc_fmwalk_validate_result { uint32_t merged, length; int32_t status[2]; uint32_t max_used_leaves[2]; uint64_t coverage[2]; uint32_t walk_length[2]; int32_t chosen /* 0, 1: that walk's string; -1: the read itself or none */; lrsc_fmwalk_read_result read; } lrsc_fmwalk_validate_result;
+/* FMIndexWalkProcess::ValidateReads for n_reads single reads against the ctx's index, byte for byte the reference's serial run.
+ * n = a read's length, m = min_overlap, k = kmer_length, T = kmer_threshold, which is the reference's `threshold`
+ * (getRequiredSupport(0) - 1, the value of -x) as in lrsc_fmwalk_merge; max_insert is ignored.
+ * 1. n <= m: no walk.  correctSequence is the read (whole = 1) and kmerize = !isLowComplexity(read), the float quotient against
+ *    the double 0.9 (418-445).
+ * 2. Otherwise two walks (SAIntervalTree::validate: mergeTwoReads without isTwoReadsOverlap, so the terminal is looked for only
+ *    after the first extension and a read whose first and last m-mers are equal is still walked): walk 0 on the read, walk 1 on its
+ *    reverse complement, each from the string's first m bases to its last m.  Depth limit (size_t)(n * 1.1), max overlap max_overlap
+ *    or, for -1, (size_t)(n * 0.9), both in double arithmetic; max_leaves leaves; an extension needs T occurrences on both strands
+ *    together.  Of a walk's results the one with the strictly greatest calculateKmerCoverage(.., m, pBWT) is its string; status 1,
+ *    -1, -2, -3, -4 as lrsc_fmwalk_merge's.
+ * 3. The decision (318-352), diffN = (double)lenN / n: only walk 0 has a string and walk 1's status is not -2: merged, the sequence
+ *    is walk 0's string if diff0 >= 1, else the read; the same with the walks exchanged; both have a string: merged, walk 0's if
+ *    diff0 >= 1, else walk 1's if diff1 >= 1, else the read.  Walk 1's string reads on the reverse strand and is given as it is.
+ * 4. Everything else, "one string, but the other walk ran out of depth" included, is split: splitRead(std::string&) with the
+ *    threshold (size_t)T - 1, unsigned (T = 1: 0, every k-mer qualifies; a T of 0, which this entry refuses, would wrap so that none
+ *    does).  A k-mer qualifies by the sum of its occurrences and its reverse complement's (the reference's growing interval with its
+ *    restarts gives that sum); a boundary p is examined unless k-mers p - 1 and p both qualify, and splits when
+ *    !isSimple(k-mer p - 1, k-mer p, 1).  The main piece is the first piece with the strictly greatest span last - first, a span of
+ *    0 never, and needs no solid k-mer.  kmerize is set when there is any piece; pieces of low complexity are dropped (kept = 0),
+ *    the main one too, and correctSequence is then empty.  correctSequence is the main piece when it is kept, kmerizedReads are
+ *    the other kept pieces in order.  Pieces and slots as lrsc_fmwalk_kmerize's.
+ * 5. m < n < k: the reference asserts.  Here the walks run; a read they do not merge gives merged = 0, kmerize = 0, an empty
+ *    sequence and no pieces.
+ * merged + i * stride holds read i's sequence when it is merged and is not written otherwise.  LRSC_ERR_ARG as lrsc_fmwalk_merge
+ * (max_insert apart), for fewer piece slots than the reads' k-mers and for a stride below (size_t)(1.1 * the longest read) + 1;
+ * LRSC_ERR_UNSUPPORTED above the limits of lrsc_fmwalk_merge and when the longest string a read's walk can leave, (size_t)(n * 1.1)
+ * + 1 bases, exceeds LRSC_FMWALK_MAX_INSERT (reads of up to 1818 bases are taken); LRSC_ERR_FORMAT when an interval leaves the
+ * strand; on an error merged, out and pieces are untouched.  n_reads == 0 does nothing.  The launches are counted under
+ * LRSC_K_FIND: one for the walks when a read is longer than m, one more when a read is split. */
+int lrsc_fmwalk_validate(lrsc_ctx* ctx, const char* reads, const uint64_t* read_off, uint32_t n_reads, const lrsc_fmwalk_params* p /* max_insert ignored */,
+                         char* merged /* n_reads * stride */, uint64_t stride, lrsc_fmwalk_validate_result* out, lrsc_fmwalk_piece* pieces, uint64_t n_piece_slots);
+
 /* ---- exact irreducible read overlaps: `stride overlap` in its default mode (StriDe/overlap.cpp:126-413 without -e; Concurrency/
  * OverlapProcess.cpp:32-109; Algorithm/OverlapAlgorithm.cpp:22-44, 270-389, 419-487, 1043-1193, 1423-1444; Algorithm/OverlapBlock.cpp:
  * 40-70, 128-160, 182-360; BWTAlgorithms::initIntervalPair / updateBothL / updateBothR / getExtCount) ---- */

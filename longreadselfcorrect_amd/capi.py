@@ -202,6 +202,8 @@ FMWALK_DTYPE = np.dtype([("merged", "<u4"), ("length", "<u4"), ("status", "<i4",
 FMWALK_PIECE_DTYPE = np.dtype([("start", "<u4"), ("length", "<u4"), ("kept", "<u4")])      # lrsc_fmwalk_piece
 FMWALK_READ_DTYPE = np.dtype([("kmerize", "<u4"), ("head", "<i4"), ("length", "<u4"), ("n_pieces", "<u4"), ("main_piece", "<i4"), ("whole", "<u4")])      # lrsc_fmwalk_read_result
 FMWALK_HYBRID_DTYPE = np.dtype([("walk", FMWALK_DTYPE), ("read", FMWALK_READ_DTYPE, (2,))], align=True)      # lrsc_fmwalk_hybrid_result
+FMWALK_VALIDATE_DTYPE = np.dtype([("merged", "<u4"), ("length", "<u4"), ("status", "<i4", (2,)), ("max_used_leaves", "<u4", (2,)), ("coverage", "<u8", (2,)),
+                                  ("walk_length", "<u4", (2,)), ("chosen", "<i4"), ("read", FMWALK_READ_DTYPE)], align=True)      # lrsc_fmwalk_validate_result
 OVERLAP_READ_DTYPE = np.dtype([("is_substring", "<u4"), ("n_blocks", "<u4"), ("status", "<u4"), ("pad", "<u4"), ("first_block", "<u8")])      # lrsc_overlap_read
 OVERLAP_BLOCK_DTYPE = np.dtype([("lower", "<i8"), ("upper", "<i8"), ("overlap_len", "<u4"), ("target_rev", "u1"), ("query_rev", "u1"), ("query_comp", "u1"),
                                 ("contained", "u1")])                 # lrsc_overlap_block
@@ -275,6 +277,7 @@ class Lrsc:
         L.lrsc_fmwalk_merge.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
         L.lrsc_kmer_sample_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
         L.lrsc_fmwalk_kmerize.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64]
+        L.lrsc_fmwalk_validate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64]
         L.lrsc_fmwalk_hybrid.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                          C.c_uint64]
         L.lrsc_overlap_exact.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
@@ -616,6 +619,25 @@ class Ctx:
         pieces = np.zeros(max(int(slots[-1]), 1), dtype=FMWALK_PIECE_DTYPE)
         self.api.check(self.api.lib.lrsc_fmwalk_hybrid(self.h, _ptr(bases), _ptr(off), n_pairs, _ptr(params), repeat_kmer_freq, _ptr(merged), stride, _ptr(out),
                                                        _ptr(pieces), int(slots[-1])), "lrsc_fmwalk_hybrid")
+        return merged, out, pieces, slots
+
+    def fmwalk_validate(self, bases: np.ndarray, off: np.ndarray, kmer_length: int = 31, kmer_threshold: int = 3, min_overlap: int = 81, max_overlap: int = -1,
+                        max_leaves: int = 32, stride: int | None = None):
+        """lrsc_fmwalk_validate of the reads (ASCII bases, n + 1 offsets) -> (the sequences of the merged reads, one row of
+        `stride` bytes per read, zero where nothing was written; FMWALK_VALIDATE_DTYPE per read; FMWALK_PIECE_DTYPE of all slots;
+        the reads' first slots)."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        off = np.ascontiguousarray(off, dtype=np.uint64)
+        n = off.size - 1
+        if stride is None:
+            stride = int(int(np.diff(off.astype(np.int64)).max(initial=0)) * 1.1) + 1
+        params = np.array([kmer_length, kmer_threshold, min_overlap, max_overlap, 0, max_leaves], dtype=np.int32)
+        slots = piece_slots(off, kmer_length)
+        merged = np.zeros((n, stride), dtype=np.uint8)
+        out = np.zeros(n, dtype=FMWALK_VALIDATE_DTYPE)
+        pieces = np.zeros(max(int(slots[-1]), 1), dtype=FMWALK_PIECE_DTYPE)
+        self.api.check(self.api.lib.lrsc_fmwalk_validate(self.h, _ptr(bases), _ptr(off), n, _ptr(params), _ptr(merged), stride, _ptr(out), _ptr(pieces), int(slots[-1])),
+                       "lrsc_fmwalk_validate")
         return merged, out, pieces, slots
 
     def overlap_exact(self, bases: np.ndarray, off: np.ndarray, min_overlap: int = 45, block_cap: int | None = None):

@@ -1,8 +1,10 @@
 // capi_fmwalk.cpp -- what `stride fmwalk` needs of the library: the merge of a batch of paired-end reads by walking a context's
-// index (fm_fmwalk.hip), and the hybrid and kmerize algorithms with the sampled k-mer counts (fm_kmerize.hip).
+// index (fm_fmwalk.hip), the hybrid and kmerize algorithms with the sampled k-mer counts (fm_kmerize.hip), and the validate
+// algorithm (fm_validate.hip).
 #include "capi_internal.h"
 #include "fm_fmwalk.h"
 #include "fm_kmerize.h"
+#include "fm_validate.h"
 
 using namespace lrsc;
 
@@ -98,9 +100,10 @@ static std::vector<uint64_t> piece_slots(const uint64_t* read_off, uint32_t n_re
     return slot;
 }
 
-// The splits of `jobs` over the staged reads: pieces[0 .. n_slots) (only the jobs' own are meaningful) and outs[job].
-static int run_splits(lrsc_ctx* ctx, const std::vector<KmJob>& jobs, uint32_t k, uint32_t threshold, bool filters, uint64_t n_slots, std::vector<KmPiece>& pieces,
-                      std::vector<KmJobOut>& outs)
+// The splits of `jobs` over the staged reads: pieces[0 .. n_slots) (only the jobs' own are meaningful) and outs[job].  validate:
+// splitRead(std::string&)'s rules (fm_validate.hip), which have no `filters`.
+static int run_splits(lrsc_ctx* ctx, const std::vector<KmJob>& jobs, uint32_t k, uint64_t threshold, bool filters, bool validate, uint64_t n_slots,
+                      std::vector<KmPiece>& pieces, std::vector<KmJobOut>& outs)
 {
     outs.assign(jobs.size(), KmJobOut{0u, -1});
     pieces.assign(n_slots, KmPiece{0u, 0u, 0u});
@@ -119,9 +122,14 @@ static int run_splits(lrsc_ctx* ctx, const std::vector<KmJob>& jobs, uint32_t k,
     HIP_TRY(hipMemcpyAsync(ctx->km_jobs.p, jobs.data(), jobs.size() * sizeof(KmJob), hipMemcpyHostToDevice, ctx->stream));
     uint32_t* d_broken = reinterpret_cast<uint32_t*>(ctx->s_flag.p);
     const int st = timed_launch(ctx, LRSC_K_FIND, [&]() {
-        return launch_kmerize_split(ctx->fm, ctx->s_codes.p, ctx->s_off.p, reinterpret_cast<const KmJob*>(ctx->km_jobs.p), (uint32_t)jobs.size(), k, threshold, filters,
-                                    (uint32_t)groups, ctx->km_ws.p, slice, longest, reinterpret_cast<KmPiece*>(ctx->km_pieces.p),
-                                    reinterpret_cast<KmJobOut*>(ctx->km_outs.p), d_broken, ctx->d_ctr, ctx->stream);
+        const KmJob* d_jobs = reinterpret_cast<const KmJob*>(ctx->km_jobs.p);
+        KmPiece* d_pieces = reinterpret_cast<KmPiece*>(ctx->km_pieces.p);
+        KmJobOut* d_outs = reinterpret_cast<KmJobOut*>(ctx->km_outs.p);
+        if(validate)
+            return launch_validate_split(ctx->fm, ctx->s_codes.p, ctx->s_off.p, d_jobs, (uint32_t)jobs.size(), k, threshold, (uint32_t)groups, ctx->km_ws.p, slice, longest,
+                                         d_pieces, d_outs, d_broken, ctx->d_ctr, ctx->stream);
+        return launch_kmerize_split(ctx->fm, ctx->s_codes.p, ctx->s_off.p, d_jobs, (uint32_t)jobs.size(), k, (uint32_t)threshold, filters, (uint32_t)groups, ctx->km_ws.p,
+                                    slice, longest, d_pieces, d_outs, d_broken, ctx->d_ctr, ctx->stream);
     });
     if(st != LRSC_OK) return st;
     int broken = 0;
@@ -199,7 +207,7 @@ extern "C" int lrsc_fmwalk_kmerize(lrsc_ctx* ctx, const char* reads, const uint6
     }
     std::vector<KmPiece> got;
     std::vector<KmJobOut> outs;
-    st = run_splits(ctx, jobs, k, (uint32_t)kmer_threshold, false, slot[n_reads], got, outs);
+    st = run_splits(ctx, jobs, k, (uint32_t)kmer_threshold, false, false, slot[n_reads], got, outs);
     if(st != LRSC_OK) return st;
     std::vector<KmRead> res(n_reads, KmRead{0u, 0, 0u, 0u, -1, 0u});
     for(size_t j = 0; j < jobs.size(); ++j) {
@@ -308,7 +316,7 @@ extern "C" int lrsc_fmwalk_hybrid(lrsc_ctx* ctx, const char* reads, const uint64
     }
     std::vector<KmPiece> got;
     std::vector<KmJobOut> jouts;
-    st = run_splits(ctx, jobs, k, (uint32_t)p->kmer_threshold, true, slot[n_reads], got, jouts);
+    st = run_splits(ctx, jobs, k, (uint32_t)p->kmer_threshold, true, false, slot[n_reads], got, jouts);
     if(st != LRSC_OK) return st;
     for(size_t j = 0; j < jobs.size(); ++j) place_pieces(jobs[j], jouts[j], got, res[jobs[j].read >> 1].read[jobs[j].read & 1u], pieces);
     for(uint32_t i = 0; i < n_pairs; ++i) {
@@ -318,5 +326,105 @@ extern "C" int lrsc_fmwalk_hybrid(lrsc_ctx* ctx, const char* reads, const uint64
     }
     static_assert(sizeof(KmHybrid) == sizeof(lrsc_fmwalk_hybrid_result), "KmHybrid is lrsc_fmwalk_hybrid_result");
     std::memcpy(out, res.data(), (uint64_t)n_pairs * sizeof(KmHybrid));
+    return LRSC_OK;
+}
+
+// FMIndexWalkProcess::ValidateReads (FMIndexWalk/FMIndexWalkProcess.cpp:269-391) with SAIntervalTree's single-read constructor and
+// validate() (FMIndexWalk/SAIntervalTree.cpp:59-94, 173-237), splitRead(std::string&) (613-722) and isLowComplexity (418-445)
+extern "C" int lrsc_fmwalk_validate(lrsc_ctx* ctx, const char* reads, const uint64_t* read_off, uint32_t n_reads, const lrsc_fmwalk_params* p, char* merged,
+                                    uint64_t stride, lrsc_fmwalk_validate_result* out, lrsc_fmwalk_piece* pieces, uint64_t n_piece_slots)
+{
+    if(!ctx || !p || (n_reads && (!reads || !read_off || !merged || !out || !pieces))) return fail(LRSC_ERR_ARG, "null");
+    if(p->kmer_length <= 0) return fail(LRSC_ERR_ARG, "fmwalk: invalid kmer length: " + std::to_string(p->kmer_length));
+    if(p->kmer_threshold <= 0) return fail(LRSC_ERR_ARG, "fmwalk: invalid kmer threshold: " + std::to_string(p->kmer_threshold));
+    if(p->min_overlap < 2) return fail(LRSC_ERR_ARG, "fmwalk: invalid min overlap: " + std::to_string(p->min_overlap));
+    if(p->max_overlap <= 0 && p->max_overlap != -1) return fail(LRSC_ERR_ARG, "fmwalk: invalid max overlap: " + std::to_string(p->max_overlap));
+    if(p->max_leaves <= 0) return fail(LRSC_ERR_ARG, "fmwalk: invalid max leaves: " + std::to_string(p->max_leaves));
+    if((uint32_t)p->max_leaves > kFwMaxLeaves || (uint32_t)p->min_overlap > kFwMaxOverlap || (uint32_t)p->kmer_length > kFwMaxKmer)
+        return fail(LRSC_ERR_UNSUPPORTED, "fmwalk: above the kernel's limits (max leaves 64, min overlap 255, kmer length 255)");
+    if(n_reads == 0) return LRSC_OK;
+    if(n_reads >= (1u << 30)) return fail(LRSC_ERR_UNSUPPORTED, "fmwalk: 2^30 reads or more in one call");
+    int st = check_offsets(read_off, n_reads);
+    if(st != LRSC_OK) return st;
+    const uint32_t k = (uint32_t)p->kmer_length, m = (uint32_t)p->min_overlap;
+    uint64_t longest = 0;
+    bool any_walk = false;
+    for(uint32_t i = 0; i < n_reads; ++i) {
+        const uint64_t len = read_off[i + 1] - read_off[i];
+        // the longest string a walk of the read can leave is one base beyond its depth limit
+        if(len >> 31 || vd_depth((uint32_t)len) + 1 > kFwMaxInsert)
+            return fail(LRSC_ERR_UNSUPPORTED, "fmwalk: read " + std::to_string(i) + " has " + std::to_string(len) + " bases: a walk of it could leave more than " +
+                                                  std::to_string(kFwMaxInsert));
+        longest = std::max(longest, len);
+        any_walk = any_walk || len > m;
+    }
+    const uint32_t depth = vd_depth((uint32_t)longest);
+    if(stride < (uint64_t)depth + 1) return fail(LRSC_ERR_ARG, "fmwalk: the stride of merged is below 1.1 * the longest read + 1");
+    const std::vector<uint64_t> slot = piece_slots(read_off, n_reads, k);
+    if(n_piece_slots < slot[n_reads]) return fail(LRSC_ERR_ARG, "fmwalk: fewer piece slots than the reads' k-mers");
+    st = stage_reads(ctx, "fmwalk", 31, reads, read_off, n_reads, 0);
+    if(st != LRSC_OK) return st;
+    const uint32_t n_walks = 2 * n_reads;
+    const uint64_t row = (uint64_t)depth + 1;                     // of a walk's string on the device
+    std::vector<uint8_t> codes;
+    std::vector<FwWalkOut> outs(n_walks, FwWalkOut{0, 0u, 0u, 0u, 0ull});
+    if(any_walk) {
+        const FwParams fp{p->kmer_length, p->kmer_threshold, p->min_overlap, p->max_overlap, (int32_t)std::max(depth, 1u), p->max_leaves};
+        const uint64_t slice = fw_workspace_bytes(fp);
+        const uint32_t waves_per_group = kVdThreads / kVdLanes;
+        uint64_t groups = std::min<uint64_t>(((uint64_t)n_walks + waves_per_group - 1) / waves_per_group, resident_waves(ctx, kVdWavesPerSimd) / waves_per_group);
+        groups = std::max<uint64_t>(1, std::min<uint64_t>(groups, kFwWorkspaceBytes / (slice * waves_per_group)));
+        HIP_TRY(ctx->fw_ws.reserve(groups * waves_per_group * slice));
+        HIP_TRY(ctx->fw_best.reserve((uint64_t)n_walks * row));
+        HIP_TRY(ctx->fw_outs.reserve((uint64_t)n_walks * sizeof(FwWalkOut)));
+        uint32_t* d_broken = reinterpret_cast<uint32_t*>(ctx->s_flag.p);
+        FwWalkOut* d_outs = reinterpret_cast<FwWalkOut*>(ctx->fw_outs.p);
+        st = timed_launch(ctx, LRSC_K_FIND, [&]() {
+            return launch_validate_walks(ctx->fm, ctx->s_codes.p, ctx->s_off.p, n_reads, fp, (uint32_t)groups, ctx->fw_ws.p, slice, ctx->fw_best.p, row, d_outs, d_broken,
+                                         ctx->d_ctr, ctx->stream);
+        });
+        if(st != LRSC_OK) return st;
+        int broken = 0;
+        COPY_TRY(ctx, &broken, ctx->s_flag.p, sizeof(int), hipMemcpyDeviceToHost);
+        if(broken) return fail(LRSC_ERR_FORMAT, "fmwalk: an interval leaves the strand (the index is no BWT of a string set)");
+        codes.resize((uint64_t)n_walks * row);
+        HIP_TRY(hipMemcpyAsync(codes.data(), ctx->fw_best.p, codes.size(), hipMemcpyDeviceToHost, ctx->stream));
+        COPY_TRY(ctx, outs.data(), d_outs, (uint64_t)n_walks * sizeof(FwWalkOut), hipMemcpyDeviceToHost);
+    }
+    // the short reads, the decision (FMIndexWalkProcess.cpp:280-294, 318-352), then the splits of the reads that are left
+    std::vector<VdResult> res(n_reads);
+    std::vector<KmJob> jobs;
+    std::vector<uint8_t> own;
+    for(uint32_t i = 0; i < n_reads; ++i) {
+        const uint32_t len = (uint32_t)(read_off[i + 1] - read_off[i]);
+        if(len <= m) {
+            own.resize(len);
+            st = encode_acgt(reads + read_off[i], len, own.data());
+            if(st != LRSC_OK) return st;
+            res[i] = vd_result(len, FwWalkOut{0, 0u, 0u, 0u, 0ull}, FwWalkOut{0, 0u, 0u, 0u, 0ull});
+            res[i].read.whole = 1;
+            res[i].read.kmerize = km_low_complexity(own.data(), len) ? 0u : 1u;
+            continue;
+        }
+        res[i] = vd_result(len, outs[2 * i], outs[2 * i + 1]);
+        if(outs[2 * i].length > row || outs[2 * i + 1].length > row) return fail(LRSC_ERR_FORMAT, "fmwalk: a walk's string longer than its slot");
+        if(!res[i].merged && len >= k) jobs.push_back(KmJob{i, 0u, len, 0u, slot[i]});
+    }
+    std::vector<KmPiece> got;
+    std::vector<KmJobOut> jouts;
+    st = run_splits(ctx, jobs, k, vd_split_threshold(p->kmer_threshold), false, true, slot[n_reads], got, jouts);
+    if(st != LRSC_OK) return st;
+    for(size_t j = 0; j < jobs.size(); ++j) place_pieces(jobs[j], jouts[j], got, res[jobs[j].read].read, pieces);
+    for(uint32_t i = 0; i < n_reads; ++i) {
+        if(!res[i].merged) continue;
+        char* to = merged + (uint64_t)i * stride;
+        if(res[i].chosen < 0) std::memcpy(to, reads + read_off[i], res[i].length);
+        else {
+            const uint8_t* from = codes.data() + (2ull * i + (uint32_t)res[i].chosen) * row;
+            for(uint32_t j = 0; j < res[i].length; ++j) to[j] = "ACGT"[from[j] & 3u];
+        }
+    }
+    static_assert(sizeof(VdResult) == sizeof(lrsc_fmwalk_validate_result), "VdResult is lrsc_fmwalk_validate_result");
+    std::memcpy(out, res.data(), (uint64_t)n_reads * sizeof(VdResult));
     return LRSC_OK;
 }

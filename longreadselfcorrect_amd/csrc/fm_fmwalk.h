@@ -243,8 +243,10 @@ struct FwWalkOut {
 // it nothing else), so the string is never longer than I + 1 and the rest of e that the reference appends is empty.  The merged
 // string goes to ws.best()[0 .. out.length); out.length = 0 is the reference's empty string.  The walk keeps q and e in its
 // workspace and reads the parameters where it uses them: what it holds in registers between its phases is its counters.
+// SHORTCUT = false is SAIntervalTree::validate (SAIntervalTree.cpp:173-237): the same walk without isTwoReadsOverlap, so that the
+// terminal is looked for only after the first extension, also when q == e.
 #define FW_M ((uint32_t)p.min_overlap)
-template <class Block, class W>
+template <class Block, class W, bool SHORTCUT = true>
 LRSC_HD void fw_walk(const StrandView<Block>* views, const uint32_t* mtab, const uint8_t* q_from, const uint8_t* e_from, const FwParams& p,
                      uint32_t max_overlap, const FwWork& ws, W& w, FwWalkOut& out, uint32_t& bad, uint32_t& n_rank, uint32_t& n_blk)
 {
@@ -269,8 +271,8 @@ LRSC_HD void fw_walk(const StrandView<Block>* views, const uint32_t* mtab, const
     });
     // ---- isTwoReadsOverlap.  Case 1 compares the intervals as they are, valid or not.  Cases 2 and 3 look for the first m bases
     // of one string in the other: with m bases each the only place is 0 and the overlap is the whole string, so both say q == e.
-    bool overlap = w.uniform64(ws.probe()[0].lo) == w.uniform64(ws.probe()[2].lo) && w.uniform64(ws.probe()[0].hi1) == w.uniform64(ws.probe()[2].hi1);
-    if(!overlap) overlap = w.min_over([&](uint32_t lane) -> uint32_t {
+    bool overlap = SHORTCUT && w.uniform64(ws.probe()[0].lo) == w.uniform64(ws.probe()[2].lo) && w.uniform64(ws.probe()[0].hi1) == w.uniform64(ws.probe()[2].hi1);
+    if(SHORTCUT && !overlap) overlap = w.min_over([&](uint32_t lane) -> uint32_t {
         uint32_t r = kFwNone;
         for(uint32_t i = lane; i < FW_M; i += kFwLanes) r = ws.q()[i] != ws.e()[i] ? 0u : r;
         return r;

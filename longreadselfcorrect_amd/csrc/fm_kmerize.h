@@ -126,8 +126,14 @@ LRSC_HD uint64_t km_max_con(const uint8_t* s, uint32_t len)
 
 // splitRead(KmerContext(read[0 .. n), k)), n >= k, with MergeAndKmerize's filters when `filters`: pieces[0 .. n_pieces) in read
 // order (start within read[], length, kept), main_piece = mainSeedIdx.  att: kKmLanes words.
-template <class Block, class W>
-LRSC_HD void km_split(const StrandView<Block>& bwt, const uint32_t* mtab, const uint8_t* read, uint32_t n, uint32_t k, uint32_t threshold, bool filters,
+//
+// VALIDATE is splitRead(std::string&) (613-722), ValidateReads' split, which differs in three places.  A k-mer qualifies by the sum
+// of its two counts: both of its bytes in solid() then say so, and the boundaries to probe are found as above.  The reference takes
+// that sum from an interval that grows along the read and restarts at k bases when it falls below the threshold; a string occurs no
+// more often than its last k bases, so this is the k-mer's own sum at every position.  A threshold of 2^32 or more is never met
+// (ValidateReads' `threshold - 1` of 0 is one).  The only filter is isLowComplexity, and the main piece needs no solid k-mer.
+template <class Block, class W, bool VALIDATE = false>
+LRSC_HD void km_split(const StrandView<Block>& bwt, const uint32_t* mtab, const uint8_t* read, uint32_t n, uint32_t k, uint64_t threshold, bool filters,
                       const KmWork& ws, uint32_t* att, W& w, KmPiece* pieces, uint32_t& n_pieces, int32_t& main_piece, uint32_t& bad, uint32_t& n_rank, uint32_t& n_blk)
 {
     const uint32_t nk = n - k + 1;
@@ -138,9 +144,15 @@ LRSC_HD void km_split(const StrandView<Block>& bwt, const uint32_t* mtab, const 
     for(uint32_t p0 = 0; p0 < nk; p0 += kKmLanes / 2) {
         w.each([&](uint32_t lane) {
             const uint32_t p = p0 + (lane >> 1);
+            if(VALIDATE) att[lane] = 0;
             if(p >= nk) return;
             const uint64_t c = fw_count<Block>(bwt, mtab, k, (lane & 1u) != 0, [&](uint32_t i) -> uint32_t { return (uint32_t)read[p + i]; }, bad, n_rank, n_blk);
-            ws.solid()[2ull * p + (lane & 1u)] = c >= threshold ? 1 : 0;
+            if(VALIDATE) att[lane] = c > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)c;      // the sum still says whether a threshold below 2^32 is met
+            else ws.solid()[2ull * p + (lane & 1u)] = c >= threshold ? 1 : 0;
+        });
+        if(VALIDATE) w.each([&](uint32_t lane) {
+            const uint32_t p = p0 + (lane >> 1);
+            if(p < nk) ws.solid()[2ull * p + (lane & 1u)] = threshold <= 0xFFFFFFFFull && (uint64_t)att[lane] + att[lane ^ 1u] >= threshold ? 1 : 0;
         });
     }
     if(fw_any_bad(w, bad)) return;
@@ -195,10 +207,11 @@ LRSC_HD void km_split(const StrandView<Block>& bwt, const uint32_t* mtab, const 
             const uint32_t i = i0 + lane;
             if(i >= np) return;
             const uint32_t first = pieces[i].start, last = i + 1 < np ? pieces[i + 1].start - 1 : nk - 1, len = last - first + k;
-            bool strong = false;
-            for(uint32_t p = first; p <= last; ++p) strong = strong || ws.solid()[2ull * p] + ws.solid()[2ull * p + 1] == 2;
+            bool strong = VALIDATE;
+            for(uint32_t p = first; !VALIDATE && p <= last; ++p) strong = strong || ws.solid()[2ull * p] + ws.solid()[2ull * p + 1] == 2;
             uint32_t kept = 1;
-            if(filters && (km_low_complexity(read + first, len) || km_max_con(read + first, len) * 3 > (uint64_t)len)) kept = 0;
+            if(VALIDATE ? km_low_complexity(read + first, len) : filters && (km_low_complexity(read + first, len) || km_max_con(read + first, len) * 3 > (uint64_t)len))
+                kept = 0;
             pieces[i].length = len;
             pieces[i].kept = kept;
             ws.list()[i] = strong ? last - first : 0u;

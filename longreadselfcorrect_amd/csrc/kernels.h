@@ -155,6 +155,18 @@ hipError_t launch_hybrid_walks(const FmIndexDev& fm, const uint64_t* read_off, u
                                hipStream_t stream);
 hipError_t launch_kmer_sample(const FmIndexDev& fm, const uint64_t* rows, uint32_t n, uint32_t len, uint8_t* ws, uint32_t* counts, uint32_t* broken, DevCounters* ctr,
                               hipStream_t stream);
+// The validate algorithm of fmwalk (fm_validate.hip), codes / read_off as above, single reads.
+// launch_validate_walks, a wavefront per walk, walk 2i + w being read i's walk w (0: on the read, 1: on its reverse complement):
+// `groups` workgroups of kVdThreads, every wavefront with its own ws_slice >= fw_workspace_bytes(p) bytes of ws, p.max_insert being
+// vd_depth of the longest read and stride at least that + 1; outs[walk] and best + walk * stride as launch_fmwalk_walks leaves them,
+// zeros for a read of min_overlap bases or fewer.
+// launch_validate_split: launch_kmerize_split with splitRead(std::string&)'s rules and its 64-bit threshold.
+// *broken is set to 1 when an interval leaves the strand.
+hipError_t launch_validate_walks(const FmIndexDev& fm, const uint8_t* codes, const uint64_t* read_off, uint32_t n_reads, const FwParams& p, uint32_t groups, uint8_t* ws,
+                                 uint64_t ws_slice, uint8_t* best, uint64_t stride, FwWalkOut* outs, uint32_t* broken, DevCounters* ctr, hipStream_t stream);
+hipError_t launch_validate_split(const FmIndexDev& fm, const uint8_t* codes, const uint64_t* read_off, const KmJob* jobs, uint32_t n_jobs, uint32_t k, uint64_t threshold,
+                                 uint32_t groups, uint8_t* ws, uint64_t ws_slice, uint32_t longest, KmPiece* pieces, KmJobOut* outs, uint32_t* broken, DevCounters* ctr,
+                                 hipStream_t stream);
 // The exact irreducible overlaps of n_reads reads (fm_overlap.hip), codes / read_off as above, no read longer than p.max_len.
 // launch_overlap_collect, a lane per chain and four chains per read: heads[4 r + c] and chain_blocks + (4 r + c) * ov_slots(p) =
 // what chain c of read r found.  launch_overlap_reduce, a wavefront per read: `groups` workgroups of kOvThreads, every wavefront

@@ -1,5 +1,5 @@
 // FMIndexWalkProcess.cpp -- see FMIndexWalkProcess.h (reference behaviour: FMIndexWalk/FMIndexWalkProcess.cpp:29-150, 153-226,
-// 229-267, 898-1020, Util/Util.h:51-98).
+// 229-267, 269-391, 898-1020, Util/Util.h:51-98).
 #include "FMIndexWalkProcess.h"
 
 #include <algorithm>
@@ -130,6 +130,43 @@ std::vector<FMIndexWalkResult> FMIndexWalkProcess::process_batch(const std::vect
     }
     if(sent.empty()) return results;
     const std::vector<uint64_t> slot = pieceSlots(off, m_params.kmerLength);
+    if(m_params.algorithm == FMW_VALIDATE) {
+        size_t longest = 0;
+        for(size_t q = 0; q < sent.size(); ++q) {
+            const SeqRecord& r = reads[sent[q]].read;
+            // a walk's string is at most one base longer than its depth limit, (size_t)(length * 1.1)
+            if((size_t)((double)r.seq.size() * 1.1) + 1 > LRSC_FMWALK_MAX_INSERT) {
+                std::cerr << "FMIndexWalk: read " << r.id << " has " << r.seq.size() << " bases: --validate takes reads whose walks leave at most "
+                          << LRSC_FMWALK_MAX_INSERT << "\n";
+                exit(EXIT_FAILURE);
+            }
+            longest = std::max(longest, r.seq.size());
+        }
+        lrsc_fmwalk_params p;
+        p.kmer_length = m_params.kmerLength;
+        p.kmer_threshold = m_params.kmerThreshold;
+        p.min_overlap = m_params.minOverlap;
+        p.max_overlap = m_params.maxOverlap;
+        p.max_insert = 0;                                         // not used: the depth limit is the read's
+        p.max_leaves = m_params.maxLeaves;
+        const uint64_t stride = (uint64_t)((double)longest * 1.1) + 1;
+        std::string merged(sent.size() * stride, '\0');
+        std::vector<lrsc_fmwalk_validate_result> res(sent.size());
+        std::vector<lrsc_fmwalk_piece> pieces(std::max<uint64_t>(slot.back(), 1));
+        orDie(lrsc_fmwalk_validate(m_params.ctx, bases.data(), off.data(), (uint32_t)sent.size(), &p, &merged[0], stride, res.data(), pieces.data(), slot.back()),
+              "lrsc_fmwalk_validate");
+        for(size_t q = 0; q < sent.size(); ++q) {
+            FMIndexWalkResult& out = results[sent[q]];
+            out.kmerize = res[q].read.kmerize != 0;
+            if(res[q].merged) {
+                out.merge = true;
+                out.correctSequence = merged.substr(q * stride, res[q].length);
+                continue;
+            }
+            takePieces(reads[sent[q]].read.seq, res[q].read, pieces.data() + slot[q], out.correctSequence, out.kmerizedReads);
+        }
+        return results;
+    }
     std::vector<lrsc_fmwalk_read_result> res(sent.size());
     std::vector<lrsc_fmwalk_piece> pieces(std::max<uint64_t>(slot.back(), 1));
     orDie(lrsc_fmwalk_kmerize(m_params.ctx, bases.data(), off.data(), (uint32_t)sent.size(), m_params.kmerLength, m_params.kmerThreshold, res.data(), pieces.data(),
@@ -164,14 +201,18 @@ static void writeKmerized(std::ostream& out, const SeqRecord& record, const std:
     for(size_t i = 0; i < kmerized.size(); ++i) out << ">" << record.id << ":" << i << "\n" << kmerized[i] << "\n";
 }
 
-// FMIndexWalkProcess.cpp:922-969 for the kmerize algorithm.  A read that is not kmerized is counted and not written: the
-// reference writes it to a writer that only the validate algorithm opens.
+// FMIndexWalkProcess.cpp:922-969 for the kmerize and validate algorithms.  In kmerize mode a read that is not kmerized is counted
+// and not written: the reference writes it to a writer that only the validate algorithm opens.  In validate mode a merged read goes
+// to the corrected writer as FASTA (SeqItem::write), a kmerized one to the discard writer, any other, with its correctSequence,
+// to LowComplexityReads.fa.
 void FMIndexWalkPostProcess::process(const SequenceWorkItem& item, const FMIndexWalkResult& result)
 {
     if(result.kmerize) m_kmerizePassed += 1;
     else if(result.merge) m_mergePassed += 1;
     else m_qcFail += 1;
-    if(result.kmerize && m_pDiscardWriter != nullptr) writeKmerized(*m_pDiscardWriter, item.read, result.correctSequence, result.kmerizedReads);
+    if(result.merge) *m_pCorrectedWriter << ">" << item.read.id << "\n" << result.correctSequence << "\n";
+    else if(result.kmerize && m_pDiscardWriter != nullptr) writeKmerized(*m_pDiscardWriter, item.read, result.correctSequence, result.kmerizedReads);
+    else if(!result.kmerize && m_pLowComplexWriter != nullptr) writeRecord(*m_pLowComplexWriter, item.read, result.correctSequence);
 }
 
 // FMIndexWalkProcess.cpp:972-1020

@@ -1,7 +1,8 @@
 // FMIndexWalkProcess.h -- the per-read and per-pair work and the post-processing of `stride fmwalk`, batch at a time: same results,
 // output and counters as the reference's FMIndexWalk/FMIndexWalkProcess.cpp:29-150 (MergeAndKmerize), 153-226 (MergePairedReads),
-// 229-267 (KmerizeReads) and 898-1020 (FMIndexWalkPostProcess on reads and on pairs).  The trim, the walks and the splits are
-// lrsc_fmwalk_merge, lrsc_fmwalk_hybrid and lrsc_fmwalk_kmerize, one device call per batch; the validate algorithm is not built.
+// 229-267 (KmerizeReads), 269-391 (ValidateReads) and 898-1020 (FMIndexWalkPostProcess on reads and on pairs).  The trim, the
+// walks and the splits are lrsc_fmwalk_merge, lrsc_fmwalk_hybrid, lrsc_fmwalk_kmerize and lrsc_fmwalk_validate, one device call
+// per batch.
 #pragma once
 #include <cstddef>
 #include <iosfwd>
@@ -13,7 +14,7 @@
 
 namespace stride {
 
-enum FMIndexWalkAlgorithm { FMW_HYBRID, FMW_MERGE, FMW_KMERIZE };
+enum FMIndexWalkAlgorithm { FMW_HYBRID, FMW_MERGE, FMW_KMERIZE, FMW_VALIDATE };
 
 struct FMIndexWalkParameters {
     lrsc_ctx* ctx = nullptr;             // the index to walk, on its device
@@ -40,7 +41,9 @@ public:
     // with a base other than A, C, G, T is neither merged nor kmerized (one warning per run for the latter); a read shorter than
     // the k-mer, on which the reference throws, counts as trimmed to nothing.
     std::vector<FMIndexWalkResult> process_batch(const std::vector<SequenceWorkItemPair>& pairs);
-    // KmerizeReads for every read of the batch, in order; an empty read or one with another base is not kmerized.
+    // KmerizeReads or, in validate mode, ValidateReads for every read of the batch, in order; an empty read or one with another
+    // base is neither kmerized nor merged.  In validate mode a read that lrsc_fmwalk_validate would refuse for its length ends the
+    // run with one line that names it.
     std::vector<FMIndexWalkResult> process_batch(const std::vector<SequenceWorkItem>& reads);
 
 private:
@@ -50,8 +53,10 @@ private:
 
 class FMIndexWalkPostProcess {           // the writers and the three counters
 public:
-    explicit FMIndexWalkPostProcess(std::ostream* pCorrectedWriter, std::ostream* pDiscardWriter = nullptr, FMIndexWalkAlgorithm algorithm = FMW_MERGE)
-        : m_pCorrectedWriter(pCorrectedWriter), m_pDiscardWriter(pDiscardWriter), m_algorithm(algorithm) {}
+    // pLowComplexWriter: the validate algorithm's LowComplexityReads.fa, the reads that are neither kmerized nor merged
+    explicit FMIndexWalkPostProcess(std::ostream* pCorrectedWriter, std::ostream* pDiscardWriter = nullptr, FMIndexWalkAlgorithm algorithm = FMW_MERGE,
+                                    std::ostream* pLowComplexWriter = nullptr)
+        : m_pCorrectedWriter(pCorrectedWriter), m_pDiscardWriter(pDiscardWriter), m_pLowComplexWriter(pLowComplexWriter), m_algorithm(algorithm) {}
     ~FMIndexWalkPostProcess();           // prints the counters
     void process(const SequenceWorkItem& item, const FMIndexWalkResult& result);
     void process(const SequenceWorkItemPair& itemPair, const FMIndexWalkResult& result);
@@ -59,6 +64,7 @@ public:
 private:
     std::ostream* m_pCorrectedWriter;
     std::ostream* m_pDiscardWriter;
+    std::ostream* m_pLowComplexWriter;
     FMIndexWalkAlgorithm m_algorithm;
     size_t m_kmerizePassed = 0, m_mergePassed = 0, m_qcFail = 0;
 };

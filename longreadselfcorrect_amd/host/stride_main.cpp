@@ -969,8 +969,11 @@ static int correctMain(int argc, char** argv)
 // `stride fmwalk --hybrid PAIRS` and `--kmerize READS` run the reference's hybrid (MergeAndKmerize) and kmerize (KmerizeReads)
 // algorithms the same way, lrsc_fmwalk_hybrid and lrsc_fmwalk_kmerize per batch; hybrid draws its 100000 sample rows as the
 // reference does (rand() % the index's strings, unseeded) and takes their counts from lrsc_kmer_sample_counts.  `-a hybrid`, `-a
-// kmerize` and an omitted -a are still refused: the two long options are how these modes are reached.  The validate algorithm is
-// not built.
+// kmerize` and an omitted -a are still refused: the two long options are how these modes are reached.
+// `stride fmwalk --validate READS` runs the validate algorithm (ValidateReads), lrsc_fmwalk_validate per batch of single reads: the
+// merged reads go to PREFIX.origin.fa (-o), the kmerized ones to PREFIX.kmerized.fa, and the reads that are neither to
+// LowComplexityReads.fa in the working directory, as in the reference (FMIndexWalkProcess.cpp:908-909).  `-a validate` is still
+// refused, like the other two.
 static const char* FMWALK_USAGE_MESSAGE =
     "Usage: " PACKAGE_NAME " FMIndexWalk [OPTION] ... READSFILE\n"
     "Merge paired end reads into long reads via FM-index walk\n"
@@ -986,6 +989,7 @@ static const char* FMWALK_USAGE_MESSAGE =
     "      --device=N                       HIP device to work on (default: 0)\n"
     "      --hybrid                         READSFILE holds pairs: merge them or cut them at unreliable kmers (no -a; --repeat-cutoff=N skips the sampling)\n"
     "      --kmerize                        READSFILE holds single reads: cut them at unreliable kmers (no -a)\n"
+    "      --validate                       READSFILE holds single reads: validate each by walks from end to end, else cut it (no -a)\n"
     "\nAlgorithm parameters:\n"
     "      -k, --kmer-size=N                The length of the kmer to use. (default: 31)\n"
     "      -x, --kmer-threshold=N           Attempt to correct kmers that are seen less than N times. (default: 3)\n"
@@ -999,14 +1003,15 @@ namespace fmwalkopt {
 static unsigned int verbose = 0;
 static int numThreads = 1, kmerLength = 31, kmerThreshold = 3, maxLeaves = 32, maxInsertSize = 400, minOverlap = 81, maxOverlap = -1, device = 0;
 static std::string prefix, readsFile, outFile, discardFile;
-static bool buildIndex = false, hybrid = false, kmerize = false;
+static bool buildIndex = false, hybrid = false, kmerize = false, validate = false;
+static const char* const lowComplexFile = "LowComplexityReads.fa";    // FMIndexWalkProcess.cpp:908-909: in the working directory
 static long long repeatCutoff = -1;                             // --repeat-cutoff: -1, from the sample
 static const size_t batch = 100000;                             // pairs per device call
 }
 
 static void parseFMWalkOptions(int argc, char** argv)
 {
-    enum { F_HELP = 1, F_VERSION, F_METRICS, F_DISCARD, F_LEARN, F_DEVICE, F_BUILDINDEX, F_LOADONDEVICE, F_HYBRID, F_KMERIZE, F_REPEATCUTOFF };
+    enum { F_HELP = 1, F_VERSION, F_METRICS, F_DISCARD, F_LEARN, F_DEVICE, F_BUILDINDEX, F_LOADONDEVICE, F_HYBRID, F_KMERIZE, F_REPEATCUTOFF, F_VALIDATE };
     static const struct option fmwalk_longopts[] = {
         {"verbose", no_argument, nullptr, 'v'},               {"threads", required_argument, nullptr, 't'},
         {"outfile", required_argument, nullptr, 'o'},         {"prefix", required_argument, nullptr, 'p'},
@@ -1020,6 +1025,7 @@ static void parseFMWalkOptions(int argc, char** argv)
         {"build-index", no_argument, nullptr, F_BUILDINDEX},  {"load-on-device", no_argument, nullptr, F_LOADONDEVICE},
         {"hybrid", no_argument, nullptr, F_HYBRID},           {"kmerize", no_argument, nullptr, F_KMERIZE},
         {"repeat-cutoff", required_argument, nullptr, F_REPEATCUTOFF},
+        {"validate", no_argument, nullptr, F_VALIDATE},
         {nullptr, 0, nullptr, 0}};
     optind = 1;
     std::string algo_str;
@@ -1043,6 +1049,7 @@ static void parseFMWalkOptions(int argc, char** argv)
             case F_BUILDINDEX: fmwalkopt::buildIndex = true; break;
             case F_HYBRID: fmwalkopt::hybrid = true; break;
             case F_KMERIZE: fmwalkopt::kmerize = true; break;
+            case F_VALIDATE: fmwalkopt::validate = true; break;
             case F_REPEATCUTOFF: arg >> fmwalkopt::repeatCutoff; break;
             case F_HELP: std::cout << FMWALK_USAGE_MESSAGE; exit(EXIT_SUCCESS);
             case F_VERSION: std::cout << "FMIndexWalk Version " PACKAGE_VERSION " (MI355X back end)\n"; exit(EXIT_SUCCESS);
@@ -1054,7 +1061,18 @@ static void parseFMWalkOptions(int argc, char** argv)
     if(fmwalkopt::numThreads <= 0) { std::cerr << "FMIndexWalk: invalid number of threads: " << fmwalkopt::numThreads << "\n"; die = true; }
     if(fmwalkopt::kmerLength <= 0) { std::cerr << "FMIndexWalk: invalid kmer length: " << fmwalkopt::kmerLength << ", must be greater than zero\n"; die = true; }
     if(fmwalkopt::kmerThreshold <= 0) { std::cerr << "FMIndexWalk: invalid kmer threshold: " << fmwalkopt::kmerThreshold << ", must be greater than zero\n"; die = true; }
-    if(fmwalkopt::hybrid || fmwalkopt::kmerize) {
+    if(fmwalkopt::validate) {
+        if(fmwalkopt::hybrid || fmwalkopt::kmerize) {
+            std::cerr << "FMIndexWalk: --validate and " << (fmwalkopt::hybrid ? "--hybrid" : "--kmerize") << " are two algorithms: give one\n";
+            die = true;
+        } else if(!algo_str.empty()) {
+            std::cerr << "FMIndexWalk: -a is not given together with --validate\n";
+            die = true;
+        } else if(fmwalkopt::minOverlap < 2) {
+            std::cerr << "FMIndexWalk: invalid min overlap: " << fmwalkopt::minOverlap << "\n";
+            die = true;
+        }
+    } else if(fmwalkopt::hybrid || fmwalkopt::kmerize) {
         if(fmwalkopt::hybrid && fmwalkopt::kmerize) { std::cerr << "FMIndexWalk: --hybrid and --kmerize are two algorithms: give one\n"; die = true; }
         else if(!algo_str.empty()) {
             std::cerr << "FMIndexWalk: -a is not given together with " << (fmwalkopt::hybrid ? "--hybrid" : "--kmerize") << "\n";
@@ -1075,8 +1093,8 @@ static void parseFMWalkOptions(int argc, char** argv)
     fmwalkopt::readsFile = argv[optind++];
     if(fmwalkopt::prefix.empty()) fmwalkopt::prefix = getFilename(fmwalkopt::readsFile);
     // StriDe/FMIndexWalk.cpp:346-361
-    if(fmwalkopt::outFile.empty()) fmwalkopt::outFile = getFilename(fmwalkopt::readsFile) + (fmwalkopt::kmerize ? ".origin.fa" : ".merge.fa");
-    if(fmwalkopt::hybrid || fmwalkopt::kmerize) fmwalkopt::discardFile = getFilename(fmwalkopt::readsFile) + ".kmerized.fa";
+    if(fmwalkopt::outFile.empty()) fmwalkopt::outFile = getFilename(fmwalkopt::readsFile) + (fmwalkopt::kmerize || fmwalkopt::validate ? ".origin.fa" : ".merge.fa");
+    if(fmwalkopt::hybrid || fmwalkopt::kmerize || fmwalkopt::validate) fmwalkopt::discardFile = getFilename(fmwalkopt::readsFile) + ".kmerized.fa";
 }
 
 // StriDe/FMIndexWalk.cpp:147-154: the 100000 sampled counts of min-overlap-mers from .rbwt, the line about them, and
@@ -1124,7 +1142,7 @@ static int fmwalkMain(int argc, char** argv)
     params.maxInsertSize = fmwalkopt::maxInsertSize;
     params.minOverlap = fmwalkopt::minOverlap;
     params.maxOverlap = fmwalkopt::maxOverlap;
-    params.algorithm = fmwalkopt::hybrid ? FMW_HYBRID : fmwalkopt::kmerize ? FMW_KMERIZE : FMW_MERGE;
+    params.algorithm = fmwalkopt::hybrid ? FMW_HYBRID : fmwalkopt::kmerize ? FMW_KMERIZE : fmwalkopt::validate ? FMW_VALIDATE : FMW_MERGE;
     if(fmwalkopt::hybrid) {
         if(fmwalkopt::minOverlap <= 0) { std::cerr << "FMIndexWalk: invalid min overlap: " << fmwalkopt::minOverlap << "\n"; return EXIT_FAILURE; }
         params.repeatKmerFreq = fmwalkopt::repeatCutoff >= 0 ? (size_t)fmwalkopt::repeatCutoff : fmwalkRepeatCutoff(idx, ctx);
@@ -1138,6 +1156,11 @@ static int fmwalkMain(int argc, char** argv)
             discard.open(fmwalkopt::discardFile.c_str());
             if(!discard) { std::cerr << "Error: could not open " << fmwalkopt::discardFile << " for write\n"; return EXIT_FAILURE; }
         }
+        std::ofstream lowComplex;
+        if(fmwalkopt::validate) {
+            lowComplex.open(fmwalkopt::lowComplexFile);
+            if(!lowComplex) { std::cerr << "Error: could not open " << fmwalkopt::lowComplexFile << " for write\n"; return EXIT_FAILURE; }
+        }
         std::cout << "Merge paired end reads into long reads for " << fmwalkopt::readsFile << " using \n"
                   << "min overlap=" << params.minOverlap << "\t"
                   << "max overlap=" << params.maxOverlap << "\t"
@@ -1145,10 +1168,11 @@ static int fmwalkMain(int argc, char** argv)
                   << "max Insert size=" << params.maxInsertSize << "\t"
                   << "kmer size=" << params.kmerLength << "\n\n";
         FMIndexWalkProcess processor(params);
-        FMIndexWalkPostProcess post(&writer, fmwalkopt::discardFile.empty() ? nullptr : &discard, params.algorithm);
+        FMIndexWalkPostProcess post(&writer, fmwalkopt::discardFile.empty() ? nullptr : &discard, params.algorithm, fmwalkopt::validate ? &lowComplex : nullptr);
         SeqReader reader(fmwalkopt::readsFile, true);
         WorkItemGenerator<SequenceWorkItem> generator(&reader);
-        if(fmwalkopt::kmerize) {
+        const bool single = fmwalkopt::kmerize || fmwalkopt::validate;
+        if(single) {
             std::vector<SequenceWorkItem> reads;
             for(bool more = true; more;) {
                 reads.clear();
@@ -1159,7 +1183,7 @@ static int fmwalkMain(int argc, char** argv)
             }
         }
         std::vector<SequenceWorkItemPair> pairs;
-        for(bool more = !fmwalkopt::kmerize; more;) {
+        for(bool more = !single; more;) {
             pairs.clear();
             SequenceWorkItemPair pair;
             while(pairs.size() < fmwalkopt::batch && (more = generator.generate(pair, &odd))) pairs.push_back(pair);

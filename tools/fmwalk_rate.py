@@ -17,13 +17,21 @@ search, a lane each with no frontier to keep.  Writes profiles/fmwalk_merge.json
 through lrsc_kmer_sample_counts as `stride fmwalk --hybrid` takes it (the rows from a seeded generator here), and merge mode
 alongside in the same session: three runs of each, alternating, and hybrid's ratio to merge.  --algorithm kmerize runs
 lrsc_fmwalk_kmerize over the pairs' reads as single reads.  Both add the k-mers whose two single-strand counts a split takes
-(KmerContext) per second.  They write profiles/fmwalk_hybrid.json and profiles/fmwalk_kmerize.json."""
+(KmerContext) per second.  They write profiles/fmwalk_hybrid.json and profiles/fmwalk_kmerize.json.
+
+--algorithm validate runs lrsc_fmwalk_validate (csrc/fm_validate.hip) over the pairs' reads as single reads with --validate-overlap
+as -m (default 31: a read of 100 bases is then walked over 69), and, on the first --cpu-reads of the same reads, the CPU build of the
+same code, tests/host_tools/fmwalk_validate_driver.cpp (g++ -O2, one process, the lanes of a wavefront one after the other; its time
+includes reading the index's RL units and building the rank blocks, which is given apart from a run of no reads).  It writes
+profiles/fmwalk_validate.json."""
 from __future__ import annotations
 
 import argparse
 import json
 import statistics
+import subprocess
 import sys
+import tempfile
 import time
 from collections import Counter
 from pathlib import Path
@@ -118,6 +126,67 @@ def kmerize_run(ctx, bases, off):
     return res, _rates(ctx, wall, n, "reads", kmers)
 
 
+def validate_run(ctx, bases, off, options):
+    n = off.size - 1
+    ctx.stats_reset()
+    res = np.zeros(n, dtype=capi.FMWALK_VALIDATE_DTYPE)
+    t = time.perf_counter()
+    for a in range(0, n, 2 * BATCH):
+        b = min(a + 2 * BATCH, n)
+        _, res[a:b], _, _ = ctx.fmwalk_validate(bases[int(off[a]): int(off[b])], off[a: b + 1] - off[a], **options)
+    wall = time.perf_counter() - t
+    kmers = int((res["read"]["length"][res["read"]["n_pieces"] > 0].astype(np.int64) - options["kmer_length"] + 1).sum())
+    return res, _rates(ctx, wall, n, "reads", kmers)
+
+
+def cpu_driver_rate(index, bases, off, options, n_reads):
+    """the CPU build of fm_validate.h on the first n_reads reads: (seconds with the reads, seconds of an empty run, its records)"""
+    info = index.info()
+    images = b"".join(np.array([info.num_symbols, u.size], dtype=np.uint64).tobytes() + u.tobytes() for u in (index.units(0), index.units(1)))
+    params = np.array([options["kmer_length"], options["kmer_threshold"], options["min_overlap"], options["max_overlap"], 0, options["max_leaves"]], dtype=np.int32)
+    code_of = np.zeros(256, dtype=np.uint8)
+    code_of[np.frombuffer(b"ACGT", dtype=np.uint8)] = np.arange(4, dtype=np.uint8)
+    with tempfile.TemporaryDirectory() as d:
+        exe = str(Path(d) / "fmwalk_validate_driver")
+        subprocess.run(["g++", "-std=c++17", "-O2", "-o", exe, str(REPO / "tests/host_tools/fmwalk_validate_driver.cpp"),
+                        str(REPO / "longreadselfcorrect_amd/csrc/fm_layout.cpp")], check=True)
+        seconds = []
+        for n in (n_reads, 1):
+            blob = images + params.tobytes() + np.array([n], dtype=np.uint64).tobytes() + off[: n + 1].tobytes() + code_of[bases[: int(off[n])]].tobytes()
+            t = time.perf_counter()
+            r = subprocess.run([exe, "0"], input=blob, capture_output=True, check=True)
+            seconds.append(time.perf_counter() - t)
+            if n == n_reads:
+                records = np.frombuffer(r.stdout, dtype=capi.FMWALK_VALIDATE_DTYPE, count=n)
+    return seconds[0], seconds[1], records
+
+
+def validate_algorithm(args, index, ctx, bases, off, workload_info):
+    out = Path(args.out) if args.out else REPO / "profiles" / "fmwalk_validate.json"
+    options = {k: v for k, v in OPTIONS.items() if k != "max_insert"}
+    options["min_overlap"] = args.validate_overlap
+    validate_run(ctx, bases, off, options)                                 # warm-up
+    runs = []
+    for _ in range(3):
+        res, r = validate_run(ctx, bases, off, options)
+        runs.append(r)
+        print(r, flush=True)
+    n_cpu = min(args.cpu_reads, off.size - 1)
+    cpu_s, cpu_empty_s, cpu_res = cpu_driver_rate(index, bases, off, options, n_cpu)
+    same = all(bool((cpu_res[f] == res[f][:n_cpu]).all()) for f in ("merged", "length", "status", "max_used_leaves", "coverage", "walk_length", "chosen"))
+    med = _median(runs)
+    cpu = {"reads": n_cpu, "wall_s": cpu_s, "index_load_s": cpu_empty_s, "reads_per_s": n_cpu / max(cpu_s - cpu_empty_s, 1e-9), "records_equal_the_device_s": same}
+    merged, split = res["merged"] != 0, res["read"]["n_pieces"] > 0
+    result = {"workload": {**workload_info, **options, "reads": int(off.size - 1)}, "runs": runs, "median": med, "cpu_driver": cpu,
+              "device_to_cpu_driver": med["reads_per_s"] / cpu["reads_per_s"],
+              "outcome": {"reads_merged_share": float(merged.mean()), "merged_with_a_walk_s_string_share": float((res["chosen"][merged] >= 0).mean()) if merged.any() else 0.0,
+                          "reads_split_share": float(split.mean()), "pieces_per_split_read_mean": float(res["read"]["n_pieces"][split].mean()) if split.any() else 0.0,
+                          "walk_codes": {str(k): int(v) for k, v in sorted(Counter(res["status"].reshape(-1).tolist()).items())}}}
+    out.parent.mkdir(parents=True, exist_ok=True)
+    out.write_text(json.dumps(result, indent=1) + "\n")
+    print(json.dumps(result))
+
+
 def _median(runs):
     return {k: statistics.median(r[k] for r in runs) for k in runs[0] if k != "launches"}
 
@@ -172,7 +241,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--genome-mb", type=float, default=1.0)
     ap.add_argument("--substitution-rate", type=float, default=P_SUB, help="0: reads as `stride correct` would leave them")
-    ap.add_argument("--algorithm", choices=["merge", "hybrid", "kmerize"], default="merge")
+    ap.add_argument("--algorithm", choices=["merge", "hybrid", "kmerize", "validate"], default="merge")
+    ap.add_argument("--validate-overlap", type=int, default=31, help="validate: -m")
+    ap.add_argument("--cpu-reads", type=int, default=2000, help="validate: the reads the CPU driver build is given")
     ap.add_argument("--out", default=None, help="default: profiles/fmwalk_<algorithm>.json")
     args = ap.parse_args()
     if args.algorithm == "merge" and args.out is None:
@@ -184,9 +255,12 @@ def main():
     build_s = time.perf_counter() - t
     ctx = index.ctx(api.params_default(5, 90), 0)
     if args.algorithm != "merge":
-        other_algorithms(args, api, ctx, bases, off, {"genome_mb": args.genome_mb, "pairs": (off.size - 1) // 2, "read_length": READ_LEN,
-                                                      "fragment_bases": [FRAG_MIN, FRAG_MAX], "coverage": COVERAGE, "substitution_rate": args.substitution_rate,
-                                                      "bases": int(bases.size), "batch": BATCH, **OPTIONS, "index_build_s": build_s})
+        info = {"genome_mb": args.genome_mb, "pairs": (off.size - 1) // 2, "read_length": READ_LEN, "fragment_bases": [FRAG_MIN, FRAG_MAX], "coverage": COVERAGE,
+                "substitution_rate": args.substitution_rate, "bases": int(bases.size), "batch": BATCH, "index_build_s": build_s}
+        if args.algorithm == "validate":
+            validate_algorithm(args, index, ctx, bases, off, info)
+        else:
+            other_algorithms(args, api, ctx, bases, off, {**info, **OPTIONS})
         ctx.close()
         index.close()
         return
