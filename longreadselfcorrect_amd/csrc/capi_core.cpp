@@ -101,11 +101,11 @@ Tunables lrsc::read_tunables(const lrsc_ctx* ctx)
     t.wp_prep_bytes = env_bytes("LRSC_WP_PREP_MB", 24ull << 30, 20);                         // 24576 MB, at least 1
     t.wp_lane_bytes = env_bytes("LRSC_WP_LANE_MB", 32ull << 30, 20);                         // 32768 MB, at least 1
     t.wp_lanes = env_clamped("LRSC_WP_LANES", resident_waves(ctx, 2) * 64u, 64, kIntMax);    // 2 wavefronts per SIMD x 64, at least 64
-    t.wp_gen_quorum = env_clamped("LRSC_WP_GEN_QUORUM", 70, 0, 100);                         // 70 %, 0..100
+    t.wp_gen_quorum = env_clamped("LRSC_WP_GEN_QUORUM", 50, 0, 100);                         // 50 %, 0..100
     t.wp_gen_wait = env_clamped("LRSC_WP_GEN_WAIT", 6, 0, kIntMax);                          // 6, at least 0
     t.wp_wide_cap = env_clamped("LRSC_WP_WIDE_CAP", kNarrowLeaves, 1, (int)kNarrowLeaves);   // 32, 1..32
     t.wp_wave = env_clamped("LRSC_WP_WAVE", 1, 0, 2);                                        // 1, 0..2
-    t.wp_deal = env_clamped("LRSC_WP_DEAL", 1, 0, 1);                                        // 1, 0..1
+    t.wp_deal = env_clamped("LRSC_WP_DEAL", (int)kDealLevelDefault, 0, (int)kDealLevelTerm);   // 1, 0..3
     { const char* e = std::getenv("LRSC_WP_BEGIN_SORT"); t.wp_begin_sort = e && e[0] != '0'; } // off; on unless the value starts with 0
     t.dp_chunk_bytes = env_bytes("LRSC_DP_CHUNK_MB", 16ull << 30, 20);                       // 16384 MB, at least 1
     t.dp_align_waves = env_clamped("LRSC_DP_ALIGN_WAVES", 0, 0, kIntMax);                    // 0 = sized as usual, at least 0

@@ -215,7 +215,7 @@ int WpFlow::bind_args()
     a.req_out = sc.d_req.p; a.req_cap = n;
     a.out_codes = sc.d_codes_out.p; a.piece_start = sc.d_pieces.p;
     a.auto_dp = (!p.no_dp && p.next_target == 1) ? 1u : 0u;
-    a.general_quorum_pct = tn.wp_gen_quorum; a.general_max_wait = tn.wp_gen_wait;
+    a.general_quorum_pct = tn.wp_gen_quorum; a.general_max_wait = tn.wp_gen_wait; a.deal_level = tn.wp_deal;
     a.ctr = ctx->d_ctr;
     if(b->debug_flags & LRSC_DEBUG_WALKS) {
         if(!b->d_walk_log) HIP_TRY(hipMalloc(reinterpret_cast<void**>(&b->d_walk_log), b->seed_cap));
@@ -228,7 +228,7 @@ int WpFlow::bind_args()
         HIP_TRY(hipMemsetAsync(sc.d_prof.p, 0, kWpProfWords * sizeof(unsigned long long), ctx->stream));
         a.prof = sc.d_prof.p;
         a.begin_stats = sc.d_prof.p + 32;                                    // [32..36): wp_begin's interval lists, zeroed every round
-                                                                             // [36..46): WpArgs::gen_stats of round 0's bulk launch
+                                                                             // [36..58): WpArgs::gen_stats of round 0's bulk launch
     }
     // side stream: the few walks across long gaps run beside the DP stage of the bulk's failed walks instead of before it (they are
     // latency-bound on their own: a walk is a chain of dependent steps)
@@ -383,8 +383,8 @@ int WpFlow::launch_order(Round& R)
 // until it ends.
 // LRSC_WP_WAVE, one-walk-per-wavefront launches: 1 = the frontier across the wavefront (wp_extend_wave_kernel), 0 = lane 0 walks alone
 // (wp_extend_kernel); 2 = test hook: every extension launch goes through wp_extend_wave_kernel at stride 64
-// LRSC_WP_DEAL, lane-per-walk launches: 1 = extendLeaves' per-leaf work dealt across the wavefront (wp_extend_deal_kernel), 0 = the
-// serial step (wp_extend_kernel)
+// LRSC_WP_DEAL, lane-per-walk launches: 0 = the serial step (wp_extend_kernel); 1..3 = wp_extend_deal_kernel with extendLeaves'
+// per-leaf work dealt across the wavefront, from 2 PrunedBySeedSupport too, from 3 isTerminated's scans too (wp_deal_level.h)
 hipError_t WpFlow::extend_range(WpArgs x, const uint32_t* list, const WpRequest* rq, uint32_t count, uint32_t pathw, hipStream_t st,
                                 bool side, uint32_t stride)
 {
@@ -650,6 +650,16 @@ int WpFlow::print_extension_profile()
                      g[0], g[1] / s, g[2] / s, (double)g[2] / std::max(g[1], 1ull), g[3] / s, (double)g[6] / std::max(g[2], 1ull), g[8] / s,
                      g[4] / s, (double)g[4] / std::max(g[1], 1ull), g[5] / s, (double)g[7] / std::max(g[4], 1ull), g[9] / s,
                      g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], g[9]);
+        // the same question for the two phases that follow extendLeaves (wp_extend_deal_kernel counts them): per phase, items and
+        // the loads behind them
+        const unsigned long long* h = g + 10;
+        if(h[0] | h[6])
+            std::fprintf(stderr, "[lrsc] wp bulk launches, phases of a general step: PrunedBySeedSupport, children that need the seed search %.1f in all, %.2f in the widest "
+                                 "(widest x lanes / all = %.2f), chain entries %.1f in all, %.1f in the widest (%.2f); isTerminated, leaves past the filter %.2f in all, "
+                                 "%.2f in the widest (%.2f), term rows %.1f in all, %.1f in the widest (%.2f); counters %llu %llu %llu %llu %llu %llu %llu %llu %llu %llu %llu %llu\n",
+                         h[0] / s, h[1] / s, (double)h[2] / std::max(h[0], 1ull), h[3] / s, h[4] / s, (double)h[5] / std::max(h[3], 1ull),
+                         h[6] / s, h[7] / s, (double)h[8] / std::max(h[6], 1ull), h[9] / s, h[10] / s, (double)h[11] / std::max(h[9], 1ull),
+                         h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[7], h[8], h[9], h[10], h[11]);
     }
     return LRSC_OK;
 }

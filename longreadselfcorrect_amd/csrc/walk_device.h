@@ -731,12 +731,14 @@ struct Walk : WalkCap<BIG> {
         while(jf != 0xFFFFu || jr != 0xFFFFu) {
             const uint64_t vf = jf != 0xFFFFu ? it9f[jf].val : 0, vr = jr != 0xFFFFu ? it9r[jr].val : 0;
             if(fv && jf != 0xFFFFu && vf >= startSeedIdx && vf <= largeSeedIdx) {
+                LRSC_WALK_TRACE(12, 0, 0);
                 const int d = abs((int)vf - (int)currSeedIdx);
                 if(d < minIdxDiff) { nd.lastSeedIdx = vf; nd.queryOverlapLen = vf + seedSize; minIdxDiff = d; }
                 nd.lastOverlapLen = currentLength;
                 nd.currOverlapLen = currentLength;
                 isNewSeedFound = true;
             } else if(rv && jr != 0xFFFFu && vr >= startSeedIdx && vr <= largeSeedIdx) {
+                LRSC_WALK_TRACE(12, 1, 0);
                 const int d = abs((int)currSeedIdx - (int)vr);
                 if(d < minIdxDiff) { nd.lastSeedIdx = vr; nd.queryOverlapLen = vr + seedSize; minIdxDiff = d; }
                 nd.lastOverlapLen = currentLength;
@@ -954,12 +956,48 @@ struct Walk : WalkCap<BIG> {
         }
     }
 
+    // profiling (WpArgs::gen_stats): the work of this step's PrunedBySeedSupport, counted before it runs -- the children that need
+    // the seed-support search, and the chain entries their searches walk (every entry of the child's bucket, per valid strand)
+    uint32_t ph_need, ph_chain;
+    // ... and of its isTerminated loop, counted after the commit: the leaves that pass term_may_hit and the term rows they scan
+    uint32_t ph_term, ph_rows;
+    LRSC_WALK_FN void count_prune_work()
+    {
+        const uint32_t mask9 = seedSize >= 16 ? 0xFFFFFFFFu : ((1u << (2 * seedSize)) - 1u);
+        ph_need = 0; ph_chain = 0;
+        for(uint32_t c = 0; c < n_nxt; ++c) {
+            const Leaf<P>& lf = nxt[c];
+            const uint64_t d = currentLength - lf.lastOverlapLen;
+            if(!(d > seedSize || d <= 1)) continue;
+            ++ph_need;
+            const uint32_t code9 = (uint32_t)lf.suf_lo & mask9;
+            const uint32_t hb = (code9 ^ (code9 >> 9)) & 255u;
+            if(lf.flo <= lf.fhi) for(uint32_t j = head9f[hb]; j != 0xFFFFu; j = next9f[j]) ++ph_chain;
+            if(lf.rlo <= lf.rhi) for(uint32_t j = head9r[hb]; j != 0xFFFFu; j = next9r[j]) ++ph_chain;
+        }
+    }
+    LRSC_WALK_FN void count_term_work()
+    {
+        ph_term = 0; ph_rows = 0;
+        if(currentLength < minLength) return;
+        for(uint32_t i = 0; i < n_cur; ++i) {
+            if(!term_may_hit(cur[i].suf_lo)) continue;
+            ++ph_term;
+            const uint64_t i0 = (uint64_t)(cur[i].res_second > 0 ? cur[i].res_second : 0), end = (uint64_t)trg_len - (int)minOverlap;
+            if(i0 <= end) ph_rows += (uint32_t)(end + 1 - i0);
+        }
+    }
+
     // ---- isTerminated for one leaf (.cpp:825-878); path given as (words, len) + optional extra char ------------
     LRSC_WALK_FN LRSC_WALK_NOINLINE void terminated_leaf(Leaf<P>& lf, const uint32_t* pw, uint32_t plen, int extra)
     {
-        const int hit = term_scan(lf);
+        terminated_hit(lf, term_scan(lf), pw, plen, extra);
+    }
+    // ... from the scan's answer on (wp_deal_step.h's deal_term hands the owner a scan that another lane ran)
+    LRSC_WALK_FN __forceinline__ void terminated_hit(Leaf<P>& lf, int hit, const uint32_t* pw, uint32_t plen, int extra)
+    {
         if(hit < 0) return;
-        if(lf.res_first == -1) {                          // the first hit of the scan takes a result slot
+        if(lf.res_first == -1) {                         // the first hit of the scan takes a result slot
             if(n_results >= max_results()) { error = LRSC_WALK_ERR_RESULTS; return; }
             ++n_results;
             lf.res_first = (int)n_results;
@@ -1306,11 +1344,18 @@ struct Walk : WalkCap<BIG> {
     // the step from PrunedBySeedSupport on: what follows extendLeaves (or its dealt form, wp_deal.hip) in the walk's own lane
     LRSC_WALK_FN void step_after_extend()
     {
+        const uint64_t t = tick();
+        PrunedBySeedSupport();
+        tock(4, t);
+        if(step_commit()) step_terminated();
+    }
+
+    // the step from the survivor count to the end of the commit (alive_lo / alive_hi / has_child are PrunedBySeedSupport's, or
+    // deal_prune's).  false: the step is over (the frontier overflowed, or an error)
+    LRSC_WALK_FN bool step_commit()
+    {
         {
             uint64_t t = tick();
-            PrunedBySeedSupport();
-            tock(4, t);
-            t = tick();
             uint32_t survivors = (uint32_t)(__builtin_popcountll(alive_lo) + __builtin_popcountll(alive_hi));
             if constexpr(BIG) { survivors = 0; for(uint32_t w = 0; w < bits_words(n_nxt); ++w) survivors += (uint32_t)__builtin_popcountll(this->alive_bits[w]); }
             auto is_alive = [&](uint32_t c) -> bool {
@@ -1326,11 +1371,11 @@ struct Walk : WalkCap<BIG> {
                         if(!is_alive(c)) continue;
                         const Leaf<P>& par = cur[nxt[c].parent];
                         terminated_leaf(nxt[c], paths + (uint64_t)par.path * pathw, par.path_len, (int)nxt[c].ext);
-                        if(error) return;
+                        if(error) return false;
                     }
                 n_cur = survivors;
                 ended = true;
-                return;
+                return false;
             }
             // materialise the survivors: the first surviving child of a parent takes over its ring and path
             // in place (SAINode::extend), further ones get copies (createChild).  A child still carries its parent's
@@ -1420,7 +1465,15 @@ struct Walk : WalkCap<BIG> {
             else for(uint32_t i = 0; i < w; ++i) leaf_move(&cur[i], &nxt[i]);
             n_cur = w;
             tock(5, t);
-            t = tick();
+        }
+        return true;
+    }
+
+    // isTerminated over the new frontier, after a commit that went through
+    LRSC_WALK_FN void step_terminated()
+    {
+        {
+            const uint64_t t = tick();
             // isTerminated over the new frontier.  term_scan starts with a filter on the leaf's last characters that rules most
             // leaves out; it is a function of suf_lo and of the walk's constants alone, and terminated_leaf writes nothing but its
             // own leaf's result index, the result slots and `error`.  So the suffixes of kTermGroup leaves are loaded together and

@@ -16,6 +16,7 @@
 #include "correct_dev.h"
 #include "dp_dev.h"
 #include "extend.h"
+#include "wp_deal_level.h"
 
 namespace lrsc {
 
@@ -173,6 +174,7 @@ struct WpArgs {
     uint32_t lane_stride;        // 1: every lane of a wavefront runs walks; 64: one walk per wavefront (the few very long walks: a lane-per-walk
                                  // wavefront advances at the pace of its slowest lane, and these are thousands of wide steps long)
     uint32_t general_quorum_pct, general_max_wait;   // lanes that need the general step wait for company (see wp_extend_kernel)
+    uint32_t deal_level;         // wp_extend_deal_kernel: how much of the general step is dealt across the wavefront (wp_deal_level.h)
     uint32_t auto_dp;            // a failed walk with next == 0 goes to the DP stage in the same round
     WpDpItem* dp_items;
     uint32_t* n_dp_items;
@@ -201,10 +203,13 @@ struct WpArgs {
     // LRSC_CORRECT_PROFILE, round 0's bulk launch only (nullptr elsewhere): over the general steps its wavefronts take, [0] steps,
     // [1] lanes taking part, [2] sum and [3] sum of the per-step maximum of their n_cur, [4] / [5] the same of n_nxt after extendLeaves,
     // [6] / [7] sum of (maximum x lanes taking part) for n_cur / n_nxt, [8] / [9] sum of ceil(sum / 64): the passes of 64 lanes that
-    // the step's leaves / children fill
+    // the step's leaves / children fill.  wp_extend_deal_kernel adds [10, 22): the work of the step's PrunedBySeedSupport and
+    // isTerminated phases (wp_gen_count_phases) -- sum, sum of the per-step maximum and sum of (maximum x lanes taking part) of the
+    // children that need the seed-support search, the chain entries they walk, the leaves that pass term_may_hit, the term rows
+    // they scan
     unsigned long long* gen_stats;
 };
-constexpr uint32_t kWpProfWords = 46;        // WpArgs::prof [0, 32), begin_stats [32, 36), gen_stats [36, 46)
+constexpr uint32_t kWpProfWords = 58;        // WpArgs::prof [0, 32), begin_stats [32, 36), gen_stats [36, 58)
 
 constexpr uint32_t kWpPathwSmall = 64, kWpPathwMid = 256;
 

@@ -51,12 +51,15 @@ struct DevLanes {
 // PROF: the LRSC_CORRECT_PROFILE instantiation.  The tick slots are an array the Walk object points to, which lives in scratch
 // memory whether or not a launch asks for ticks (72 B of the private segment); the launches that do not ask run without it.
 // ---------------------------------------------------------------------------------------
-template <bool WIDE, bool PROF>
-__global__ __launch_bounds__(64, LRSC_WP_EXTEND_OCC) void wp_extend_deal_kernel(FmIndexDev fm, WpArgs a)
+// MAXLVL: the highest LRSC_WP_DEAL level the body can run.  Two kernels share the body: wp_extend_deal_kernel is level 1, compiled
+// without deal_prune and deal_term, so that it pays neither for their registers nor for their spills; wp_extend_deal_phases_kernel
+// runs levels 2 and 3 (a.deal_level, wavefront-uniform).  As one kernel with the level read at run time the body had 152 / 163
+// spilled VGPRs against 85 / 97 and ran level 1 one per cent slower; as two bodies in one kernel its private segment was 592 /
+// 736 B, past the bound tests/test_deal_kernel_build.py holds it to ("The prune and isTerminated dealt").
+template <bool WIDE, bool PROF, uint32_t MAXLVL>
+__device__ __forceinline__ void wp_extend_deal_body(const FmIndexDev& fm, const WpArgs& a, const uint32_t* mtab)
 {
     using P = typename Lay<WIDE>::pos_t;
-    __shared__ __attribute__((aligned(16))) uint32_t mtab[MaskTabSize<WIDE>::value];
-    init_mask_table<WIDE>(mtab);
     const uint32_t lane = threadIdx.x;
     const uint32_t lane_id = blockIdx.x * 64 + lane;
     bool done = lane_id >= a.n_lanes;
@@ -133,9 +136,14 @@ __global__ __launch_bounds__(64, LRSC_WP_EXTEND_OCC) void wp_extend_deal_kernel(
                 const bool act = r == 2;
                 if(act) { gen_wait = 0; want_gen = false; }
                 const uint32_t n_cur0 = W.n_cur;
-                const bool took = deal_step<DevLanes>(W, act, lane);
+                const bool took = deal_step<DevLanes, WIDE, MAXLVL>(W, act, lane, a.deal_level);
                 if(act) r = took ? 1 : 0;
-                if constexpr(PROF) { if(a.gen_stats) wp_gen_count(a.gen_stats, took, n_cur0, W.n_nxt); }
+                if constexpr(PROF) {
+                    if(a.gen_stats) {
+                        wp_gen_count(a.gen_stats, took, n_cur0, W.n_nxt);
+                        if(prof) wp_gen_count_phases(a.gen_stats + 10, took, W.ph_need, W.ph_chain, W.ph_term, W.ph_rows);
+                    }
+                }
             }
         }
         if(r == 0) {
@@ -159,13 +167,36 @@ __global__ __launch_bounds__(64, LRSC_WP_EXTEND_OCC) void wp_extend_deal_kernel(
     flush_counters(a.ctr, W.n_rank, W.n_blk);
 }
 
+template <bool WIDE, bool PROF>
+__global__ __launch_bounds__(64, LRSC_WP_EXTEND_OCC) void wp_extend_deal_kernel(FmIndexDev fm, WpArgs a)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t mtab[MaskTabSize<WIDE>::value];
+    init_mask_table<WIDE>(mtab);
+    wp_extend_deal_body<WIDE, PROF, kDealLevelExtend>(fm, a, mtab);
+}
+template <bool WIDE, bool PROF>
+__global__ __launch_bounds__(64, LRSC_WP_EXTEND_OCC) void wp_extend_deal_phases_kernel(FmIndexDev fm, WpArgs a)
+{
+    __shared__ __attribute__((aligned(16))) uint32_t mtab[MaskTabSize<WIDE>::value];
+    init_mask_table<WIDE>(mtab);
+    wp_extend_deal_body<WIDE, PROF, kDealLevelTerm>(fm, a, mtab);
+}
+
 hipError_t launch_wp_extend_deal(const FmIndexDev& fm, const WpArgs& a, hipStream_t stream)
 {
     if(a.n_list == 0 || a.n_lanes == 0) return hipSuccess;
     if(a.lane_stride > 1) return hipErrorInvalidValue;                 // one walk per lane only
     const unsigned nb = (unsigned)(((uint64_t)a.n_lanes + 63) / 64);
     const bool prof = a.prof != nullptr || a.gen_stats != nullptr;
-    if(fm.wide) {
+    if(a.deal_level >= kDealLevelPrune) {
+        if(fm.wide) {
+            if(prof) hipLaunchKernelGGL((wp_extend_deal_phases_kernel<true, true>), dim3(nb), dim3(64), 0, stream, fm, a);
+            else     hipLaunchKernelGGL((wp_extend_deal_phases_kernel<true, false>), dim3(nb), dim3(64), 0, stream, fm, a);
+        } else {
+            if(prof) hipLaunchKernelGGL((wp_extend_deal_phases_kernel<false, true>), dim3(nb), dim3(64), 0, stream, fm, a);
+            else     hipLaunchKernelGGL((wp_extend_deal_phases_kernel<false, false>), dim3(nb), dim3(64), 0, stream, fm, a);
+        }
+    } else if(fm.wide) {
         if(prof) hipLaunchKernelGGL((wp_extend_deal_kernel<true, true>), dim3(nb), dim3(64), 0, stream, fm, a);
         else     hipLaunchKernelGGL((wp_extend_deal_kernel<true, false>), dim3(nb), dim3(64), 0, stream, fm, a);
     } else {

@@ -14,8 +14,13 @@
 // make_child on the EXECUTING lane's Walk object, so sF / sR / fm / mtab, PBcoverage, PacBioErrorRate, freqsOfKmerSize, minOverlap
 // and whatever else wp_walk_consts sets must be the same on all lanes.  What differs from walk to walk and a task reads
 // (min_SA_threshold, currentLength, maxIndelSize, the 5-mer chains) steps aside for the owner's in deal_attempt; a constant that
-// becomes per-walk has to join that list.
+// becomes per-walk has to join that list.  deal_prune's tasks run prune_leaf on the executing lane's Walk object in the same way:
+// seedSize, PacBioErrorRate, errorRate and localK are wavefront-uniform, and what steps aside for the owner's is currentLength and
+// the 9-mer tables (head9f/r, it9f/r, next9f/r); nxt, rings, maxIndelSize and Lq are read across lanes into the task's own
+// values.  deal_term's tasks run term_scan: minOverlap is uniform, and currentKmerSize, tmask0/1, term and trg_len step aside;
+// cur is read across lanes.
 #pragma once
+#include "wp_deal_level.h"
 
 #ifndef LRSC_DEAL_TRACE
 #define LRSC_DEAL_TRACE(kind, a, b, c)         // test hook (tests/host_walk_deal): which shapes of the dealt passes were run
@@ -200,10 +205,163 @@ LRSC_WALK_FN void deal_attempt(Walk<WIDE>& W, bool on, uint32_t lane)
     X::sync();
 }
 
-// ---- one iteration of extendOverlap's loop (Walk::step) for the lanes with `act`; every lane of the wavefront comes here ----------
-// returns Walk::step()'s answer for an `act` lane (false otherwise)
+// the tasks of the pass at `base` that belong to this lane as an owner: [s0, s1) of the deal, none where s0 >= s1
+struct DealSpan {
+    uint32_t s0, s1;
+};
+LRSC_WALK_FN DealSpan deal_span(const Deal& d, uint32_t base)
+{
+    DealSpan s;
+    s.s0 = d.excl > base ? d.excl : base;
+    s.s1 = d.incl < base + 64 ? d.incl : base + 64;
+    return s;
+}
+// bit k = bit (s0 - base + k) of a ballot over the pass's task lanes, for the s1 - s0 tasks of the span
+LRSC_WALK_FN uint64_t deal_span_bits(uint64_t ballot, const DealSpan& s, uint32_t base)
+{
+    const uint32_t n = s.s1 - s.s0;
+    return (ballot >> (s.s0 - base)) & (n >= 64 ? ~0ull : (1ull << n) - 1ull);
+}
+
+// ---- PrunedBySeedSupport (.cpp:491-563) of the owners with `on`: a task is prune_leaf<true> of one child of nxt[0, n_nxt) ----------
+// The order of the children cannot be observed (the comment in Walk::PrunedBySeedSupport): a child's evaluation reads its own
+// fields, the walk's tables, fixed since begin_static, and one slot of its parent's ring, which only the commit writes; it writes
+// its own fields.  The owner receives the frontier's bit sets: alive_lo / alive_hi from a ballot of the pass's tasks, shifted to
+// the owner's child indices and accumulated over the passes its children fall into; has_child from an OR over the owner's tasks of
+// the pass (a scan that restarts at the owner's first task).  Both are ORs of one bit per surviving child, so the order in which
+// they are set is the serial loop's as far as anything can tell.
 template <class X, bool WIDE>
-LRSC_WALK_FN bool deal_step(Walk<WIDE>& W, bool act, uint32_t lane)
+LRSC_WALK_FN void deal_prune(Walk<WIDE>& W, bool on, uint32_t lane)
+{
+    using P = typename Lay<WIDE>::pos_t;
+    if(on) { W.alive_lo = 0; W.alive_hi = 0; W.has_child = 0; }
+    const Deal d = deal_make<X>(on ? W.n_nxt : 0u, lane);
+    if(lane == 0) { LRSC_DEAL_TRACE(4, d.total, 0, 0); }
+    for(uint32_t base = 0; base < d.total; base += 64) {
+        const uint32_t t = base + lane;
+        const bool have = t < d.total;
+        const uint32_t tt = have ? t : d.total - 1;
+        const uint32_t o = deal_owner<X>(d, tt);
+        const uint32_t o_excl = X::shfl(d.excl, o);
+        const uint32_t c = tt - o_excl;
+        // the owner's walk, as far as prune_leaf, seed_support_core and computeErrorRate read it
+        Leaf<P>* const o_nxt = deal_shfl_ptr<X>(W.nxt, o);
+        double* const o_rings = deal_shfl_ptr<X>(W.rings, o);
+        uint16_t* const o_head9f = deal_shfl_ptr<X>(W.head9f, o);
+        uint16_t* const o_head9r = deal_shfl_ptr<X>(W.head9r, o);
+        SortItem* const o_it9f = deal_shfl_ptr<X>(W.it9f, o);
+        SortItem* const o_it9r = deal_shfl_ptr<X>(W.it9r, o);
+        uint16_t* const o_next9f = deal_shfl_ptr<X>(W.next9f, o);
+        uint16_t* const o_next9r = deal_shfl_ptr<X>(W.next9r, o);
+        const uint64_t o_len = deal_shfl_u64<X>(W.currentLength, o), o_indel = deal_shfl_u64<X>(W.maxIndelSize, o);
+        const uint32_t o_Lq = X::shfl(W.Lq, o);
+        // this lane's own walk steps aside for the task
+        const uint64_t s_len = W.currentLength;
+        uint16_t* const s_head9f = W.head9f;
+        uint16_t* const s_head9r = W.head9r;
+        SortItem* const s_it9f = W.it9f;
+        SortItem* const s_it9r = W.it9r;
+        uint16_t* const s_next9f = W.next9f;
+        uint16_t* const s_next9r = W.next9r;
+        W.currentLength = o_len;
+        W.head9f = o_head9f; W.head9r = o_head9r; W.it9f = o_it9f; W.it9r = o_it9r; W.next9f = o_next9f; W.next9r = o_next9r;
+        bool alive = false;
+        uint32_t pbit = 0;
+        if(have) {
+            // PrunedBySeedSupport's window of the owner's step
+            const uint64_t currSeedIdx = o_len - W.seedSize;
+            const uint64_t indelOffset = W.seedSize + o_indel;
+            const uint64_t smallSeedIdx = currSeedIdx <= indelOffset ? 0 : currSeedIdx - indelOffset;
+            const uint64_t largeSeedIdx = (currSeedIdx + indelOffset) >= (o_Lq - W.seedSize) ? (o_Lq - W.seedSize) : currSeedIdx + indelOffset;
+            Leaf<P>& ch = o_nxt[c];
+            LRSC_DEAL_TRACE(5, base, o_excl, (o_len - ch.lastOverlapLen > W.seedSize || o_len - ch.lastOverlapLen <= 1) ? 1 : 0);
+            // a child still carries its parent's ring id: the parent's error history, which no commit has touched yet
+            W.template prune_leaf<true>(ch, o_rings + (uint64_t)ch.ring * 100, currSeedIdx, smallSeedIdx, largeSeedIdx);
+            alive = ch.alive != 0;
+            if(alive) pbit = 1u << ch.parent;
+            LRSC_DEAL_TRACE(6, c, alive, ch.parent);
+        }
+        W.currentLength = s_len;
+        W.head9f = s_head9f; W.head9r = s_head9r; W.it9f = s_it9f; W.it9r = s_it9r; W.next9f = s_next9f; W.next9r = s_next9r;
+        // the owners take their children's bits of this pass
+        const uint64_t am = X::ballot(alive);
+        const uint32_t first = o_excl > base ? o_excl - base : 0u;      // the lane of the first task of this task's owner in this pass
+        uint32_t hc = pbit;
+        for(uint32_t s = 1; s < 64; s <<= 1) { const uint32_t w = X::shfl_up(hc, s); if(lane >= first + s) hc |= w; }
+        const DealSpan sp = deal_span(d, base);
+        const bool mine = on && sp.s0 < sp.s1;
+        const uint32_t got = X::shfl(hc, mine ? sp.s1 - 1 - base : 0u);
+        if(mine) {
+            const uint64_t seg = deal_span_bits(am, sp, base);
+            const uint32_t c0 = sp.s0 - d.excl;                          // the owner's first child of this pass
+            LRSC_DEAL_TRACE(7, base, d.excl, (seg != 0 ? 1 : 0) | ((W.alive_lo | W.alive_hi) != 0 ? 2 : 0));
+            if(c0 < 64) { W.alive_lo |= seg << c0; if(c0) W.alive_hi |= seg >> (64 - c0); }
+            else W.alive_hi |= seg << (c0 - 64);
+            W.has_child |= got;
+        }
+    }
+    X::sync();                                            // the children's fields are in memory for their owners' commits
+}
+
+// ---- isTerminated (.cpp:825-878) over the new frontier of the owners with `on`: a task is term_scan of one leaf of cur[0, n_cur) ----
+// term_scan is a function of the leaf and of the walk's constants and issues no rank query.  The owner then takes its hits of the
+// pass in leaf order and does with each what terminated_leaf does from the scan's answer on (the result slot, LRSC_WALK_ERR_RESULTS,
+// res_second, term_store), and stops at the first error as the serial loop does: a later hit of the same owner, in this pass or a
+// later one, is dropped.  The scan that ran for a leaf behind the error cannot be observed: it stores nothing and counts nothing.
+template <class X, bool WIDE>
+LRSC_WALK_FN void deal_term(Walk<WIDE>& W, bool on, uint32_t lane)
+{
+    using P = typename Lay<WIDE>::pos_t;
+    X::sync();                                            // the owners' new frontiers are in memory for every lane
+    const Deal d = deal_make<X>(on ? W.n_cur : 0u, lane);
+    if(lane == 0) { LRSC_DEAL_TRACE(8, d.total, 0, 0); }
+    for(uint32_t base = 0; base < d.total; base += 64) {
+        const uint32_t t = base + lane;
+        const bool have = t < d.total;
+        const uint32_t tt = have ? t : d.total - 1;
+        const uint32_t o = deal_owner<X>(d, tt);
+        const uint32_t i = tt - X::shfl(d.excl, o);
+        // the owner's walk, as far as term_may_hit and term_scan read it
+        Leaf<P>* const o_cur = deal_shfl_ptr<X>(W.cur, o);
+        const P* const o_term = deal_shfl_ptr<X>(W.term, o);
+        const uint64_t o_kmer = deal_shfl_u64<X>(W.currentKmerSize, o), o_tm0 = deal_shfl_u64<X>(W.tmask0, o), o_tm1 = deal_shfl_u64<X>(W.tmask1, o);
+        const uint32_t o_trg = X::shfl(W.trg_len, o);
+        // this lane's own walk steps aside for the task
+        const P* const s_term = W.term;
+        const uint64_t s_kmer = W.currentKmerSize, s_tm0 = W.tmask0, s_tm1 = W.tmask1;
+        const uint32_t s_trg = W.trg_len;
+        W.term = o_term; W.currentKmerSize = o_kmer; W.tmask0 = o_tm0; W.tmask1 = o_tm1; W.trg_len = o_trg;
+        int hit = -1;
+        if(have) {
+            LRSC_DEAL_TRACE(9, base, W.term_may_hit(o_cur[i].suf_lo), 0);
+            hit = W.term_scan(o_cur[i]);
+        }
+        W.term = s_term; W.currentKmerSize = s_kmer; W.tmask0 = s_tm0; W.tmask1 = s_tm1; W.trg_len = s_trg;
+        // the owners take their leaves' hits of this pass, lowest leaf first
+        const uint64_t hm = X::ballot(hit >= 0);
+        const DealSpan sp = deal_span(d, base);
+        uint64_t todo = on && sp.s0 < sp.s1 && !W.error ? deal_span_bits(hm, sp, base) : 0ull;
+        while(X::ballot(todo != 0)) {
+            const uint32_t l = todo ? sp.s0 - base + (uint32_t)__builtin_ctzll(todo) : 0u;
+            const int h = (int)X::shfl((uint32_t)hit, l);
+            if(todo) {
+                todo &= todo - 1ull;
+                Leaf<P>& lf = W.cur[base + l - d.excl];
+                LRSC_DEAL_TRACE(10, lf.res_first == -1, todo != 0 || d.incl > base + 64, 0);
+                W.terminated_hit(lf, h, W.paths + (uint64_t)lf.path * W.pathw, lf.path_len, -1);
+                if(W.error) { LRSC_DEAL_TRACE(11, todo != 0 || d.incl > base + 64, 0, 0); todo = 0; }
+            }
+        }
+    }
+}
+
+// ---- one iteration of extendOverlap's loop (Walk::step) for the lanes with `act`; every lane of the wavefront comes here ----------
+// level (wp_deal_level.h, wavefront-uniform): what follows extendLeaves is dealt too -- from kDealLevelPrune PrunedBySeedSupport,
+// from kDealLevelTerm isTerminated's scans; below that it runs in the walk's own lane, as Walk::step_after_extend() has it.
+// MAXLVL: the highest level this instantiation can run (a lower one carries neither the dealt phases' code nor their registers).
+// returns Walk::step()'s answer for an `act` lane (false otherwise)
+template <class X, bool WIDE, uint32_t MAXLVL = kDealLevelTerm>
+LRSC_WALK_FN bool deal_step(Walk<WIDE>& W, bool act, uint32_t lane, uint32_t level = kDealLevelDefault)
 {
     if(act && (W.ended || W.error || !(W.n_cur != 0 && W.n_cur <= W.maxLeaves && W.currentLength <= W.maxLength))) act = false;
     const bool took = act;
@@ -261,8 +419,44 @@ LRSC_WALK_FN bool deal_step(Walk<WIDE>& W, bool act, uint32_t lane)
         deal_refine<X>(W, relax, W.nxt, W.n_nxt, RelaxSize, lane);
     }
     if(took) W.tock(0, t_ext);
-    // --- PrunedBySeedSupport, the commit and isTerminated, in the walk's own lane ---
-    if(act) W.step_after_extend();
+    if constexpr(MAXLVL < kDealLevelPrune) {
+        // --- PrunedBySeedSupport, the commit and isTerminated, in the walk's own lane ---
+        // (Walk::step_after_extend(), with the phases' work counted between its pieces in a profiling launch)
+        if(W.prof) { W.ph_need = 0; W.ph_chain = 0; W.ph_term = 0; W.ph_rows = 0; }
+        if(act) {
+            if(W.prof) W.count_prune_work();
+            t = W.tick();
+            W.PrunedBySeedSupport();
+            W.tock(4, t);
+            if(W.step_commit()) {
+                if(W.prof) W.count_term_work();
+                W.step_terminated();
+            }
+        }
+        return took;
+    }
+    // profiling launches: what the two phases below have to do, for the general-step counters (wp_gen_count_phases)
+    if(W.prof) {
+        W.ph_need = 0; W.ph_chain = 0; W.ph_term = 0; W.ph_rows = 0;
+        if(act) W.count_prune_work();
+    }
+    // --- PrunedBySeedSupport: dealt, or in the walk's own lane ---
+    t = W.tick();
+    if(level >= kDealLevelPrune) deal_prune<X>(W, act, lane);
+    else if(act) W.PrunedBySeedSupport();
+    if(act) W.tock(4, t);
+    // --- the commit, in the walk's own lane (with the overflow branch and its terminated_leaf calls) ---
+    const bool committed = act && W.step_commit();
+    if(W.prof && committed) W.count_term_work();
+    // --- isTerminated over the new frontier: the scans dealt, or all of it in the walk's own lane ---
+    if(level >= kDealLevelTerm) {
+        const bool scan = committed && W.currentLength >= W.minLength;
+        if(X::ballot(scan)) {
+            t = W.tick();
+            deal_term<X>(W, scan, lane);
+            if(scan) W.tock(6, t);
+        }
+    } else if(committed) W.step_terminated();
     return took;
 }
 

@@ -74,6 +74,32 @@ __device__ __forceinline__ void wp_gen_count(unsigned long long* g, bool took, u
     }
 }
 
+// the same for the work of the step's PrunedBySeedSupport and isTerminated phases (Walk::count_prune_work / count_term_work):
+// g[3 k + 0] sum, g[3 k + 1] sum of the per-step maximum, g[3 k + 2] sum of (maximum x lanes taking part), for k = 0 children that
+// need the seed-support search, 1 chain entries they walk, 2 leaves that pass term_may_hit, 3 term rows they scan
+__device__ __forceinline__ void wp_gen_count_phases(unsigned long long* g, bool took, uint32_t need, uint32_t chain, uint32_t term, uint32_t rows)
+{
+    const uint64_t m = __ballot(took);
+    if(m == 0) return;
+    const uint32_t v[4] = {need, chain, term, rows};
+    uint32_t sum[4], mx[4];
+    for(int k = 0; k < 4; ++k) {
+        bool cand = took;
+        sum[k] = 0; mx[k] = 0;
+        for(int b = 23; b >= 0; --b) {
+            const bool bit = took && ((v[k] >> b) & 1u);
+            sum[k] += (uint32_t)__builtin_popcountll(__ballot(bit)) << b;
+            if(__ballot(cand && bit)) { mx[k] |= 1u << b; cand = cand && bit; }
+        }
+    }
+    if(threadIdx.x == (uint32_t)__builtin_ctzll(m))
+        for(int k = 0; k < 4; ++k) {
+            atomicAdd(&g[3 * k], (unsigned long long)sum[k]);
+            atomicAdd(&g[3 * k + 1], (unsigned long long)mx[k]);
+            atomicAdd(&g[3 * k + 2], (unsigned long long)mx[k] * (unsigned long long)__builtin_popcountll(m));
+        }
+}
+
 // ---- a walk's slot: setup and finish ----------------------------------------------------------------------------------------
 // the walk's fixed inputs: the query and the tables wp_prepare_kernel / wp_begin_kernel built in the slot's prepared workspace
 template <bool WIDE, bool BIG>
