@@ -112,6 +112,9 @@ Tunables lrsc::read_tunables(const lrsc_ctx* ctx)
     t.msa_force_global = std::getenv("LRSC_MSA_FORCE_GLOBAL") != nullptr;                    // off; on when set
     t.msa_lds_max = env_clamped("LRSC_MSA_LDS_MAX", 0, 1, kIntMax);                          // not set = the computed budget; bytes, at least 1
     { const char* e = std::getenv("LRSC_MSA_BATCH"); t.msa_batch = !(e && e[0] == '0'); }    // on; off when the value starts with 0
+    t.msa_waves = env_clamped("LRSC_MSA_WAVES", 0, 1, 8);                                    // not set = by launch (msa_buckets); 1, 2, 4, 8 (3 -> 2, 5..7 -> 4)
+    t.msa_waves = t.msa_waves >= 8 ? 8 : t.msa_waves >= 4 ? 4 : t.msa_waves;
+    if(t.msa_waves == 3) t.msa_waves = 2;
     t.profile = std::getenv("LRSC_CORRECT_PROFILE") != nullptr;                              // off; on when set
     t.wp_dump = std::getenv("LRSC_WP_DUMP") != nullptr;                                      // off; on when set (with LRSC_CORRECT_PROFILE)
     t.dp_debug = std::getenv("LRSC_DP_DEBUG") != nullptr;                                    // off; on when set

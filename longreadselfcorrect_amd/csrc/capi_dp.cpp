@@ -163,7 +163,7 @@ int DpStage::run(lrsc_ctx* ctx, const Tunables& tn, const uint8_t* d_query_codes
     HIP_TRY(hipMemcpyAsync(d_reqs.p, reqs.data(), (size_t)n * sizeof(DpRequest), hipMemcpyHostToDevice, ctx->stream));
     DpPipeArgs a{};
     a.codes = d_query_codes; a.reqs = d_reqs.p; a.n_reqs = n; a.ctr = ctx->d_ctr;
-    a.row_batch = tn.msa_batch;
+    a.row_batch = tn.msa_batch; a.msa_nw = 1;
     st = timed_launch(ctx, LRSC_K_LF, [&]() { return launch_dp_seeds(ctx->fm, a, ctx->stream); });
     if(st != LRSC_OK) return st;
     COPY_TRY(ctx, reqs.data(), d_reqs.p, (size_t)n * sizeof(DpRequest), hipMemcpyDeviceToHost);
@@ -265,27 +265,31 @@ struct DpStage::MsaLaunch {
 // The launches for the chunk's requests `todo`, one per non-empty bucket, and their request lists back to back in `lists`; returns
 // the bytes of global workspace the last bucket's launch needs (0: none).  A bucket holds the requests of which kWgsPerCu[..]
 // workgroups fit the LDS budget of a CU (lds_budget) and one more does not; what is beyond the budget goes to the global-workspace
-// variant.
+// variant.  Wavefronts per workgroup: `waves` where LRSC_MSA_WAVES sets it, else the bucket's own (kMsaWideWaves in the global launch
+// and in the bucket of two workgroups per CU, whose launches are shorter with them; 1 in the others).  A wide workgroup's
+// cross-wavefront words count towards its LDS, so a request is sized per bucket.
 uint64_t DpStage::msa_buckets(const std::vector<DpRequest>& reqs, const Chunk& ch, const std::vector<uint32_t>& todo, bool force_global,
-                              std::vector<MsaLaunch>& launches, std::vector<uint32_t>& lists) const
+                              uint32_t waves, std::vector<MsaLaunch>& launches, std::vector<uint32_t>& lists) const
 {
-    static const uint32_t kWgsPerCu[] = {20, 13, 10, 8, 6, 5, 4, 2, 1};
-    uint32_t buckets[sizeof(kWgsPerCu) / sizeof(kWgsPerCu[0]) + 1];
-    uint32_t nb = 0;
-    for(uint32_t w : kWgsPerCu) buckets[nb++] = (lds_budget / w) & ~15u;
-    buckets[nb++] = 0xFFFFFFFFu;
-    uint32_t lo = 0;
+    static const struct { uint32_t wgs_per_cu, waves; } kBuckets[] = {{20, 1}, {13, 1}, {10, 1}, {8, 1}, {6, 1}, {5, 1}, {4, 1},
+                                                                      {2, kMsaWideWaves}, {1, 1}, {0, kMsaWideWaves}};   // 0: the global-workspace launch
+    std::vector<uint8_t> taken(todo.size(), 0);
     uint64_t ws_bytes = 0;
-    for(uint32_t bk : buckets) {
-        if(force_global && bk != 0xFFFFFFFFu) continue;
+    for(const auto& b : kBuckets) {
+        const uint32_t w = b.wgs_per_cu;
+        if(force_global && w) continue;
+        const uint32_t bk = w ? (lds_budget / w) & ~15u : 0xFFFFFFFFu;
+        const uint32_t nw = waves ? waves : b.waves;
         const size_t first = lists.size();
-        uint32_t need_max = 0;
-        for(uint32_t i : todo) {
-            const DpRequest& r = reqs[ch.begin + i];
-            const uint32_t need = dp_msa_lds_bytes(r.w_cols, r.lq, r.str_cap, r.ops_cap, r.n_str);
-            if(need > lo && need <= bk) { lists.push_back(i); need_max = std::max(need_max, need); }
+        uint32_t need_max = 0, str_max = 0;
+        for(size_t t = 0; t < todo.size(); ++t) {
+            if(taken[t]) continue;
+            const DpRequest& r = reqs[ch.begin + todo[t]];
+            const uint32_t need = dp_msa_lds_bytes(r.w_cols, r.lq, r.str_cap, r.ops_cap, r.n_str, nw);
+            if(need > bk) continue;
+            taken[t] = 1;
+            lists.push_back(todo[t]); need_max = std::max(need_max, need); str_max = std::max(str_max, r.n_str);
         }
-        lo = bk;
         if(lists.size() == first) continue;
         // a launch hands its requests to the wavefronts round-robin: the biggest pile-ups (rows x columns) first, so that the
         // launch does not end on one of them
@@ -294,12 +298,14 @@ uint64_t DpStage::msa_buckets(const std::vector<DpRequest>& reqs, const Chunk& c
             const uint64_t wx = (uint64_t)rx.lq * rx.n_str, wy = (uint64_t)ry.lq * ry.n_str;
             return wx != wy ? wx > wy : x < y;
         });
-        MsaLaunch L{ch.args, first, bk == 0xFFFFFFFFu, 0};
+        MsaLaunch L{ch.args, first, w == 0, 0};
         for(size_t t = first; t < lists.size(); ++t) { const DpRequest& r = reqs[ch.begin + lists[t]]; L.work += (uint64_t)r.lq * r.n_str; }
         L.args.n_list = (uint32_t)(lists.size() - first);
         L.args.lds_bytes = (need_max + 15) & ~15u;
+        L.args.msa_nw = nw;
+        L.args.lds_small = dp_msa_small_bytes(str_max);
         if(L.global_ws) {
-            // one slot per wavefront of the launch: as many as its list has requests, or, where this bucket is the pass's first
+            // one slot per workgroup of the launch: as many as its list has requests, or, where this bucket is the pass's first
             // (nothing fits the LDS, or LRSC_MSA_FORCE_GLOBAL), as many as the chunk has (dp_msa_waves counts n_reqs without a list)
             DpPipeArgs sized = L.args;
             sized.req_list = first ? d_list.p : nullptr;
@@ -323,7 +329,7 @@ int DpStage::msa_chunk(lrsc_ctx* ctx, const Tunables& tn, std::vector<DpRequest>
     while(!todo.empty()) {
         std::vector<MsaLaunch> launches;
         std::vector<uint32_t> all_lists;
-        const uint64_t ws_bytes = msa_buckets(reqs, ch, todo, tn.msa_force_global, launches, all_lists);
+        const uint64_t ws_bytes = msa_buckets(reqs, ch, todo, tn.msa_force_global, tn.msa_waves, launches, all_lists);
         HIP_TRY(d_list.reserve(std::max<size_t>(all_lists.size(), 1)));
         if(ws_bytes) HIP_TRY(d_msa_ws.reserve(ws_bytes));
         HIP_TRY(hipMemcpyAsync(d_list.p, all_lists.data(), all_lists.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
@@ -359,6 +365,28 @@ int DpStage::msa_chunk(lrsc_ctx* ctx, const Tunables& tn, std::vector<DpRequest>
         });
         if(st != LRSC_OK) return st;
         COPY_TRY(ctx, mo.data(), d_msa.p + begin, (size_t)nc * sizeof(DpMsaOut), hipMemcpyDeviceToHost);
+        if(tn.profile) {
+            // a request's ticks are a difference of two counter reads; one that came out negative (seen once in 18 720 requests of a
+            // wide launch, not explained) counts as 0, so that it cannot pose as the launch's longest request
+            for(DpMsaOut& o : mo) if((int32_t)o.kc_total < 0) o.kc_total = 0;
+            // one line per launch: is it as long as its longest pile-up?
+            for(const MsaLaunch& L : launches) {
+                uint64_t sum = 0;
+                uint32_t top = all_lists[L.list_first];
+                for(uint32_t t = 0; t < L.args.n_list; ++t) {
+                    const uint32_t i = all_lists[L.list_first + t];
+                    sum += mo[i].kc_total;
+                    if(mo[i].kc_total > mo[top].kc_total) top = i;
+                }
+                const DpRequest& r = reqs[begin + top];
+                char where[24];
+                if(L.global_ws) std::snprintf(where, sizeof where, "global");
+                else std::snprintf(where, sizeof where, "LDS %u B", (unsigned)L.args.lds_bytes);
+                std::fprintf(stderr, "[lrsc] msa launch: %s, %u requests, %u workgroups of %u wavefronts, k-ticks sum %llu max %u (w_cols %u, n_str %u, n_rows %u)\n",
+                             where, (unsigned)L.args.n_list, (unsigned)dp_msa_waves(L.args, L.global_ws, lds_budget), (unsigned)L.args.msa_nw,
+                             (unsigned long long)sum, (unsigned)mo[top].kc_total, (unsigned)r.w_cols, (unsigned)r.n_str, (unsigned)mo[top].n_rows);
+            }
+        }
         redo.clear();
         for(uint32_t i : todo) {
             if(mo[i].error != 1) continue;                       // 0 = done; 2 = consensus beyond its capacity: stays an error of this request

@@ -103,6 +103,7 @@ struct Tunables {
     uint64_t dp_chunk_bytes;
     uint32_t dp_align_waves;
     bool msa_batch, msa_force_global;
+    uint32_t msa_waves;                    // LRSC_MSA_WAVES: wavefronts per MSA workgroup in every launch (0 = not set: chosen per launch)
     uint32_t msa_lds_max;                  // LRSC_MSA_LDS_MAX: upper bound of the MSA launches' LDS budget per CU (0 = not set)
 };
 
@@ -151,7 +152,7 @@ private:
     int msa_lds_budget(lrsc_ctx* ctx, const Tunables& tn, uint32_t* budget) const;
     int align_chunk(lrsc_ctx* ctx, const Tunables& tn, const std::vector<DpRequest>& reqs, const Chunk& ch, uint32_t lds_waves);
     uint64_t msa_buckets(const std::vector<DpRequest>& reqs, const Chunk& ch, const std::vector<uint32_t>& todo, bool force_global,
-                         std::vector<MsaLaunch>& launches, std::vector<uint32_t>& lists) const;
+                         uint32_t waves, std::vector<MsaLaunch>& launches, std::vector<uint32_t>& lists) const;
     int msa_chunk(lrsc_ctx* ctx, const Tunables& tn, std::vector<DpRequest>& reqs, const Chunk& ch);
 };
 

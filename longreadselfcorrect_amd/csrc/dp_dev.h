@@ -76,6 +76,8 @@ struct DpPipeArgs {
     uint8_t* msa_ws;              // set: state in this global workspace (lds_bytes per workgroup) instead of LDS
     uint32_t* work_ctr;           // optional, zeroed: the MSA kernel's wavefronts take their next request from it (after their first)
     uint32_t row_batch;           // MSA rows added in wavefront-wide passes (default); 0: the step-by-step walk only
+    uint32_t msa_nw;              // wavefronts per MSA workgroup of this launch: 1, 2, 4 or 8
+    uint32_t lds_small;           // msa_ws set and msa_nw > 1: dynamic LDS of the launch (dp_msa_small_bytes of its largest n_str)
     DevCounters* ctr;
 };
 
@@ -112,16 +114,24 @@ hipError_t launch_dp_align(const DpAlignArgs& a, uint32_t n_waves, hipStream_t s
 hipError_t launch_dp_seeds(const FmIndexDev& fm, const DpPipeArgs& a, hipStream_t stream);
 // lane per retrieved string: LF-walk (retrieveStr), writes the string in its final orientation and its DpJob
 hipError_t launch_dp_retrieve(const FmIndexDev& fm, const DpPipeArgs& a, hipStream_t stream);
-// wavefront per request: MultipleAlignment::addOverlap for every accepted overlap + calculateBaseConsensus
+// workgroup of a.msa_nw wavefronts per request: MultipleAlignment::addOverlap for every accepted overlap + calculateBaseConsensus
 // lds_per_cu: the LDS of a CU that the launch may count on (what other kernels in flight leave of it): sizes the grid
 hipError_t launch_dp_msa(const DpPipeArgs& a, uint32_t lds_per_cu, hipStream_t stream);
-uint32_t dp_msa_lds_bytes(uint32_t w_cols, uint32_t lq, uint32_t str_cap, uint32_t ops_cap, uint32_t n_str);
+// LDS of one pile-up in a workgroup of nw wavefronts (nw > 1: with the words the wavefronts exchange their prefix counts in)
+uint32_t dp_msa_lds_bytes(uint32_t w_cols, uint32_t lq, uint32_t str_cap, uint32_t ops_cap, uint32_t n_str, uint32_t nw = 1);
+// what a workgroup of several wavefronts keeps in LDS in the global-workspace variant too: the exchange words, the current row's
+// new columns and every row's lead / size
+uint32_t dp_msa_small_bytes(uint32_t n_str);
+// Where LRSC_MSA_WAVES does not say: wavefronts per workgroup in the launches that DpStage::msa_buckets runs wide (DESIGN.md
+// section 4b, "Wide pile-ups")
+constexpr uint32_t kMsaWideWaves = 4;
 // initial column capacity of one multiple alignment: the query plus the gap columns insertions may open
 constexpr uint32_t dp_msa_columns(uint32_t lq) { return 3 * lq + 128; }
 constexpr uint32_t dp_cons_capacity(uint32_t lq) { return 2 * lq + 128; }
 // bytes of LDS a compute unit has, and the granule in which it is handed to workgroups (gfx950: 160 KB in blocks of 320 dwords)
 constexpr uint32_t kLdsPerCu = 160u * 1024u, kLdsGranule = 1280u;
-// workgroups of an MSA launch: lds_per_cu / a.lds_bytes per CU (global: 8, they hold no LDS), at most one per request
+// workgroups of an MSA launch: lds_per_cu / a.lds_bytes per CU (global: 8, they hold no LDS), at most one per request; with
+// several wavefronts each, no more than fill the CU's 32 wavefront slots less one per SIMD (the long-gap launch beside it holds those)
 uint32_t dp_msa_waves(const DpPipeArgs& a, bool global, uint32_t lds_per_cu);
 
 } // namespace lrsc
