@@ -1,5 +1,5 @@
-"""The pile-up kernel with several wavefronts per multiple alignment (csrc/dp_msa.hip, msa_wide; DESIGN.md section 4b, "wide
-pile-ups") against the oracle's restatement of LongReadOverlap.cpp / multiple_alignment.cpp.
+"""The pile-up kernel with several wavefronts per multiple alignment (csrc/dp_msa.hip, msa_pileup<GLOBAL, NW> with NW > 1; DESIGN.md
+section 4b, "wide pile-ups") against the oracle's restatement of LongReadOverlap.cpp / multiple_alignment.cpp.
 
 LRSC_MSA_WAVES=2 / 4 / 8 gives every launch that many wavefronts per workgroup, so the few-hundred- to two-thousand-column pile-ups
 of the small set go through the code that the default keeps for pile-ups of thousands of columns.  The query lengths sit around
@@ -85,10 +85,12 @@ def test_wide_workgroups_match_oracle(api, gpu_index, queries, want, monkeypatch
 
 
 @pytest.mark.parametrize("force_global", [False, True], ids=["lds", "global"])
-def test_step_walk_inside_a_wide_workgroup(api, gpu_index, queries, want, monkeypatch, force_global):
-    """LRSC_MSA_BATCH=0: every row through the step walk, which one wavefront of the four runs while the others wait; in LDS and,
-    with its wavefront-level synchronisation on workspace memory, in the global variant."""
-    env = {"LRSC_MSA_WAVES": "4", "LRSC_MSA_BATCH": "0"}
+@pytest.mark.parametrize("waves", [1, 4])
+def test_step_walk_inside_a_wide_workgroup(api, gpu_index, queries, want, monkeypatch, waves, force_global):
+    """LRSC_MSA_BATCH=0: every row through the step walk (msa_row_walk), which one wavefront of the four runs while the others wait,
+    and which in a workgroup of one wavefront is the whole workgroup; in LDS and, with its wavefront-level synchronisation on
+    workspace memory, in the global variant."""
+    env = {"LRSC_MSA_WAVES": str(waves), "LRSC_MSA_BATCH": "0"}
     if force_global:
         env["LRSC_MSA_FORCE_GLOBAL"] = "1"
     got, walked = consensus(api, gpu_index, queries, monkeypatch, env)

@@ -2,8 +2,9 @@
 MultipleAlignment::_addSequence (Thirdparty/multiple_alignment.cpp:291-377) on adversarial random cigars -- CPU only.
 
 Both sides here are Python twins of the two paths inside dp_msa_kernel, written from the kernel's own statements: `add_row_walk`
-is the walk the kernel keeps for corner-case rows (itself pinned to the oracle's restatement of the reference by the GPU tests),
-`add_row_passes` the prefix-count formulation with the same fall-back conditions.  What this checks is the *derivation*: that in
+is the walk the kernel keeps for corner-case rows (msa_row_walk; itself pinned to the oracle's restatement of the reference by the
+GPU tests), `add_row_passes` the prefix-count formulation (msa_pileup's row in a workgroup of one wavefront) with the same
+fall-back conditions.  What this checks is the *derivation*: that in
 the base row's old coordinates every op's effect follows from prefix counts, and that insertGapBeforeColumn's effect on the other
 rows does not depend on the order of a row's insertions -- on cigars far nastier than an alignment ever produces (long I runs in
 and around existing gap columns, rows starting at base 0, rows ending behind the last base).  The HIP code itself is checked

@@ -1,7 +1,7 @@
-"""The pile-up kernel's passes in a workgroup of several wavefronts (csrc/dp_msa.hip, msa_wide) against the step-by-step cigar walk
--- CPU only, as tests/test_msa_row_passes.py holds the single-wavefront derivation.
+"""The pile-up kernel's passes in a workgroup of several wavefronts (csrc/dp_msa.hip, msa_pileup with NW > 1) against the
+step-by-step cigar walk -- CPU only, as tests/test_msa_row_passes.py holds the single-wavefront derivation.
 
-`add_row_wide` is a Python twin of msa_wide's row, written from the kernel's statements with the wavefront width and the number of
+`add_row_wide` is a Python twin of msa_pileup's row, written from the kernel's statements with the wavefront width and the number of
 wavefronts as parameters: every pass goes chunk by chunk of width x NW entries, every wavefront ballots its own `width` entries,
 posts its counts, and a thread adds up the wavefronts in front of its own; the carries (bases seen, M/D and M/I ops, new columns,
 the position behind the last M/D op) are the sums over all wavefronts.  At widths of 4 and 8 lanes and 1-4 wavefronts every
@@ -22,7 +22,8 @@ def popc_before(mask, lane):
 
 
 def add_row_wide(p, m0s, m1s, ops, S, stats, width, nw, shift_chunks=2, max_ins=256, drop_run_carry=False):
-    """msa_wide's row; False when the row must take the walk (nothing but scratch has been touched then)."""
+    """msa_pileup's row in a workgroup of nw wavefronts; False when the row must take the walk (nothing but scratch has been touched
+    then)."""
     NT = width * nw
     n_ops = len(ops)
     size_b = p.size_b
